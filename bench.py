@@ -5,12 +5,20 @@ A step = one full frame of the configured workload rendered from scene data alre
 HBM (BVH built and uploaded before timing). Ray = one closest-hit query (camera.rs:187), counted
 on the device by the kernel itself.
 
+A plain run (`bench.py --gpus N --steps K --warmup W`) does only what the headline figure needs:
+it sets up, warms up, times the K steps, writes the last step's frame when `--dump-outputs DIR` is
+given, and prints the contract line (metric, value, unit, ms_per_step, dtype, the config, the kernel
+and gather times). Everything else the benchmark measures takes runs of its own and sits behind
+`--full`: the instrumented work count and the `roofline` built on it, the wall-clock split, the
+CPU baseline, the C1 / 1-GPU C3 / f64 legs, the 1-GPU base of an N > 1 run (`scaling_efficiency`)
+and the opt-in reference slot. Under `--full` the `--no-*` options switch single legs off.
+
 * N = 1 (default): config C2, 1920x1080x512 spp (BASELINE.json configs[1], the metric's config),
-  the whole frame on one GPU, no gather. The line also carries a 1-GPU C3 frame (`c3_one_gpu`,
-  the strong-scaling base of the N > 1 runs), the C1 CPU-path config timed on the CPU and the
-  GPU (`c1`), the wall-clock split, the CPU baseline, and (opt-in, `--ref-slot`) the reference's
-  own GPU kernel (its CUDA_SOURCE built for gfx950, oracle/_ref) timed beside this backend on a
-  bounded sample of the same workload (`reference_gpu_slot`).
+  the whole frame on one GPU, no gather. With `--full` the line also carries a 1-GPU C3 frame
+  (`c3_one_gpu`, the strong-scaling base of the N > 1 runs), the C1 CPU-path config timed on the
+  CPU and the GPU (`c1`), the wall-clock split, the CPU baseline, and (opt-in, `--ref-slot`) the
+  reference's own GPU kernel (its CUDA_SOURCE built for gfx950, oracle/_ref) timed beside this
+  backend on a bounded sample of the same workload (`reference_gpu_slot`).
 * N > 1 (`python bench.py --gpus N` starts `python -m torch.distributed.run --nproc-per-node N
   bench.py --gpus N` as a child process before touching any device and forwards rank 0's line;
   under an external launcher WORLD_SIZE must equal N): config C3,
@@ -20,9 +28,18 @@ on the device by the kernel itself.
   all samples, and the
   float tiles are gathered to rank 0 over RCCL inside the timed step (`distributed.gather_rows`).
   Strong scaling: the frame is fixed, value = all ranks' rays / the max over ranks of the timed
-  wall-clock. The line carries each rank's kernel time, the gather time and the same frame on
-  rank 0's GPU alone (`c3_one_gpu`), so `scaling_efficiency` is in the line. `--split samples` is the opt-in weak-scaling mode (every rank renders the whole
-  frame over its own sample range; partial accums summed on rank 0 in rank order).
+  wall-clock. The line carries each rank's kernel time and the gather time, and with `--full` the
+  same frame on rank 0's GPU alone (`c3_one_gpu`), so `scaling_efficiency` is in the line, and the
+  f64 books kernel over the same split (`f64_books`). `--split samples` is the opt-in weak-scaling
+  mode (every rank renders the whole frame over its own sample range; partial accums summed on
+  rank 0 in rank order).
+
+`--dump-outputs DIR` writes what the timed path computed in its last step, as a caller receives it:
+`DIR/accum.npy`, the (H, W, 4) float accum of the frame (rank 0's gathered frame when N > 1), in
+the timed kernel's dtype. A frame above the size cap is written as a fixed seeded sample of its
+pixels, `accum.npy` (n, 4) with their flat pixel indices in `accum_pixels.npy`. The scene, the
+camera and every random stream are functions of the arguments alone, so two runs with the same
+arguments render the same inputs and their dumps compare element for element.
 """
 from __future__ import annotations
 
@@ -49,6 +66,8 @@ FLOP_PER_BOX_TEST = 12  # aabb.rs:56-82 with hoisted reciprocal
 BYTES_PER_SPHERE_TEST = 16
 BYTES_PER_NODE_VISIT = 56  # per BVH2 node visit: two child boxes (2 x 24 B) + two links (2 x 4 B)
 BAND_ROWS = 16
+DUMP_CAP_BYTES = 48 << 20  # --dump-outputs: what one run may write (C2's f32 frame is 33 MB)
+DUMP_SEED = 0x5EED
 SCENES = {
     "C1": "three-sphere Lambertian scene (books CPU path)",
     "C2": "RTOW final scene (gpu/mod.rs generator, seed 0x5EED1234)",
@@ -70,6 +89,15 @@ def parse(argv=None):
                          "weak scaling")
     ap.add_argument("--width", type=int, default=None)
     ap.add_argument("--spp", type=int, default=None)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other leg: the instrumented work count and the "
+                         "roofline, the wall-clock split, the CPU baseline, the C1 / 1-GPU C3 / f64 legs, the 1-GPU "
+                         "base of an N > 1 run (the --no-* options below switch single legs off); a plain run does "
+                         "none of them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's frame to DIR/accum.npy (float32, or float64 "
+                         f"with --f64; above {DUMP_CAP_BYTES >> 20} MB a fixed seeded sample of its pixels, their "
+                         "flat indices in DIR/accum_pixels.npy)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the CPU baseline sample")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-breakdown", action="store_true", help="skip the wall-clock split (one extra frame)")
@@ -79,14 +107,36 @@ def parse(argv=None):
                     help="time the f64 books kernel (RRT_FLAG_F64, bit-identical to the books path) as the headline "
                          "leg instead of the f32 kernel: value, dtype f64, the same band split and gather")
     ap.add_argument("--ref-slot", action="store_true",
-                    help="also time the reference's own GPU kernel on a bounded sample (reference_gpu_slot; opt-in: "
-                         "a third-party kernel, kept out of the default run)")
+                    help="with --full, also time the reference's own GPU kernel on a bounded sample "
+                         "(reference_gpu_slot; opt-in: a third-party kernel, kept out of the --full run's defaults)")
     ap.add_argument("--issue-json", default=None,
                     help="issue-side PMC record (tools/pmc_issue.py); default profiles/issue_<config>.json")
     ap.add_argument("--traffic-json", default=None,
                     help="per-launch HBM bytes from rocprofv3 PMC passes (tools/pmc_traffic.py); "
                          "default profiles/traffic_<config>.json")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
+
+
+def dump_outputs(out_dir, frame):
+    """--dump-outputs: the last timed step's frame (a torch tensor (H, W, 4), f32 or f64, on the
+    device or the host) as out_dir/accum.npy. A frame above DUMP_CAP_BYTES is written as a sample:
+    the pixels default_rng(DUMP_SEED) draws without replacement, sorted, as accum.npy (n, 4), and
+    their flat indices (row * W + column, exact in float64) as accum_pixels.npy."""
+    import numpy as np
+
+    host = frame.detach().cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    pixel_bytes = 4 * host.itemsize
+    n_pixels = host.shape[0] * host.shape[1]
+    if n_pixels * pixel_bytes > DUMP_CAP_BYTES:
+        n = DUMP_CAP_BYTES // (pixel_bytes + 8)  # + 8: the pixel's float64 index
+        pick = np.sort(np.random.default_rng(DUMP_SEED).choice(n_pixels, size=n, replace=False))
+        host = host.reshape(n_pixels, 4)[pick]
+        np.save(os.path.join(out_dir, "accum_pixels.npy"), pick.astype(np.float64))
+    np.save(os.path.join(out_dir, "accum.npy"), np.ascontiguousarray(host))
 
 
 def launcher_command(args, argv, env):
@@ -595,6 +645,57 @@ def load_issue(path, config, W, S, lib_path):
                         f"VALU wave-instructions / (1024 SIMDs x cycles)"}
 
 
+def work_and_roofline(ds, tile, scene, config, whole_frame, f64, avg_kernel_s, args):
+    """--full: the timed tile once more through the instrumented twin kernel (same paths, per-launch
+    work counts) and the headline leg's roofline record over the timed steps' average kernel time.
+    Returns (work counts, roofline)."""
+    import rustraytrace_amd as rrt
+
+    W, S = scene.width, scene.spp
+    work = ds.count_work(tile)
+    flops = FLOP_PER_SPHERE_TEST * work["sphere_tests"] + FLOP_PER_BOX_TEST * work["box_tests"]
+    achieved = flops / avg_kernel_s / 1e12
+    alg_bytes = BYTES_PER_SPHERE_TEST * work["sphere_tests"] + BYTES_PER_NODE_VISIT * work["node_visits"]
+    traffic_json = args.traffic_json or os.path.join(ROOT, "profiles", f"traffic_{config}.json")
+    traffic, traffic_src = (None, None)
+    issue = None
+    if whole_frame and not f64:  # the PMC records are of a whole-frame f32 launch
+        traffic, traffic_src = load_traffic(traffic_json, config, W, S, rrt._lib.LIB_PATH)
+        issue = load_issue(args.issue_json or os.path.join(ROOT, "profiles", f"issue_{config}.json"), config, W, S,
+                           rrt._lib.LIB_PATH)
+    peak = PEAK_F64_VALU_TFLOPS if f64 else PEAK_F32_VALU_TFLOPS
+    roofline = {
+        "bound": "valu",
+        "achieved": round(achieved, 3),
+        "peak": peak,
+        "unit": "TFLOP/s",
+        "frac": round(achieved / peak, 4),
+        "traffic": traffic,
+        "traffic_source": traffic_src,
+        "hbm_GBps": round(traffic / avg_kernel_s / 1e9, 2) if traffic else None,
+        "hbm_frac": round(traffic / avg_kernel_s / 1e9 / PEAK_HBM_GBPS, 5) if traffic else None,
+        "hbm_note": "measured HBM bytes per launch (PMC) / average kernel time, against 8 TB/s; the scene "
+                    "is read from LDS (C2/C4) or L2 (C5), so HBM is not the bound",
+        "algorithmic_flop_per_launch": flops,
+        "algorithmic_scene_bytes_per_launch": alg_bytes,
+        "lds_l2_scene_read_GBps_algorithmic": round(alg_bytes / avg_kernel_s / 1e9, 1),
+        "note": "f32 VALU issue bound (SURVEY 8d): 23 FLOP/sphere test + 12 FLOP/box test over the "
+                "average HIP-event kernel time; peak = wave64 v_fma_f32 at 2 cycles on SIMD-32 "
+                "(SURVEY 8d's 78.6 assumed 16-lane SIMDs). lds_l2_scene_read_GBps_algorithmic = "
+                "(16 B/sphere test + 56 B/node visit) / kernel time: scene reads served by LDS/L2, not HBM",
+    }
+    if f64:
+        roofline["note"] = ("f64 VALU issue bound: the books path's 23 FLOP per sphere test + 12 FLOP per box test "
+                            "(SURVEY 8d), all f64 in the reference, over the average HIP-event time of the frame; "
+                            "peak = MI355X FP64 vector 78.6 TFLOP/s (half the FP32 rate)")
+    if scene.quads is not None or scene.media is not None:
+        roofline["note"] += (" Book-2 scene: the kernel's primitive-test count (spheres, quads, medium boundaries) "
+                             "is priced at the sphere test's 23 FLOP / 16 B.")
+    if issue:  # the binding limit: VALU issue slots and lanes per instruction (FLOP frac is low by construction)
+        roofline.update(issue)
+    return work, roofline
+
+
 def device_shortfall(backend: str, local_rank: int, n_devices: int):
     """Under RCCL each rank owns GPU `local_rank`: a box with fewer devices cannot run the job, so
     the rank stops with this message before init_process_group (where it would wait in the
@@ -702,6 +803,8 @@ def main():
     gather_ms = [a.elapsed_time(b) for a, b in zip(k_end, g_end)] if world > 1 else None
     ctr = ds.counters()
     rays = ctr["rays"]
+    if args.dump_outputs and rank == 0:  # before any other leg touches the device
+        dump_outputs(args.dump_outputs, accum[:rows] if world == 1 else image[0])
     kmax = float(np.mean(kernel_ms))
     rank_kernel_ms = [kmax]
     one_gpu = None
@@ -713,31 +816,20 @@ def main():
         elapsed, kmax = float(every[:, 0].max()), float(every[:, 1].max())
         rank_kernel_ms = [float(v) for v in every[:, 1]]
         rays = int(every[:, 2].sum())
-        if rank == 0 and bands and not args.no_extra:
+        if rank == 0 and bands and args.full and not args.no_extra:
             # the strong-scaling base on this node: the same frame on rank 0's GPU alone, after the
             # timed region (the other ranks wait at the barrier below)
             one_gpu = one_gpu_frame_f64(scene, device) if f64 else one_gpu_frame(config, kw, device)
         dist.barrier()
     f64_leg = None
-    if world > 1 and bands and not f64 and not args.no_f64 and config in ("C1", "C2", "C3", "C4", "C5"):
+    if world > 1 and args.full and bands and not f64 and not args.no_f64 and config in ("C1", "C2", "C3", "C4", "C5"):
         # the path that meets the north star's bar, over the same split (after the f32 leg's timed
         # steps; its own barrier-bracketed timing and max over ranks)
         f64_leg = f64_band_leg(scene, config, band, rank, world, device, backend, dist,
                                steps=max(1, min(args.steps, 3)), warmup=1, base=not args.no_extra)
 
     if rank == 0:
-        work = ds.count_work(tile)  # instrumented twin kernel: same paths, per-launch work counts
         avg_kernel_s = float(np.mean(kernel_ms)) / 1e3
-        flops = FLOP_PER_SPHERE_TEST * work["sphere_tests"] + FLOP_PER_BOX_TEST * work["box_tests"]
-        achieved = flops / avg_kernel_s / 1e12
-        alg_bytes = BYTES_PER_SPHERE_TEST * work["sphere_tests"] + BYTES_PER_NODE_VISIT * work["node_visits"]
-        traffic_json = args.traffic_json or os.path.join(ROOT, "profiles", f"traffic_{config}.json")
-        traffic, traffic_src = (None, None)
-        issue = None
-        if rows == H and not f64:  # the PMC records are of a whole-frame f32 launch
-            traffic, traffic_src = load_traffic(traffic_json, config, W, S, rrt._lib.LIB_PATH)
-            issue = load_issue(args.issue_json or os.path.join(ROOT, "profiles", f"issue_{config}.json"), config, W, S,
-                               rrt._lib.LIB_PATH)
         if bands:
             split = (f"{band}-row bands dealt in serpentine order over {world} rank(s), RCCL gather of the float tiles "
                      f"to rank 0 inside the timed step" if world > 1 else
@@ -749,36 +841,6 @@ def main():
             split += " (gloo rehearsal: ranks share a GPU, host copies)"
         if f64:
             split += "; f64 books kernel (RRT_FLAG_F64), f64 tiles"
-        peak = PEAK_F64_VALU_TFLOPS if f64 else PEAK_F32_VALU_TFLOPS
-        roofline = {
-            "bound": "valu",
-            "achieved": round(achieved, 3),
-            "peak": peak,
-            "unit": "TFLOP/s",
-            "frac": round(achieved / peak, 4),
-            "traffic": traffic,
-            "traffic_source": traffic_src,
-            "hbm_GBps": round(traffic / avg_kernel_s / 1e9, 2) if traffic else None,
-            "hbm_frac": round(traffic / avg_kernel_s / 1e9 / PEAK_HBM_GBPS, 5) if traffic else None,
-            "hbm_note": "measured HBM bytes per launch (PMC) / average kernel time, against 8 TB/s; the scene "
-                        "is read from LDS (C2/C4) or L2 (C5), so HBM is not the bound",
-            "algorithmic_flop_per_launch": flops,
-            "algorithmic_scene_bytes_per_launch": alg_bytes,
-            "lds_l2_scene_read_GBps_algorithmic": round(alg_bytes / avg_kernel_s / 1e9, 1),
-            "note": "f32 VALU issue bound (SURVEY 8d): 23 FLOP/sphere test + 12 FLOP/box test over the "
-                    "average HIP-event kernel time; peak = wave64 v_fma_f32 at 2 cycles on SIMD-32 "
-                    "(SURVEY 8d's 78.6 assumed 16-lane SIMDs). lds_l2_scene_read_GBps_algorithmic = "
-                    "(16 B/sphere test + 56 B/node visit) / kernel time: scene reads served by LDS/L2, not HBM",
-        }
-        if f64:
-            roofline["note"] = ("f64 VALU issue bound: the books path's 23 FLOP per sphere test + 12 FLOP per box test "
-                                "(SURVEY 8d), all f64 in the reference, over the average HIP-event time of the frame; "
-                                "peak = MI355X FP64 vector 78.6 TFLOP/s (half the FP32 rate)")
-        if scene.quads is not None or scene.media is not None:
-            roofline["note"] += (" Book-2 scene: the kernel's primitive-test count (spheres, quads, medium boundaries) "
-                                 "is priced at the sphere test's 23 FLOP / 16 B.")
-        if issue:  # the binding limit: VALU issue slots and lanes per instruction (FLOP frac is low by construction)
-            roofline.update(issue)
         out = {
             "metric": METRIC,
             "value": round(rays / elapsed / 1e6, 2),
@@ -803,14 +865,15 @@ def main():
             },
             "wall_clock_s_per_frame": round(elapsed / args.steps, 4),
             "rays_per_step": rays // args.steps,
-            "rank0_rays_per_launch": work["rays"],
-            "rank0_paths_per_launch": work["paths"],
-            "sphere_tests_per_s": round(work["sphere_tests"] / avg_kernel_s, 1),
             "kernel_ms_avg": round(avg_kernel_s * 1e3, 3),
             "kernel_ms_max_over_ranks": round(kmax, 3),
             "bvh": ds.bvh_info(),
-            "roofline": roofline,
         }
+        if args.full:  # the instrumented twin kernel (a launch of its own) and the roofline built on its counts
+            work, out["roofline"] = work_and_roofline(ds, tile, scene, config, rows == H, f64, avg_kernel_s, args)
+            out["rank0_rays_per_launch"] = work["rays"]
+            out["rank0_paths_per_launch"] = work["paths"]
+            out["sphere_tests_per_s"] = round(work["sphere_tests"] / avg_kernel_s, 1)
         if gather_ms is not None:
             out["gather_ms"] = round(float(np.mean(gather_ms)), 3)
             out["gather_note"] = "rank 0, HIP events between the end of its render and the end of the gather"
@@ -827,18 +890,19 @@ def main():
                                        "after the timed steps)")
         if f64_leg is not None:
             out["f64_books"] = f64_leg
-        if world == 1 and not args.no_breakdown and not f64:
+        legs = world == 1 and args.full  # a plain run ends here: none of the legs below
+        if legs and not args.no_breakdown and not f64:
             out["wall_clock_breakdown"] = wall_clock_breakdown(scene, accum, avg_kernel_s * 1e3)
-        cpus = host_cpus()
-        if world == 1 and not args.no_extra and not f64:
+        cpus = host_cpus() if legs else None
+        if legs and not args.no_extra and not f64:
             if config != "C3":
                 out["c3_one_gpu"] = one_gpu_frame("C3")
             out["c1"] = c1_timings(cpus)
-        if world == 1 and not args.no_f64 and not f64 and config in ("C1", "C2", "C4", "C5"):
+        if legs and not args.no_f64 and not f64 and config in ("C1", "C2", "C4", "C5"):
             out["f64_books"] = f64_books_frame(config)
-        if world == 1 and args.ref_slot and config in ("C1", "C2", "C5"):
+        if legs and args.ref_slot and config in ("C1", "C2", "C5"):
             out["reference_gpu_slot"] = reference_gpu_slot(config)
-        if world == 1 and not args.no_cpu_baseline:
+        if legs and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(scene, args.cpu_seconds, cpus)
         print(json.dumps(out), flush=True)
     ds.close()

@@ -80,7 +80,7 @@ def test_bench_f64_band_leg():
     per-rank kernel times, gather, 1-GPU base), 2 ranks sharing the GPU over gloo; and `--f64` makes
     the f64 kernel the timed headline leg (dtype f64)."""
     base = ["bench.py", "--gpus", "2", "--config", "C3", "--width", "256", "--spp", "8", "--steps", "2",
-            "--warmup", "1", "--no-cpu-baseline", "--no-breakdown"]
+            "--warmup", "1", "--full", "--no-cpu-baseline", "--no-breakdown"]
     env = dict(os.environ, RRT_BENCH_BACKEND="gloo", OMP_NUM_THREADS="1")
     scene = rrt.config_scene("C3", image_width=256, samples_per_pixel=8)
     ds = rrt.DeviceScene(scene, f64=True)
@@ -136,9 +136,9 @@ def test_bench_band_split_line(ranks):
 def test_bench_spawns_its_own_ranks():
     # `python bench.py --gpus 2` with no external launcher: bench.py starts torch.distributed.run as
     # a child (2 ranks sharing this GPU over gloo), forwards rank 0's line, and the N > 1 line
-    # carries the per-rank kernel times, the gather time and the same frame on one GPU.
+    # carries the per-rank kernel times, the gather time and (--full) the same frame on one GPU.
     args = ["bench.py", "--gpus", "2", "--config", "C3", "--width", "256", "--spp", "8", "--steps", "2",
-            "--warmup", "1", "--no-cpu-baseline", "--no-breakdown"]
+            "--warmup", "1", "--full", "--no-cpu-baseline", "--no-breakdown"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(RRT_BENCH_BACKEND="gloo", OMP_NUM_THREADS="1")
     r = subprocess.run([sys.executable] + args, capture_output=True, text=True, cwd=ROOT, env=env, timeout=110)

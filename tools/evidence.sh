@@ -19,17 +19,17 @@ if [[ $STEPS == *suite* ]]; then
   run smoke 300 python3 -c "import __graft_entry__ as g; g.smoke()"
 fi
 if [[ $STEPS == *bench* ]]; then
-  run bench 600 python3 bench.py
+  run bench 600 python3 bench.py --full
   tail -n 1 gpurun_out/bench.log > gpurun_out/profiles/${TAG}_bench_full.json
   for c in C4 C5 NW9; do
-    run bench_$c 300 python3 bench.py --config $c --no-extra --no-cpu-baseline --no-breakdown
+    run bench_$c 300 python3 bench.py --config $c --full --no-extra --no-cpu-baseline --no-breakdown
     tail -n 1 gpurun_out/bench_$c.log > gpurun_out/profiles/${TAG}_bench_$c.json
   done
 fi
 if [[ $STEPS == *multi* ]]; then  # full-size rehearsals of the N > 1 legs on one GPU
-  run bench_C3_f64 600 python3 bench.py --config C3 --f64 --steps 2 --warmup 1 --no-cpu-baseline --no-breakdown
+  run bench_C3_f64 600 python3 bench.py --config C3 --f64 --steps 2 --warmup 1 --full --no-cpu-baseline --no-breakdown
   tail -n 1 gpurun_out/bench_C3_f64.log > gpurun_out/profiles/${TAG}_bench_C3_f64.json
-  run bench_gpus2_gloo 900 env RRT_BENCH_BACKEND=gloo python3 bench.py --gpus 2 --steps 2 --warmup 1 --no-cpu-baseline
+  run bench_gpus2_gloo 900 env RRT_BENCH_BACKEND=gloo python3 bench.py --gpus 2 --steps 2 --warmup 1 --full --no-cpu-baseline
   tail -n 1 gpurun_out/bench_gpus2_gloo.log > gpurun_out/profiles/${TAG}_bench_gpus2_gloo_rehearsal.json
 fi
 if [[ $STEPS == *stats* ]]; then

@@ -20,5 +20,5 @@ run traffic_c5 60 python3 tools/pmc_traffic.py gpurun_out/traffic_fetch_c5 gpuru
 cp profiles/traffic_C5.json gpurun_out/profiles/traffic_C5.json
 run kstats_c5 300 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_c5_$TAG -o run --output-format csv -- python3 tools/prof_render.py --config C5 --spp 64 --iters 2
 run rocprof_stats 600 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_$TAG -o run --output-format csv -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline
-run bench_full 900 python3 bench.py
+run bench_full 900 python3 bench.py --full
 cp gpurun_out/bench_full.log gpurun_out/profiles/bench_$TAG.json
