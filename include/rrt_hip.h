@@ -561,9 +561,40 @@ void rrt_testing_device_wrap(int32_t on);
  * (RRT_FLAG_F64) stages a scene that fits its block — bit 0: f64-widened sphere records, bit 1: the
  * 1/r table, bit 2: the f32 pre-test records beside widened ones (with bit 0) — instead of its
  * automatic choice; -1 (the default at every load) restores it. A forced layout over the block's
- * 64 KB fails the render. Every layout renders the same bits (tests/test_gpu_books64.py).
+ * 64 KB fails scene creation and the render. Every layout renders the same bits (tests/test_gpu_books64.py).
  * Process-wide. */
 void rrt_testing_f64_layout(int32_t layout);
+
+/* Test support, not part of the drop-in (no reference counterpart; RRT_ABI_VERSION is unchanged and
+ * the Rust shim does not bind it): the launch shape the library picks for a scene, computed on the
+ * host from the scene's counts alone by the code the render launches and rrt_scene_create use. No
+ * device is needed (tests/test_launch_plan.py).
+ * Query: n_nodes, n_prims and stack_depth (BVH depth + 1) as rrt_build_bvh reports them; node_stride
+ * 80 (BVH2 staged in LDS), 32 (BVH2 read from global memory) or 128 (the width-4 tree, staged when
+ * bvh4_in_lds); book 0 (book 1), 2 (the scene has book-2 data: motion, quads, media, checker / noise
+ * materials) or 3 (RRT_FLAG_BOOK3); specular / image_tex: some material is metal or dielectric /
+ * image-textured; n_perlin, n_media, n_quads as in RrtSceneExt; f64: RRT_FLAG_F64; min_waves /
+ * global_waves: 0 for the defaults (the RRT_MIN_WAVES / RRT_GLOBAL_WAVES overrides otherwise).
+ * Result: ok = 0 when rrt_scene_create refuses such a scene (no launch shape), else the kernel class
+ * (f32: -2 diffuse, -1 untextured, 0 full book 1, 1-3 book 2 spheres / quads / media, 4 book 3; f64:
+ * 0 full, 1 untextured, 2 diffuse), its block (threads, launch-bounds waves per SIMD, 1 = none),
+ * bytes per stack entry, what is staged in LDS, the block's dynamic LDS bytes, and raise_limit = 1
+ * when those exceed 64 KiB and the launch raises the kernel's dynamic-LDS limit (at most 160 KiB). */
+typedef struct RrtLaunchPlanQuery {
+    uint32_t n_nodes, n_prims, stack_depth, node_stride;
+    uint32_t book, specular, image_tex, n_perlin;
+    uint32_t n_media, n_quads, f64, bvh4_in_lds;
+    uint32_t min_waves, global_waves, _pad[2];
+} RrtLaunchPlanQuery;
+typedef struct RrtLaunchPlan {
+    uint32_t ok, f64;
+    int32_t kernel_class, shape;
+    uint32_t stack_bytes, threads, waves, waves_noise_free;
+    uint32_t scene_in_lds, perlin_in_lds, inv_r_in_lds, rec32_in_lds;
+    uint32_t raise_limit, _pad;
+    uint64_t lds_bytes;
+} RrtLaunchPlan;
+int32_t rrt_testing_launch_plan(const RrtLaunchPlanQuery *query, RrtLaunchPlan *plan);
 
 /* Test support, not part of the drop-in: runs the f32 kernel's short reciprocal (v_rcp_f32 + one
  * fma Newton step) and short square root over every f32 bit pattern against the IEEE results;

@@ -46,6 +46,8 @@ def load() -> ctypes.CDLL:
     lib.oracle_render_kbvh.restype = c_int
     lib.oracle_render_kbvh.argtypes = [P, P, c_uint32, P, c_uint32, P, c_uint32, P, c_uint32, P, c_uint32, c_uint32, P,
                                        c_uint32, c_uint32, c_uint32, c_uint32, c_uint32, c_int, P, P, P, c_uint32]
+    lib.oracle_kbvh_stack_peak.restype = c_uint32
+    lib.oracle_kbvh_stack_peak.argtypes = []
     lib.oracle_sin_f32.restype = None
     lib.oracle_sin_f32.argtypes = [c_uint32, P, P]
     lib.oracle_cos_f32.restype = None
@@ -211,6 +213,13 @@ def render_kbvh(scene, nodes, order, layout, rows=None, samples=None, threads=1,
     if rc != 0:
         raise RuntimeError(f"oracle_render_kbvh failed ({rc})")
     return accum, rays.value, tests.value
+
+
+def kbvh_stack_peak():
+    """The deepest live stack entry (largest stack pointer after a push) of render_kbvh's walks since
+    the last call, which resets it. The kernel's walk pushes at the same steps, so this is the
+    number of LDS stack slots a GPU render of the same tree writes and reads back."""
+    return int(load().oracle_kbvh_stack_peak())
 
 
 def rtow_scene(seed=0x5EED_1234, grid_half=11):

@@ -859,6 +859,10 @@ static inline float half_to_float(uint16_t h) {
         out = nr_ < fr_;                                                                                           \
     } while (0)
 
+// The deepest live stack entry of any kbvh_hit walk since the last oracle_kbvh_stack_peak(): the
+// largest sp after a push (renders run on several threads: an atomic max, once per ray).
+std::atomic<uint32_t> g_kbvh_stack_peak{0};
+
 // std::fmaf is a slow libm call without -mfma: clone the traversal for FMA-capable hosts
 // (results are identical either way: fmaf is correctly rounded in both).
 __attribute__((target_clones("fma", "default")))
@@ -884,7 +888,7 @@ bool kbvh_hit(const World<float> &w, const KTree &kt, Vec3<float> o, Vec3<float>
         }
     };
     int32_t stack[128];
-    int sp = 0;
+    int sp = 0, peak = 0;
     int32_t node = 0;
     for (;;) {
         if (kt.width == 2) {
@@ -923,6 +927,7 @@ bool kbvh_hit(const World<float> &w, const KTree &kt, Vec3<float> o, Vec3<float>
             if (h0 && h1) {
                 const bool first1 = tn1 < tn0;
                 stack[sp++] = first1 ? l[0] : l[1];
+                peak = sp > peak ? sp : peak;
                 node = first1 ? l[1] : l[0];
                 continue;
             }
@@ -959,10 +964,14 @@ bool kbvh_hit(const World<float> &w, const KTree &kt, Vec3<float> o, Vec3<float>
             if (key[3] < inf) stack[sp++] = idx[3];
             if (key[2] < inf) stack[sp++] = idx[2];
             if (key[1] < inf) stack[sp++] = idx[1];
+            peak = sp > peak ? sp : peak;
             if (key[0] < inf) { node = idx[0]; continue; }
         }
         if (sp == 0) break;
         node = stack[--sp];
+    }
+    for (uint32_t seen = g_kbvh_stack_peak.load(std::memory_order_relaxed);
+         (uint32_t)peak > seen && !g_kbvh_stack_peak.compare_exchange_weak(seen, (uint32_t)peak, std::memory_order_relaxed);) {
     }
     if (hit < 0) return false;
     rec = Hit<float>{closest, (int32_t)kt.order[hit]};
@@ -1849,6 +1858,10 @@ int oracle_render_kbvh(const RrtCamera *cam, const RrtSphere *s, uint32_t n, con
     return render<float>(cam, s, n, m, nm, tex, ntex, ext, flags, 0, y0, y1, s0, s1, threads, accum, rays, sphere_tests,
                          chunk, &kt);
 }
+
+// The deepest live traversal-stack entry (the largest sp after a push) of the KBVH walks since the
+// last call; the call resets it to 0.
+uint32_t oracle_kbvh_stack_peak(void) { return g_kbvh_stack_peak.exchange(0); }
 
 // gpu::build_in_one_weekend_scene's sphere/material list (no overrides, camera seed out).
 int oracle_rtow_scene(uint64_t seed, int grid_half, float *center_radius, uint32_t *mat_index, float *albedo_fuzz,

@@ -80,6 +80,7 @@ EXPORTED_SYMBOLS = (
     "rrt_quantize_accum_books_f64",
     "rrt_testing_device_wrap",
     "rrt_testing_f64_layout",
+    "rrt_testing_launch_plan",
     "rrt_testing_recip_check",
     "rrt_testing_trig32_check",
     "rrt_testing_sqrt64_check",
@@ -186,6 +187,33 @@ class RrtBvhInfo(ctypes.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_ if not k.startswith("_")}
 
 
+class RrtLaunchPlanQuery(ctypes.Structure):  # include/rrt_hip.h, test support
+    _fields_ = [(f, c_uint32) for f in ("n_nodes", "n_prims", "stack_depth", "node_stride", "book", "specular",
+                                        "image_tex", "n_perlin", "n_media", "n_quads", "f64", "bvh4_in_lds",
+                                        "min_waves", "global_waves")] + [("_pad", c_uint32 * 2)]
+
+
+class RrtLaunchPlan(ctypes.Structure):  # include/rrt_hip.h, test support
+    _fields_ = [("ok", c_uint32), ("f64", c_uint32), ("kernel_class", c_int32), ("shape", c_int32)] + [
+        (f, c_uint32) for f in ("stack_bytes", "threads", "waves", "waves_noise_free", "scene_in_lds", "perlin_in_lds",
+                                "inv_r_in_lds", "rec32_in_lds", "raise_limit", "_pad")] + [("lds_bytes", c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_ if not k.startswith("_")}
+
+
+def launch_plan(**query) -> dict:
+    """rrt_testing_launch_plan (test support): the launch shape for a scene given by its counts
+    (RrtLaunchPlanQuery fields as keywords); {"ok": 0} when scene creation would refuse it."""
+    q, out = RrtLaunchPlanQuery(), RrtLaunchPlan()
+    for k, v in query.items():
+        if not hasattr(q, k) or k.startswith("_"):
+            raise KeyError(f"unknown launch-plan query field {k!r}")
+        setattr(q, k, int(v))
+    check(load().rrt_testing_launch_plan(ctypes.byref(q), ctypes.byref(out)))
+    return out.as_dict()
+
+
 class RrtError(RuntimeError):
     """A non-zero return of the C-ABI (the Rust shim's Err(rrt_hip_last_error()))."""
 
@@ -259,6 +287,7 @@ def load() -> ctypes.CDLL:
         "rrt_quantize_accum_books_f64": (c_int32, [c_uint32, c_uint32, P, c_uint32, P]),
         "rrt_testing_device_wrap": (None, [c_int32]),
         "rrt_testing_f64_layout": (None, [c_int32]),
+        "rrt_testing_launch_plan": (c_int32, [P, P]),
         "rrt_testing_recip_check": (c_int32, [P]),
         "rrt_testing_trig32_check": (c_int32, [P]),
         "rrt_testing_sqrt64_check": (c_int32, [P]),

@@ -1574,14 +1574,95 @@ size_t f64_lds_min_bytes(uint32_t n_nodes, uint32_t n_prims, uint32_t stack_dept
 
 namespace {
 
+// rrt_testing_f64_layout: a forced LDS layout (bit 0: widened Sphere64 records, bit 1: the 1/r table,
+// bit 2: the f32 pre-test records beside widened ones), or -1 for the automatic choice below
+std::atomic<int> g_f64_layout{-1};
+
+#ifndef RRT_F64_CLASSES
+#define RRT_F64_CLASSES 1
+#endif
+#ifndef RRT_F64_WIDE_SPHERES
+#define RRT_F64_WIDE_SPHERES 1
+#endif
+#ifndef RRT_F64_PREFER_F32REC
+#define RRT_F64_PREFER_F32REC 0
+#endif
+
+}  // namespace
+
+// The f64 launch plan (rrt_internal.h LaunchPlan): the class by the materials present, its block,
+// and the scene placement: the f32 nodes, spheres and materials in LDS when they fit (C1, C2, C4),
+// else the f16 nodes and records from global memory (C5).
+LaunchPlan plan_launch_f64(const KParams &p) {
+    LaunchPlan pl{};
+    pl.f64 = 1u;
+    if (p.bvh_width != 2 || p.prim_motion || p.stack_depth > (uint32_t)kMaxStackDepth || p.n_nodes > 65535u)
+        return pl;  // the host builds a 16-bit-stack BVH2 for book-1 scenes
+    const int cls = RRT_F64_CLASSES && !p.specular ? kF64Diffuse : RRT_F64_CLASSES && !p.image_tex ? kF64Untextured : kF64Full;
+    const int B = blk64(cls);
+    KParams q = p;
+    q.rec32_in_lds = 0u;
+    q.inv_r_in_lds = 0u;
+    int mode = kF64Global;
+    if (p.scene_in_lds) {
+        mode = -1;
+        if (const int lay = g_f64_layout.load(); lay >= 0) {  // a forced layout over the budget fails the render
+            const bool wide = (lay & 1) != 0;
+            q.inv_r_in_lds = (lay & 2) ? 1u : 0u;
+            q.rec32_in_lds = wide && (lay & 4) ? 1u : 0u;
+            mode = wide ? kF64LdsWide : kF64Lds;
+        } else {
+            // the widened sphere records and the 1/r table join the staged scene while the block stays
+            // within the LDS it may declare (lds_budget64)
+            // (widened records before the 1/r table: a sphere test reads a record, a hit reads 1/r)
+            if (RRT_F64_WIDE_SPHERES && !(RRT_F64_PREFER_F32REC && p.sphere32)) {
+                // with the pre-test: the f32 records staged too, or read from global memory (L1 / L2)
+                for (const uint32_t rec32 : {p.sphere32 && RRT_F64_SPHERE32 ? 1u : 0u, 0u}) {
+                    for (const uint32_t inv_r : {1u, 0u}) {
+                        if (mode >= 0) break;
+                        q.rec32_in_lds = rec32;
+                        q.inv_r_in_lds = inv_r;
+                        if (lds64_bytes(q, kF64LdsWide, B) <= lds_budget64(B)) mode = kF64LdsWide;
+                    }
+                }
+            }
+            if (mode < 0) {
+                mode = kF64Lds;
+                q.rec32_in_lds = 0u;
+                q.inv_r_in_lds = 1u;
+                if (lds64_bytes(q, kF64Lds, B) > lds_budget64(B)) q.inv_r_in_lds = 0u;
+            }
+        }
+    }
+    const size_t lds = lds64_bytes(q, mode, B);
+    if (lds > lds_budget64(B) || lds > kLdsBlockMax) return pl;
+    pl.ok = 1u;
+    pl.kclass = cls;
+    pl.arm = mode;
+    pl.stack_bytes = 2u;
+    pl.threads = (uint32_t)B;
+    pl.waves = pl.waves_nf = cls == kF64Full ? 1u : (uint32_t)RRT_F64_WAVES;
+    pl.scene_in_lds = mode != kF64Global ? 1u : 0u;
+    pl.inv_r_in_lds = q.inv_r_in_lds;
+    pl.rec32_in_lds = q.rec32_in_lds;
+    pl.lds_bytes = lds;
+    pl.raise_limit = lds > kLdsDefaultMax ? 1u : 0u;
+    return pl;
+}
+
+namespace {
+
 template <int kMode, int kClass>
-hipError_t launch64(const KParams &p, bool count, hipStream_t stream) {
+hipError_t launch64(const KParams &p, const LaunchPlan &pl, bool count, hipStream_t stream) {
     constexpr int B = blk64(kClass);
-    const size_t lds = lds64_bytes(p, kMode, B);
-    if (lds > lds_budget64(B)) return hipErrorInvalidValue;
+    if (pl.arm != kMode || pl.kclass != kClass || pl.threads != (uint32_t)B) return hipErrorInvalidValue;
+    KParams q = p;
+    q.inv_r_in_lds = pl.inv_r_in_lds;
+    q.rec32_in_lds = pl.rec32_in_lds;
+    const size_t lds = (size_t)pl.lds_bytes;
     auto kernel = count ? rrt_render64<kMode, true, kClass> : rrt_render64<kMode, false, kClass>;
     hipError_t e;
-    if (lds > 64u * 1024u) {  // beyond the default dynamic-LDS limit (gfx950 allows 160 KiB per block)
+    if (pl.raise_limit) {  // beyond the default dynamic-LDS limit (gfx950 allows 160 KiB per block)
         e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)lds);
         if (e != hipSuccess) return e;
@@ -1590,77 +1671,36 @@ hipError_t launch64(const KParams &p, bool count, hipStream_t stream) {
     e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, B, lds);
     if (e != hipSuccess) return e;
     if (per_cu < 1) per_cu = 1;
-    const uint32_t want = (p.n_units + B - 1) / B;
-    uint32_t blocks = std::max<uint32_t>(std::min<uint32_t>(want, (uint32_t)per_cu * p.n_cus), kQueues);
+    const uint32_t want = (q.n_units + B - 1) / B;
+    uint32_t blocks = std::max<uint32_t>(std::min<uint32_t>(want, (uint32_t)per_cu * q.n_cus), kQueues);
     if (RRT_F64_B2F) {  // every lane needs a history slot
-        if (!p.hist || p.hist_lanes < kQueues * (uint32_t)B) return hipErrorInvalidValue;
-        blocks = std::min<uint32_t>(blocks, p.hist_lanes / (uint32_t)B);
+        if (!q.hist || q.hist_lanes < kQueues * (uint32_t)B) return hipErrorInvalidValue;
+        blocks = std::min<uint32_t>(blocks, q.hist_lanes / (uint32_t)B);
     }
-    e = hipMemsetAsync(p.unit_counter, 0, kQueues * 32u * sizeof(uint32_t), stream);
+    e = hipMemsetAsync(q.unit_counter, 0, kQueues * 32u * sizeof(uint32_t), stream);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(B), lds, stream, p);
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(B), lds, stream, q);
     return hipGetLastError();
 }
 
-// The scene placement: the f32 nodes, spheres and materials in LDS when they fit (C1, C2, C4), else
-// the f16 nodes and records from global memory (C5).
-#ifndef RRT_F64_WIDE_SPHERES
-#define RRT_F64_WIDE_SPHERES 1
-#endif
-// rrt_testing_f64_layout: a forced LDS layout (bit 0: widened Sphere64 records, bit 1: the 1/r table,
-// bit 2: the f32 pre-test records beside widened ones), or -1 for the automatic choice below
-std::atomic<int> g_f64_layout{-1};
-
+// The plan's scene mode among the class's kernels.
 template <int kClass>
-hipError_t launch64_placed(const KParams &p, bool count, hipStream_t stream) {
-    if (!p.scene_in_lds) return launch64<kF64Global, kClass>(p, count, stream);
-    if (const int lay = g_f64_layout.load(); lay >= 0) {
-        KParams q = p;
-        const bool wide = (lay & 1) != 0;
-        q.inv_r_in_lds = (lay & 2) ? 1u : 0u;
-        q.rec32_in_lds = wide && (lay & 4) ? 1u : 0u;
-        if (lds64_bytes(q, wide ? kF64LdsWide : kF64Lds, blk64(kClass)) > lds_budget64(blk64(kClass)))
-            return hipErrorInvalidValue;
-        return wide ? launch64<kF64LdsWide, kClass>(q, count, stream) : launch64<kF64Lds, kClass>(q, count, stream);
-    }
-    // the widened sphere records and the 1/r table join the staged scene while the block stays
-    // within the 64 KB it may declare
-    // (widened records before the 1/r table: a sphere test reads a record, a hit reads 1/r)
-    KParams q = p;
-    q.rec32_in_lds = 0u;
-#ifndef RRT_F64_PREFER_F32REC
-#define RRT_F64_PREFER_F32REC 0
-#endif
-    if (RRT_F64_WIDE_SPHERES && !(RRT_F64_PREFER_F32REC && p.sphere32)) {
-        // with the pre-test: the f32 records staged too, or read from global memory (L1 / L2)
-        for (const uint32_t rec32 : {p.sphere32 && RRT_F64_SPHERE32 ? 1u : 0u, 0u}) {
-            q.rec32_in_lds = rec32;
-            for (const uint32_t inv_r : {1u, 0u}) {
-                q.inv_r_in_lds = inv_r;
-                if (lds64_bytes(q, kF64LdsWide, blk64(kClass)) <= lds_budget64(blk64(kClass)))
-                    return launch64<kF64LdsWide, kClass>(q, count, stream);
-            }
-        }
-    }
-    q.rec32_in_lds = 0u;
-    q.inv_r_in_lds = 1u;
-    if (lds64_bytes(q, kF64Lds, blk64(kClass)) > lds_budget64(blk64(kClass))) q.inv_r_in_lds = 0u;
-    return launch64<kF64Lds, kClass>(q, count, stream);
+hipError_t launch64_placed(const KParams &p, const LaunchPlan &pl, bool count, hipStream_t stream) {
+    if (pl.arm == kF64Global) return launch64<kF64Global, kClass>(p, pl, count, stream);
+    return pl.arm == kF64LdsWide ? launch64<kF64LdsWide, kClass>(p, pl, count, stream)
+                                 : launch64<kF64Lds, kClass>(p, pl, count, stream);
 }
 
 }  // namespace
 
 hipError_t launch_render_pass_f64(const KParams &p, bool count, hipStream_t stream) {
     if (p.n_units == 0) return hipSuccess;
-    if (p.bvh_width != 2 || p.prim_motion || p.stack_depth > (uint32_t)kMaxStackDepth || p.n_nodes > 65535u)
-        return hipErrorInvalidValue;  // the host builds a 16-bit-stack BVH2 for book-1 scenes
-#ifndef RRT_F64_CLASSES
-#define RRT_F64_CLASSES 1
-#endif
+    const LaunchPlan pl = plan_launch_f64(p);
+    if (!pl.ok) return hipErrorInvalidValue;
     hipError_t e;
-    if (RRT_F64_CLASSES && !p.specular) e = launch64_placed<kF64Diffuse>(p, count, stream);
-    else if (RRT_F64_CLASSES && !p.image_tex) e = launch64_placed<kF64Untextured>(p, count, stream);
-    else e = launch64_placed<kF64Full>(p, count, stream);
+    if (pl.kclass == kF64Diffuse) e = launch64_placed<kF64Diffuse>(p, pl, count, stream);
+    else if (pl.kclass == kF64Untextured) e = launch64_placed<kF64Untextured>(p, pl, count, stream);
+    else e = launch64_placed<kF64Full>(p, pl, count, stream);
     if (e != hipSuccess || p.n_chunks <= 1 || p.seq) return e;
     const uint32_t n_pixels = p.tile_rows * p.width;
     hipLaunchKernelGGL(rrt_combine_chunks64, dim3((n_pixels + 255) / 256), dim3(256), 0, stream, p.partial64,

@@ -1533,16 +1533,6 @@ static int32_t scene_create(const RrtCamera *cam, const RrtSphere *spheres, uint
     // BVH2: the node layout already encodes the choice (80-B sign-ordered nodes are the LDS ones)
     p.scene_in_lds = fb.width == 2 ? fb.stride == (uint32_t)sizeof(rrt::GNode)
                                    : scene_lds_fit(fb.bytes.size(), n_prims, book2);
-    {  // Perlin tables in LDS when the block's LDS (stack + staged scene + tables) stays within 64 KB
-        // the block that launches (book-2 classes 1-3: 256 threads; book 3: 512), as launch_variant sizes it
-        const bool wide = fb.n_nodes > 65535u;
-        const size_t threads = (size_t)rrt::render_block_threads(book2 && !book3, wide, book3);
-        const size_t stack = ((size_t)p.stack_depth * threads * (wide ? 4u : 2u) + 15u) / 16u * 16u;
-        const size_t scene = p.scene_in_lds ? fb.bytes.size() + (size_t)n_prims * (rrt::kPrimBytes + (book2 ? rrt::kMotionBytes : 0)) : 0;
-        p.perlin_in_lds = book2 && n_perlin > 0 &&
-                          stack + scene + (size_t)n_perlin * sizeof(rrt::GPerlin) <= 64u * 1024u ? 1u : 0u;
-        if (const char *e = std::getenv("RRT_PERLIN_IN_LDS")) p.perlin_in_lds = p.perlin_in_lds && std::atoi(e) != 0;
-    }
     // traversal exit / leaf batch thresholds (x/256 of the live lanes), same-box sweeps against 32/32:
     // book-1 LDS scenes 56/56 (C2 +0.6 %, C4 +0.25 %); L2 scenes 64/48 (C5 +2.0 %, final_scene and
     // bouncing spheres +4 %). Book-2/3 LDS scenes by kernel class (round 6, after the class launch
@@ -1567,6 +1557,16 @@ static int32_t scene_create(const RrtCamera *cam, const RrtSphere *spheres, uint
     if (const char *e = std::getenv("RRT_GLOBAL_WAVES")) p.global_waves = (uint32_t)std::atoi(e);
     if (const char *e = std::getenv("RRT_TRAV_FRAC")) p.trav_frac = (uint32_t)std::min(256, std::max(0, std::atoi(e)));
     if (const char *e = std::getenv("RRT_LEAF_FRAC")) p.leaf_frac = (uint32_t)std::min(256, std::max(0, std::atoi(e)));
+    // Perlin tables in LDS when the block that launches (rrt::plan_launch) still fits 64 KB with them
+    p.perlin_in_lds = rrt::perlin_fits_lds(p) ? 1u : 0u;
+    if (const char *e = std::getenv("RRT_PERLIN_IN_LDS")) p.perlin_in_lds = p.perlin_in_lds && std::atoi(e) != 0;
+    // every render of the scene launches this plan; a scene without one fails here, not at a launch
+    if (!rrt::plan_launch(p).ok) {
+        free_scene(s);
+        return fail(RRT_E_INVALID, "no launch shape holds the scene's traversal stack (" + std::to_string(fb.stack_need) +
+                                       " entries) and staged data within a block's " +
+                                       std::to_string(rrt::kLdsBlockMax / 1024u) + " KiB of LDS");
+    }
 
     RrtBvhInfo &bi = s->info;
     bi.n_nodes = fb.n_nodes;
@@ -1803,6 +1803,56 @@ extern "C" void rrt_testing_device_wrap(int32_t on) { g_device_wrap.store(on != 
 // the block's LDS in the given layout instead of its automatic choice (every layout renders the same
 // bits; tests/test_gpu_books64.py reaches each fallback with it). -1 restores the automatic choice.
 extern "C" void rrt_testing_f64_layout(int32_t layout) { rrt::set_f64_layout(layout); }
+
+// Test support (rrt_testing_launch_plan): the launch plan of a scene given by its counts, through the
+// same rrt::plan_launch / perlin_fits_lds the launches and scene creation use; no device needed.
+extern "C" int32_t rrt_testing_launch_plan(const RrtLaunchPlanQuery *q, RrtLaunchPlan *out) {
+    if (!q || !out) return fail(RRT_E_INVALID, "null query or out");
+    *out = RrtLaunchPlan{};
+    if (q->node_stride != 32u && q->node_stride != 80u && q->node_stride != 128u)
+        return fail(RRT_E_INVALID, "node_stride must be 80 (staged BVH2), 32 (global BVH2) or 128 (BVH4)");
+    if (q->book > 3u || q->book == 1u) return fail(RRT_E_INVALID, "book must be 0 (book 1), 2 or 3");
+    rrt::KParams p{};
+    static float4 some_motion;  // book 2 / 3: any non-null motion array
+    p.n_nodes = q->n_nodes;
+    p.n_prims = q->n_prims;
+    p.stack_depth = q->stack_depth;
+    p.bvh_width = q->node_stride == 128u ? 4u : 2u;
+    p.scene_in_lds = q->node_stride == 128u ? q->bvh4_in_lds : q->node_stride == 80u ? 1u : 0u;
+    p.prim_motion = q->book ? &some_motion : nullptr;
+    p.flags = (q->book == 3u ? RRT_FLAG_BOOK3 | RRT_FLAG_RAY_TIME : 0u) | (q->f64 ? RRT_FLAG_F64 : 0u);
+    p.specular = q->specular;
+    p.image_tex = q->image_tex;
+    p.n_perlin = q->n_perlin;
+    p.n_media = q->n_media;
+    p.n_quads = q->n_quads;
+    p.sphere32 = q->f64 ? 1u : 0u;
+    p.min_waves = q->min_waves ? q->min_waves : 6u;        // scene creation's defaults
+    p.global_waves = q->global_waves ? q->global_waves : 7u;
+    // the scenes rrt_scene_create rejects before it plans
+    const bool book2 = q->book != 0u;
+    if (q->stack_depth > (uint32_t)rrt::kMaxStackDepth || (q->f64 && (book2 || q->n_perlin || q->n_nodes > 65535u)) ||
+        (book2 && p.bvh_width != 2u))
+        return RRT_OK;
+    p.perlin_in_lds = rrt::perlin_fits_lds(p) ? 1u : 0u;
+    const rrt::LaunchPlan pl = rrt::plan_launch(p);
+    out->ok = pl.ok;
+    if (!pl.ok) return RRT_OK;
+    out->f64 = pl.f64;
+    out->kernel_class = pl.kclass;
+    out->shape = pl.arm;
+    out->stack_bytes = pl.stack_bytes;
+    out->threads = pl.threads;
+    out->waves = pl.waves;
+    out->waves_noise_free = pl.waves_nf;
+    out->scene_in_lds = pl.scene_in_lds;
+    out->perlin_in_lds = pl.perlin_in_lds;
+    out->inv_r_in_lds = pl.inv_r_in_lds;
+    out->rec32_in_lds = pl.rec32_in_lds;
+    out->raise_limit = pl.raise_limit;
+    out->lds_bytes = pl.lds_bytes;
+    return RRT_OK;
+}
 
 extern "C" int32_t rrt_testing_recip_check(uint64_t *mismatches) {
     if (!mismatches) return fail(RRT_E_INVALID, "null mismatches");

@@ -293,20 +293,59 @@ constexpr int kBook2Waves = RRT_B2_WAVES;  // book-2 kernels (classes 1-3): laun
 constexpr int kBook2Block = RRT_B2_BLOCK;  // and block size; book 3 and unbounded launches use kBlock
 constexpr int kBook3Waves = RRT_B3_WAVES;  // book 3 (class 4): launch bound (1 = none, 512-thread blocks;
                                            // else kBook2Block-thread blocks)
-// Threads per block of the render launch for a scene (rrt_kernel.hip launch_width): the host sizes
-// the block's LDS (traversal stack, Perlin tables) with it. book2_class: a book-2 scene rendered by
-// kernel classes 1-3 (not book 3); wide_stack: more than 65535 nodes (32-bit stack, kBlock).
-inline int render_block_threads(bool book2_class, bool wide_stack, bool book3 = false) {
-    if (wide_stack) return kBlock;
-    if (book3) return kBook3Waves > 1 ? kBook2Block : kBlock;
-    return book2_class && kBook2Waves > 1 ? kBook2Block : kBlock;
-}
 // Per-block LDS budget for staging the scene (BVH nodes + spheres + per-sphere materials)
 // next to the stack. RTOW: 13.5 KB nodes + 486 x 48 B = 36.9 KB; + ~11 KB of stack per
 // 512-thread block keeps 3 blocks (6 waves/SIMD) within the CU's 160 KB.
 constexpr size_t kLdsSceneBudget = 40 * 1024;
 constexpr size_t kPrimBytes = sizeof(float4) + sizeof(GMaterial);  // per primitive: sphere + material
 constexpr size_t kMotionBytes = sizeof(float4);                     // + motion, scenes with moving spheres
+
+// Dynamic LDS one block may declare: 64 KiB by default, up to the CU's 160 KiB (gfx950,
+// MI355X_MICROARCH.md occupancy section) once the kernel's hipFuncAttributeMaxDynamicSharedMemorySize
+// is raised to the size.
+constexpr size_t kLdsDefaultMax = 64u * 1024u;
+constexpr size_t kLdsBlockMax = 160u * 1024u;
+
+// The shape of a scene's render launch, decided on the host without a HIP call (plan_launch); the
+// launches (rrt_kernel.hip launch_variant, rrt_books64.hip launch64) run what it says and declare
+// its lds_bytes, and scene creation asks it where the Perlin tables go and whether a launch exists.
+//   f32 (rrt_kernel.hip): the block's LDS is the traversal stack (stack_depth x threads x
+//     stack_bytes, rounded up to 16 B) + the staged scene (nodes, 48 B per primitive, + 16 B of
+//     motion in the book-2/3 classes) + the Perlin tables when perlin_in_lds. Each kernel class has an
+//     ordered list of launch shapes, all of them instantiated: the first is the tuned one (C2's
+//     class: 1024 x 8, then 512 x 6). The plan takes the first whose LDS fits 64 KiB — the tuned shape
+//     whenever it fits, so no measured config moves — else the smallest of them with the limit raised
+//     (raise_limit), which every scene rrt_scene_create accepts fits into 160 KiB: 512 threads need at
+//     most 64 KB of 16-bit stack + the 40 KB scene budget, the 32-bit stack at most 128 KB.
+//   f64 (rrt_books64.hip): the class's block and, for a staged scene, the richest layout within its
+//     budget (lds_budget64), as before.
+// ok = 0: no shape within kLdsBlockMax (or a stack deeper than kMaxStackDepth): scene creation fails.
+struct LaunchPlan {
+    uint32_t ok;
+    uint32_t f64;
+    int32_t kclass;         // f32: -2 diffuse, -1 untextured, 0 full book 1, 1-3 book 2 (spheres, quads, media),
+                            // 4 book 3; f64: 0 full, 1 untextured, 2 diffuse
+    int32_t arm;            // f32: the launch shape's place in rrt_kernel.hip's LaunchArm; f64: the scene mode
+                            // (0 global, 1 staged with f32 sphere records, 2 staged with widened records)
+    uint32_t stack_bytes;   // per stack entry: 2, or 4 for more than 65535 nodes
+    uint32_t threads;       // per block
+    uint32_t waves;         // launch-bounds waves per SIMD (1: no bound)
+    uint32_t waves_nf;      // the same for the noise-free kernel of book-2/3 scenes without Perlin tables
+    uint32_t scene_in_lds;  // the scene is staged in LDS
+    uint32_t perlin_in_lds; // f32: the Perlin tables too
+    uint32_t inv_r_in_lds;  // f64: the 1/r table too
+    uint32_t rec32_in_lds;  // f64: the f32 pre-test records beside widened ones
+    uint32_t raise_limit;   // lds_bytes > 64 KiB: the launch raises the kernel's dynamic-LDS limit first
+    uint64_t lds_bytes;     // dynamic LDS of the block
+};
+// From the scene's counts and flags in p (n_nodes, n_prims, stack_depth, bvh_width, scene_in_lds,
+// prim_motion / n_quads / n_media / flags for the class, specular, image_tex, n_perlin,
+// perlin_in_lds, min_waves, global_waves; f64: sphere32 too). Pure: no device, no HIP call.
+LaunchPlan plan_launch(const KParams &p);
+LaunchPlan plan_launch_f64(const KParams &p);  // rrt_books64.hip; plan_launch forwards flags & kFlagF64 here
+// Whether a book-2/3 scene's Perlin tables are staged in LDS: when the launch planned with them
+// still fits the default 64 KiB.
+bool perlin_fits_lds(KParams p);
 
 // Launch wrappers implemented in rrt_kernel.hip.
 hipError_t launch_render(const KParams &p, hipStream_t stream);

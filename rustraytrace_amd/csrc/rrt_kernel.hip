@@ -25,6 +25,8 @@
 #include "rrt_internal.h"
 
 #include <algorithm>
+#include <cstdio>
+#include <cstdlib>
 #include <type_traits>
 
 namespace rrt {
@@ -2107,24 +2109,162 @@ __global__ __launch_bounds__(256) void rrt_quantize(const float4 *__restrict__ a
     }
 }
 
-template <bool kLds, typename StackT, bool kWide, int kBook2, int kWaves = 1, int kBlk = kBlock, int kWavesNF = kWaves>
-hipError_t launch_variant(const KParams &p, bool count, hipStream_t stream) {
+// ---- The launch plan (rrt_internal.h LaunchPlan): the f32 kernels' launch shapes --------------
+// The instantiated shapes of a kernel class; a class's candidates are a few of them, in order.
+enum LaunchArm : int {
+    kArmStack32 = 0,  // more than 65535 nodes: the 32-bit stack, kBlock threads, no bound, scene read from L2
+    kArmBook2,        // book-2 classes 1-3: kBook2Block x kBook2Waves (noise-free: RRT_B2_NF_WAVES for classes 1-2)
+    kArmBook3,        // book 3 (class 4): kBook2Block x kBook3Waves
+    kArmB1U,          // C2's class (-1) staged in LDS: RRT_B1U_BLOCK x RRT_B1U_WAVES (fewer scene copies)
+    kArmB1D,          // the diffuse class (-2, C4) staged in LDS: 256 x RRT_B1D_WAVES
+    kArmMain,         // kBlock x kWavesPerSimd
+    kArmGlobal,       // book-1 scenes read from L2 (C5): kGlobalBlock x kGlobalWaves (72 VGPRs, which
+                      // 512-thread blocks cannot reach: 3.5 blocks); C5 +2.8 % same-box over 512 x 6
+    kArmUnbound,      // kBlock, no launch bound
+};
+struct ArmShape {
+    int threads, waves, waves_nf, stack_bytes;
+};
+// Book-2 variants (motion, textures, quads) need ~105 VGPRs unbounded. In round 1, with 40-110
+// spilled SGPRs, a 6-wave bound cost 3-14 % and a 5-wave bound 0-8 %. Book 2 (classes
+// 1-3): 256-thread blocks at 5 waves/SIMD (96 VGPRs). Measured on the 1/4-spp scene table against
+// 512 threads unbounded (~105 VGPRs, 4 waves): +2 ... +16 % on every book-2 scene once the
+// parameter spills were gone (256 x 4: +-1 %, 256 x 6: -21 ... +9 %). Book 3 (class 4, the
+// light-list pdfs) at 256 x 5 too (rrt_internal.h RRT_B3_WAVES). Class 3 (media: final_scene,
+// cornell_smoke) read from L2: RRT_B2_MEDIA_GLOBAL_WAVES. Classes 1-2 without noise textures need
+// ~88 VGPRs and run at RRT_B2_NF_WAVES (6: bouncing spheres +6.4 %, checkered spheres +4 %, quads
+// +3.3 %, cornell_box +6.8 % same-box over 5; the media class and the noise kernels lose 8-15 % at 6
+// and stay at 5).
+constexpr ArmShape arm_shape(int cls, int arm, bool lds) {
+    switch (arm) {
+    case kArmStack32: return {kBlock, 1, 1, 4};
+    case kArmBook2: {
+        const int gw = (cls == 3 && RRT_B2_MEDIA_GLOBAL_WAVES > 0) ? RRT_B2_MEDIA_GLOBAL_WAVES : kBook2Waves;
+        const int w = lds ? kBook2Waves : gw;
+        return {kBook2Block, w, cls <= 2 ? RRT_B2_NF_WAVES : w, 2};
+    }
+    case kArmBook3: return {kBook2Block, kBook3Waves, kBook3Waves, 2};
+    case kArmB1U: return {RRT_B1U_BLOCK, RRT_B1U_WAVES, RRT_B1U_WAVES, 2};
+    case kArmB1D: return {kGlobalBlock, RRT_B1D_WAVES, RRT_B1D_WAVES, 2};
+    case kArmMain: return {kBlock, kWavesPerSimd, kWavesPerSimd, 2};
+    case kArmGlobal: return {kGlobalBlock, kGlobalWaves, kGlobalWaves, 2};
+    default: return {kBlock, 1, 1, 2};
+    }
+}
+
+// The kernel class of an f32 scene. Book-2 scenes (moving spheres, checker / noise textures, quads,
+// media; motion is always present, zero for static spheres) by their geometry. Book-1 scenes
+// without image textures run the kernel with the texture path compiled out: C2 +1.0 %; for scenes
+// read from L2 (C5) it removes the 7-wave kernel's 4 spilled VGPRs (20 B of scratch per lane,
+// written and read back through memory) at equal time. The width-4 tree (an experiment) has the
+// full class only.
+int f32_class(const KParams &p) {
+    if (p.prim_motion) return (p.flags & 0x4u) ? 4 : p.n_media ? 3 : p.n_quads ? 2 : 1;  // 0x4: RRT_FLAG_BOOK3
+    if (p.bvh_width == 4) return 0;
+    if (!p.specular && p.scene_in_lds) return kBook1Diffuse;
+    return p.image_tex ? 0 : kBook1Untextured;
+}
+
+// Dynamic LDS of a block: the one formula (the kernel's carve-up: stack, nodes, primitives, motion,
+// Perlin tables, rrt_device.h / render_body).
+size_t f32_lds_bytes(const KParams &p, int cls, const ArmShape &s, bool lds) {
+    size_t n = ((size_t)p.stack_depth * (size_t)s.threads * (size_t)s.stack_bytes + 15u) / 16u * 16u;
+    if (lds)
+        n += (size_t)p.n_nodes * (p.bvh_width == 4 ? sizeof(GNode4) : sizeof(GNode)) +  // LDS BVH2 = GNode
+             (size_t)p.n_prims * (kPrimBytes + (cls > 0 ? kMotionBytes : 0));
+    if (cls > 0 && p.perlin_in_lds) n += (size_t)p.n_perlin * sizeof(GPerlin);
+    return n;
+}
+
+}  // namespace
+
+LaunchPlan plan_launch(const KParams &p) {
+    if (p.flags & kFlagF64) return plan_launch_f64(p);
+    LaunchPlan pl{};
+    if (p.stack_depth > (uint32_t)kMaxStackDepth) return pl;
+    const int cls = f32_class(p);
+    if (cls > 0 && p.bvh_width != 2) return pl;  // books 2 / 3: the binary BVH only
+    const bool wide = p.bvh_width == 4;
+    int cand[3];
+    int n = 0;
+    bool lds = p.scene_in_lds != 0;
+    if (p.n_nodes > 65535u) {
+        cand[n++] = kArmStack32;
+        lds = false;
+    } else if (cls > 0) {
+        cand[n++] = cls != 4 ? (kBook2Waves > 1 ? kArmBook2 : kArmUnbound) : (kBook3Waves > 1 ? kArmBook3 : kArmUnbound);
+    } else if (!wide && lds && p.min_waves >= 6) {
+        if (cls == kBook1Untextured && RRT_B1U_WAVES > 6) cand[n++] = kArmB1U;
+        if (cls == kBook1Diffuse && RRT_B1D_WAVES > 6) cand[n++] = kArmB1D;
+        cand[n++] = kArmMain;
+    } else if (!wide && !lds && p.global_waves >= 6) {
+        cand[n++] = p.global_waves >= 7 ? kArmGlobal : kArmMain;
+    } else {
+        cand[n++] = kArmUnbound;
+    }
+    // the first candidate within the default limit, else the smallest (the earlier of equals)
+    int pick = -1;
+    size_t best = 0;
+    for (int i = 0; i < n; ++i) {
+        const size_t b = f32_lds_bytes(p, cls, arm_shape(cls, cand[i], lds), lds);
+        if (b <= kLdsDefaultMax) {
+            pick = i, best = b;
+            break;
+        }
+        if (pick < 0 || b < best) pick = i, best = b;
+    }
+    if (best > kLdsBlockMax) return pl;
+    const ArmShape s = arm_shape(cls, cand[pick], lds);
+    pl.ok = 1u;
+    pl.kclass = cls;
+    pl.arm = cand[pick];
+    pl.stack_bytes = (uint32_t)s.stack_bytes;
+    pl.threads = (uint32_t)s.threads;
+    pl.waves = (uint32_t)s.waves;
+    pl.waves_nf = (uint32_t)s.waves_nf;
+    pl.scene_in_lds = lds ? 1u : 0u;
+    pl.perlin_in_lds = cls > 0 && p.perlin_in_lds && p.n_perlin ? 1u : 0u;
+    pl.lds_bytes = best;
+    pl.raise_limit = best > kLdsDefaultMax ? 1u : 0u;
+    return pl;
+}
+
+bool perlin_fits_lds(KParams p) {
+    if (p.n_perlin == 0 || !p.prim_motion) return false;
+    p.perlin_in_lds = 1u;
+    const LaunchPlan pl = plan_launch(p);
+    return pl.ok && !pl.raise_limit;
+}
+
+namespace {
+
+// One instantiated shape: launches what the plan says, at the plan's LDS size.
+template <bool kLds, typename StackT, bool kWide, int kBook2, int kArm>
+hipError_t launch_variant(const KParams &p, const LaunchPlan &pl, bool count, hipStream_t stream) {
+    constexpr ArmShape kS = arm_shape(kBook2, kArm, kLds);
+    constexpr int kWaves = kS.waves, kWavesNF = kS.waves_nf, kBlk = kS.threads;
+    static_assert(kS.stack_bytes == (int)sizeof(StackT), "stack type of the launch shape");
     // Book 2/3: a noise-free scene runs a kernel without the noise path (the counting twin and the
     // 32-bit-stack kernels keep it: one instantiation each serves both), at kWavesNF waves per SIMD.
     constexpr bool kNoiseFree = kBook2 > 0 && sizeof(StackT) == 2;
     if (p.n_units == 0) return hipSuccess;
-    size_t lds = ((size_t)p.stack_depth * kBlk * sizeof(StackT) + 15u) / 16u * 16u;
-    if (kLds)
-        lds += (size_t)p.n_nodes * (kWide ? sizeof(GNode4) : sizeof(GNode)) +  // LDS BVH2 = GNode
-               (size_t)p.n_prims * (kPrimBytes + (kBook2 > 0 ? kMotionBytes : 0));
-    if (kBook2 > 0 && p.perlin_in_lds) lds += (size_t)p.n_perlin * sizeof(GPerlin);
+    if (pl.arm != kArm || pl.kclass != kBook2 || pl.threads != (uint32_t)kBlk || pl.scene_in_lds != (kLds ? 1u : 0u) ||
+        (p.bvh_width == 4) != kWide)
+        return hipErrorInvalidValue;  // the plan names another instantiation
+    const size_t lds = (size_t)pl.lds_bytes;
     auto kernel = count                       ? rrt_render<kLds, true, StackT, kWide, kWaves, kBook2, kBlk, (kBook2 > 0)>
                   : !kNoiseFree || p.n_perlin ? rrt_render<kLds, false, StackT, kWide, kWaves, kBook2, kBlk, (kBook2 > 0)>
                                               : rrt_render<kLds, false, StackT, kWide, kWavesNF, kBook2, kBlk, false>;
+    hipError_t e;
+    if (pl.raise_limit) {  // beyond the default dynamic-LDS limit (gfx950 allows 160 KiB per block)
+        e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)lds);
+        if (e != hipSuccess) return e;
+    }
     // Persistent grid: as many blocks as can be resident (occupancy at this LDS size), capped
     // by the work; the queue counter is zeroed on the stream before the launch.
     int per_cu = 0;
-    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kBlk, lds);
+    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kBlk, lds);
     if (e != hipSuccess) return e;
     if (per_cu < 1) per_cu = 1;
     const uint32_t want = (p.n_units + kBlk - 1) / kBlk;
@@ -2134,6 +2274,11 @@ hipError_t launch_variant(const KParams &p, bool count, hipStream_t stream) {
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kBlk), lds, stream, p);
     e = hipGetLastError();
+    static const bool log = std::getenv("RRT_LAUNCH_LOG") != nullptr;  // debug: one line per launch on stderr
+    if (log)
+        std::fprintf(stderr, "rrt launch: class %d, %d x %d, stack %d B x %u, %zu B of LDS%s, %d block(s)/CU, %u blocks: %s\n",
+                     kBook2, kBlk, kWaves, (int)sizeof(StackT), p.stack_depth, lds, pl.raise_limit ? " (limit raised)" : "",
+                     per_cu, blocks, hipGetErrorString(e));
     if (e != hipSuccess || p.n_chunks <= 1) return e;
     const uint32_t n_pixels = p.tile_rows * p.width;
     hipLaunchKernelGGL(rrt_combine_chunks, dim3((n_pixels + 255) / 256), dim3(256), 0, stream, p.partial, p.accum,
@@ -2141,76 +2286,53 @@ hipError_t launch_variant(const KParams &p, bool count, hipStream_t stream) {
     return hipGetLastError();
 }
 
+// The plan's shape among the class's instantiations.
 template <bool kWide, int kBook2>
-hipError_t launch_width(const KParams &p, bool count, hipStream_t stream) {
-    if (p.stack_depth > (uint32_t)kMaxStackDepth) return hipErrorInvalidValue;
-    if (p.n_nodes > 65535u) return launch_variant<false, uint32_t, kWide, kBook2>(p, count, stream);
-    if constexpr (kBook2 > 0) {
-        // Book-2 variants (motion, textures, quads) need ~105 VGPRs unbounded. In round 1, with
-        // 40-110 spilled SGPRs, a 6-wave bound cost 3-14 % and a 5-wave bound 0-8 %.
-        // Book 2 (classes 1-3): 256-thread blocks at 5 waves/SIMD (96 VGPRs). Measured on the
-        // 1/4-spp scene table against 512 threads unbounded (~105 VGPRs, 4 waves): +2 ... +16 %
-        // on every book-2 scene once the parameter spills were gone (256 x 4: +-1 %, 256 x 6:
-        // -21 ... +9 %). Book 3 (class 4, the light-list pdfs) keeps the unbounded 512: -8 % at 5.
-        // Class 3 (media: final_scene, cornell_smoke) read from L2: RRT_B2_MEDIA_GLOBAL_WAVES.
-        constexpr int kGW = (kBook2 == 3 && RRT_B2_MEDIA_GLOBAL_WAVES > 0) ? RRT_B2_MEDIA_GLOBAL_WAVES : kBook2Waves;
-        // Classes 1-2 without noise textures need ~88 VGPRs and run at RRT_B2_NF_WAVES (6: bouncing
-        // spheres +6.4 %, checkered spheres +4 %, quads +3.3 %, cornell_box +6.8 % same-box over 5;
-        // the media class and the noise kernels lose 8-15 % at 6 and stay at 5).
-        constexpr int kNF = kBook2 <= 2 ? RRT_B2_NF_WAVES : kBook2Waves;
-        constexpr int kGNF = kBook2 <= 2 ? RRT_B2_NF_WAVES : kGW;
-        if constexpr (kBook2 != 4 && kBook2Waves > 1)
-            return p.scene_in_lds ? launch_variant<true, uint16_t, kWide, kBook2, kBook2Waves, kBook2Block, kNF>(p, count, stream)
-                                  : launch_variant<false, uint16_t, kWide, kBook2, kGW, kBook2Block, kGNF>(p, count, stream);
-        if constexpr (kBook2 == 4 && kBook3Waves > 1)
-            return p.scene_in_lds ? launch_variant<true, uint16_t, kWide, kBook2, kBook3Waves, kBook2Block>(p, count, stream)
-                                  : launch_variant<false, uint16_t, kWide, kBook2, kBook3Waves, kBook2Block>(p, count, stream);
-        return p.scene_in_lds ? launch_variant<true, uint16_t, kWide, kBook2>(p, count, stream)
-                              : launch_variant<false, uint16_t, kWide, kBook2>(p, count, stream);
-    } else {
-        // C2's class staged in LDS: RRT_B1U_WAVES > 6 runs RRT_B1U_BLOCK-thread blocks (fewer scene copies)
+hipError_t launch_width(const KParams &p, const LaunchPlan &pl, bool count, hipStream_t stream) {
+    const bool lds = pl.scene_in_lds != 0;
+    if (pl.arm == kArmStack32) return launch_variant<false, uint32_t, kWide, kBook2, kArmStack32>(p, pl, count, stream);
+    if constexpr (kBook2 > 0 && kBook2 != 4 && kBook2Waves > 1)
+        if (pl.arm == kArmBook2)
+            return lds ? launch_variant<true, uint16_t, kWide, kBook2, kArmBook2>(p, pl, count, stream)
+                       : launch_variant<false, uint16_t, kWide, kBook2, kArmBook2>(p, pl, count, stream);
+    if constexpr (kBook2 == 4 && kBook3Waves > 1)
+        if (pl.arm == kArmBook3)
+            return lds ? launch_variant<true, uint16_t, kWide, kBook2, kArmBook3>(p, pl, count, stream)
+                       : launch_variant<false, uint16_t, kWide, kBook2, kArmBook3>(p, pl, count, stream);
+    if constexpr (kBook2 <= 0 && !kWide) {
         if constexpr (kBook2 == kBook1Untextured && RRT_B1U_WAVES > 6)
-            if (!kWide && p.scene_in_lds && p.min_waves >= 6)
-                return launch_variant<true, uint16_t, kWide, kBook2, RRT_B1U_WAVES, RRT_B1U_BLOCK>(p, count, stream);
-        // the diffuse-only class (C4) staged in LDS: RRT_B1D_WAVES > 6 runs 256-thread blocks
+            if (pl.arm == kArmB1U && lds) return launch_variant<true, uint16_t, kWide, kBook2, kArmB1U>(p, pl, count, stream);
         if constexpr (kBook2 == kBook1Diffuse && RRT_B1D_WAVES > 6)
-            if (!kWide && p.scene_in_lds && p.min_waves >= 6)
-                return launch_variant<true, uint16_t, kWide, kBook2, RRT_B1D_WAVES, kGlobalBlock>(p, count, stream);
-        if (!kWide && p.scene_in_lds && p.min_waves >= 6)
-            return launch_variant<true, uint16_t, kWide, kBook2, kWavesPerSimd>(p, count, stream);
-        // Scenes read from L2 (C5) hold only the stack in LDS: 256-thread blocks at 7 waves/SIMD
-        // (72 VGPRs), which 512-thread blocks cannot reach (3.5 blocks); C5 +2.8 % same-box over
-        // 512 x 6 (256 x 8, 64 VGPRs: -16 %, spills).
-        if (!kWide && !p.scene_in_lds && p.global_waves >= 7)
-            return launch_variant<false, uint16_t, kWide, kBook2, kGlobalWaves, kGlobalBlock>(p, count, stream);
-        if (!kWide && !p.scene_in_lds && p.global_waves >= 6)
-            return launch_variant<false, uint16_t, kWide, kBook2, kWavesPerSimd>(p, count, stream);
-        return p.scene_in_lds ? launch_variant<true, uint16_t, kWide, kBook2>(p, count, stream)
-                              : launch_variant<false, uint16_t, kWide, kBook2>(p, count, stream);
+            if (pl.arm == kArmB1D && lds) return launch_variant<true, uint16_t, kWide, kBook2, kArmB1D>(p, pl, count, stream);
+        if (pl.arm == kArmMain)
+            return lds ? launch_variant<true, uint16_t, kWide, kBook2, kArmMain>(p, pl, count, stream)
+                       : launch_variant<false, uint16_t, kWide, kBook2, kArmMain>(p, pl, count, stream);
+        if (pl.arm == kArmGlobal && !lds) return launch_variant<false, uint16_t, kWide, kBook2, kArmGlobal>(p, pl, count, stream);
     }
+    if (pl.arm == kArmUnbound)
+        return lds ? launch_variant<true, uint16_t, kWide, kBook2, kArmUnbound>(p, pl, count, stream)
+                   : launch_variant<false, uint16_t, kWide, kBook2, kArmUnbound>(p, pl, count, stream);
+    return hipErrorInvalidValue;
 }
 
 }  // namespace
 
 hipError_t launch_render_pass(const KParams &p, bool count, hipStream_t stream) {
     if (p.flags & kFlagF64) return launch_render_pass_f64(p, count, stream);  // the f64 books path
-    // Variant choice: BVH width, smallest LDS stack that holds the traversal, and the scene
-    // staged in LDS when the BVH + spheres fit the per-block budget (RTOW: ~20-26 KB).
-    // Book-2 scenes (moving spheres, checker / noise textures): BVH2 only (the host builds a
-    // binary tree for them); motion is always present (zero for static spheres).
-    if (p.prim_motion) {  // book 2: the binary BVH only
-        if (p.bvh_width != 2) return hipErrorInvalidValue;
-        if (p.flags & 0x4u) return launch_width<false, 4>(p, count, stream);  // RRT_FLAG_BOOK3
-        if (p.n_media) return launch_width<false, 3>(p, count, stream);
-        return p.n_quads ? launch_width<false, 2>(p, count, stream) : launch_width<false, 1>(p, count, stream);
+    // Variant choice (plan_launch): BVH width, smallest LDS stack that holds the traversal, and the
+    // scene staged in LDS when the BVH + spheres fit the per-block budget (RTOW: ~20-26 KB).
+    const LaunchPlan pl = plan_launch(p);
+    if (!pl.ok) return hipErrorInvalidValue;  // scene creation refuses such a scene
+    switch (pl.kclass) {
+    case 4: return launch_width<false, 4>(p, pl, count, stream);
+    case 3: return launch_width<false, 3>(p, pl, count, stream);
+    case 2: return launch_width<false, 2>(p, pl, count, stream);
+    case 1: return launch_width<false, 1>(p, pl, count, stream);
+    case kBook1Diffuse: return launch_width<false, kBook1Diffuse>(p, pl, count, stream);
+    case kBook1Untextured: return launch_width<false, kBook1Untextured>(p, pl, count, stream);
+    default: break;
     }
-    if (p.bvh_width == 4) return launch_width<true, 0>(p, count, stream);
-    // Scenes without image textures run the kernel with the texture path compiled out: C2 +1.0 %;
-    // for scenes read from L2 (C5) it removes the 7-wave kernel's 4 spilled VGPRs (20 B of scratch
-    // per lane, written and read back through memory) at equal time.
-    if (!p.specular && p.scene_in_lds) return launch_width<false, kBook1Diffuse>(p, count, stream);
-    if (!p.image_tex) return launch_width<false, kBook1Untextured>(p, count, stream);
-    return launch_width<false, 0>(p, count, stream);
+    return p.bvh_width == 4 ? launch_width<true, 0>(p, pl, count, stream) : launch_width<false, 0>(p, pl, count, stream);
 }
 
 // One launch (+ combine) per sample pass of at most p.pass_chunks chunks, in chunk order.
