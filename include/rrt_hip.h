@@ -617,6 +617,67 @@ int32_t rrt_testing_trig32_check(double *out);
  * (tests/test_gpu_trig32.py: 0 differ). */
 int32_t rrt_testing_sqrt64_check(uint64_t *out);
 
+/* Test support, not part of the drop-in (no reference counterpart; RRT_ABI_VERSION is unchanged and
+ * the Rust shim does not bind it): the f32 kernel's own numeric building blocks (rrt_kernel.hip)
+ * applied elementwise on the device, so tests can choose their arguments (tests/test_gpu_device_ops.py
+ * compares every result bit for bit with the oracle's f32 twin). `in` holds n rows of f32 columns,
+ * `out` receives n rows of 32-bit words (f32 bits unless noted); host pointers, copied inside.
+ *   op          in columns                        out columns
+ *   SIN COS LOG ACOS   x                          f(x)                    (rrt_sinf, rrt_cosf, rrt_logf, rrt_acosf)
+ *   ATAN2       y, x                              rrt_atan2f(y, x)
+ *   DIV_A       n, a                              div_by_a<false>(n) on ra = refine_ra(a), div_by_a<true>(n)
+ *                                                 (the former when ra = 0), the IEEE n / a, ra
+ *   DIV_CONST   x                                 div_by_const(x, 2 pi), IEEE x / (2 pi), div_by_const(x, pi), IEEE x / pi
+ *   FLOOR_I32   x                                 floor_i32(x) (i32)
+ *   CHECKER     inv_scale, p.xyz                  checker_even (u32 0 / 1)
+ *   PERLIN      p.xyz                             (perlin_noise, noise_value) x 4: generic pointer with the corner
+ *                                                 loop unrolled, rolled; the LDS pointer unrolled, rolled.
+ *                                                 aux: one RrtPerlin table, then the f32 scale (packed into the
+ *                                                 device table by scene creation's code, staged into LDS as the
+ *                                                 render stages it)
+ *   VEC         v.xyz, n.xyz, e, cosine, r0       unit(v) 3, reflect(v, n) 3, refract(v, n, e) 3,
+ *                                                 reflectance_r0(cosine, r0), onb_transform(n, v) 3
+ *   QUAD        o.xyz, d.xyz, tmin, closest, j    quad_hit of quad j over [tmin, closest]: hit (u32), t (0 on a miss).
+ *                                                 aux: u32 count, 12 bytes of padding, then count RrtQuad records
+ *                                                 (derived planes formed by scene creation's code); j < count
+ *   SPHERE      o.xyz, d.xyz, c.xyz, r, closest   for the book-1 record (r * r stored), then the book-2 record (r):
+ *                                                 exact_root<false>, exact_root<true> (the former when the ray's ra = 0),
+ *                                                 test_range's decision against `closest` with the IEEE division
+ *                                                 (hit u32, t), the same with the per-ray reciprocal (hit, t); last
+ *                                                 sphere_root over (0.001, inf) (u32). 13 words. r < 0 is taken as 0.
+ * div_by_a<true> / <false> (and with them exact_root<true> / <false> and test_range's two divisions)
+ * are the same function since div_by_a guards its own range; both instantiations are still run.
+ * Every input, NaN and infinities included, is ordinary arithmetic. */
+enum RrtDeviceOp {
+    RRT_OP_SIN = 0,
+    RRT_OP_COS = 1,
+    RRT_OP_LOG = 2,
+    RRT_OP_ACOS = 3,
+    RRT_OP_ATAN2 = 4,
+    RRT_OP_DIV_A = 5,
+    RRT_OP_DIV_CONST = 6,
+    RRT_OP_FLOOR_I32 = 7,
+    RRT_OP_CHECKER = 8,
+    RRT_OP_PERLIN = 9,
+    RRT_OP_VEC = 10,
+    RRT_OP_QUAD = 11,
+    RRT_OP_SPHERE = 12
+};
+int32_t rrt_testing_device_ops(uint32_t op, uint32_t n, const void *in, void *out, const void *aux);
+
+/* Test support, not part of the drop-in: the sphere tests' root division (rrt_kernel.hip div_by_a on
+ * the per-ray reciprocal refine_ra(a)) against the IEEE quotient q = n / a, for each of the n_a <= 48
+ * divisors a over every f32 bit pattern n, both div_by_a<false> and <true>; and div_by_const on the
+ * device. "Same" is bit equality or both NaN; a root t is accepted when 0.001 < t < inf. out (8 x u64):
+ *   [0] a in [2^-64, 2^64], finite |n| >= 2^-103, q finite and |q| >= 2^-126: results that differ from q
+ *   [1] a in that range, every n: accepted(result) != accepted(q), or both accepted and not the same
+ *   [2] a outside it (ra = 0): div_by_a<false> differs from q
+ *   [3] a in the range, q subnormal or zero: results whose bits differ from q's (no decision reads them)
+ *   [4], [5] x = 0 and every f32 x in [2^-100, 8] whose div_by_const(x, 2 pi) / (x, pi) differs from x / c
+ *   [6] (n, a) pairs checked (n_a << 32), [7] x values checked
+ * (tests/test_gpu_device_ops.py: [0], [1], [2], [4], [5] are 0). */
+int32_t rrt_testing_div_check(const float *a_values, uint32_t n_a, uint64_t *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -78,6 +78,12 @@ def load() -> ctypes.CDLL:
     lib.oracle_acos_atan2_f64.argtypes = [c_uint32, P, P, P, P]
     lib.oracle_acos_atan2_f32.restype = None
     lib.oracle_acos_atan2_f32.argtypes = [c_float, c_float, P, P]
+    for name, args in (("oracle_acos_f32", [c_uint32, P, P]), ("oracle_atan2_f32", [c_uint32, P, P]),
+                       ("oracle_floor_i32", [c_uint32, P, P]), ("oracle_vec_f32", [c_uint32, P, P]),
+                       ("oracle_quad_hit_f32", [c_uint32, P, c_uint32, P, P, P]),
+                       ("oracle_sphere_hit_f32", [c_uint32, P, P, P])):
+        getattr(lib, name).restype = None
+        getattr(lib, name).argtypes = args
     _LIB = lib
     return lib
 
@@ -314,6 +320,62 @@ def acos_atan2_f64(x, y):
     a, b = np.zeros_like(xs), np.zeros_like(xs)
     lib.oracle_acos_atan2_f64(xs.size, _p(xs), _p(ys), _p(a), _p(b))
     return a, b
+
+
+def _rows(x, cols):
+    return np.ascontiguousarray(x, dtype=np.float32).reshape(-1, cols)
+
+
+def acos_f32(x):
+    """The f32 Cephes acos of the kernel (rrt_acosf) at each element of x."""
+    xs = _rows(x, 1)
+    out = np.zeros(len(xs), np.float32)
+    load().oracle_acos_f32(len(xs), _p(xs), _p(out))
+    return out
+
+
+def atan2_f32(yx):
+    """The f32 Cephes atan2 of the kernel (rrt_atan2f) at each row (y, x)."""
+    r = _rows(yx, 2)
+    out = np.zeros(len(r), np.float32)
+    load().oracle_atan2_f32(len(r), _p(r), _p(out))
+    return out
+
+
+def floor_i32(x):
+    """`x.floor() as i32` (saturating, NaN -> 0) at each element of x."""
+    xs = _rows(x, 1)
+    out = np.zeros(len(xs), np.int32)
+    load().oracle_floor_i32(len(xs), _p(xs), _p(out))
+    return out
+
+
+def vec_f32(rows):
+    """Rows (v, n, e, cosine, r0) -> (n, 13): unit_vector(v), reflect(v, n), refract(v, n, e),
+    Schlick's reflectance at r0, Onb::new(n).transform(v), in the f32 twin arithmetic."""
+    r = _rows(rows, 9)
+    out = np.zeros((len(r), 13), np.float32)
+    load().oracle_vec_f32(len(r), _p(r), _p(out))
+    return out
+
+
+def quad_hit_f32(quads, rows):
+    """Rows (o, d, tmin, closest, quad index) over RrtQuad records -> (hit, t) arrays (f32 twin)."""
+    q = np.ascontiguousarray(quads)
+    assert q.dtype.itemsize == 64, "RrtQuad records"
+    r = _rows(rows, 9)
+    hit, t = np.zeros(len(r), np.uint32), np.zeros(len(r), np.float32)
+    load().oracle_quad_hit_f32(len(q), _p(q), len(r), _p(r), _p(hit), _p(t))
+    return hit, t
+
+
+def sphere_hit_f32(rows):
+    """Rows (o, d, c, r, closest) -> hit (n, 5), t (n, 4): Sphere::hit over (0.001, inf) as a book-1
+    and a book-2 sphere, over (0.001, closest) for both, and the light pdf's static root (hit only)."""
+    r = _rows(rows, 11)
+    hit, t = np.zeros((len(r), 5), np.uint32), np.zeros((len(r), 4), np.float32)
+    load().oracle_sphere_hit_f32(len(r), _p(r), _p(hit), _p(t))
+    return hit, t
 
 
 def cos_f32(x):

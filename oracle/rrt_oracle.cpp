@@ -120,6 +120,19 @@ template <class T> Vec3<T> refract(Vec3<T> uv, Vec3<T> n, T etai_over_etat) {  /
     const Vec3<T> r_out_parallel = -std::sqrt(std::fabs(T(1) - length_squared(r_out_perp))) * n;
     return r_out_perp + r_out_parallel;
 }
+// Dielectric::reflectance (material.rs:75-80) from its r0 = ((1 - ri) / (1 + ri))^2 on: Schlick's
+// polynomial, powi(5) == x * ((x*x)*(x*x)). The scatter functions and the known-answer hooks all
+// call this one (the kernel's reflectance_r0).
+template <class T> T schlick_at_r0(T cosine, T r0) {
+    const T x = T(1) - cosine;
+    const T x2 = x * x;
+    const T x4 = x2 * x2;
+    return r0 + (T(1) - r0) * (x * x4);
+}
+template <class T> T schlick_r0(T ri) {
+    const T r0 = (T(1) - ri) / (T(1) + ri);
+    return r0 * r0;
+}
 
 // ---- RNG (restatement choice, see header) ---------------------------------------------------
 uint64_t splitmix64(uint64_t z) {
@@ -1376,16 +1389,7 @@ bool scatter(const World<T> &w, PathRng &rng, Vec3<T> d_in, const Record<T> &rec
             const T cos_theta = rmin(-dot(ud, rec.normal), T(1));
             const T sin_theta = std::sqrt(T(1) - cos_theta * cos_theta);
             const bool cannot = ri * sin_theta > T(1);
-            // reflectance (material.rs:75-80): powi(5) == x * ((x*x)*(x*x))
-            auto reflectance = [&](T cosine, T rix) {
-                T r0 = (T(1) - rix) / (T(1) + rix);
-                r0 = r0 * r0;
-                const T x = T(1) - cosine;
-                const T x2 = x * x;
-                const T x4 = x2 * x2;
-                return r0 + (T(1) - r0) * (x * x4);
-            };
-            if (cannot || reflectance(cos_theta, ri) > rng.random_double<T>()) dir = reflect(ud, rec.normal);
+            if (cannot || schlick_at_r0(cos_theta, schlick_r0(ri)) > rng.random_double<T>()) dir = reflect(ud, rec.normal);
             else dir = refract(ud, rec.normal, ri);
             return true;
         }
@@ -1602,12 +1606,7 @@ template <class T> void b3_skip_scatter(const Material<T> &m, PathRng &rng, Vec3
     const T cos_theta = rmin(-dot(ud, rec.normal), T(1));
     const T sin_theta = std::sqrt(T(1) - cos_theta * cos_theta);
     const bool cannot = ri * sin_theta > T(1);
-    T r0 = (T(1) - ri) / (T(1) + ri);
-    r0 = r0 * r0;
-    const T x = T(1) - cos_theta;
-    const T x2 = x * x;
-    const T x4 = x2 * x2;
-    const T refl = r0 + (T(1) - r0) * (x * x4);
+    const T refl = schlick_at_r0(cos_theta, schlick_r0(ri));
     if (cannot || refl > rng.random_double<T>()) dir = reflect(ud, rec.normal);
     else dir = refract(ud, rec.normal, ri);
 }
@@ -2014,10 +2013,7 @@ void oracle_reflect_refract(int f32, const double *v, const double *n, double et
         const Vec3<T> a = reflect(V, N), b = refract(V, N, (T)eta);
         for (int i = 0; i < 3; ++i) { refl[i] = a[i]; refr[i] = b[i]; }
         const T cosine = (T)schlick_cos_eta[0], rix = (T)schlick_cos_eta[1];
-        T r0 = (T(1) - rix) / (T(1) + rix);
-        r0 = r0 * r0;
-        const T x = T(1) - cosine, x2 = x * x, x4 = x2 * x2;
-        schlick_cos_eta[2] = r0 + (T(1) - r0) * (x * x4);
+        schlick_cos_eta[2] = schlick_at_r0(cosine, schlick_r0(rix));
     };
     if (f32) run(0.0f); else run(0.0);
 }
@@ -2080,6 +2076,76 @@ void oracle_book2_textures(int f32, const RrtPerlin *pt, double scale, double in
         }
     };
     if (f32) run(0.0f); else run(0.0);
+}
+
+// ---- array forms of the known-answer hooks in the f32 twin arithmetic: the functions the render
+// uses, row by row, for the device's elementwise checks (tests/test_gpu_device_ops.py; the row
+// layouts are those of include/rrt_hip.h rrt_testing_device_ops) ------------------------------------
+void oracle_acos_f32(uint32_t n, const float *x, float *out) {
+    for (uint32_t i = 0; i < n; ++i) out[i] = cephes_acosf(x[i]);
+}
+
+void oracle_atan2_f32(uint32_t n, const float *yx, float *out) {  // rows (y, x)
+    for (uint32_t i = 0; i < n; ++i) out[i] = cephes_atan2f(yx[2 * i], yx[2 * i + 1]);
+}
+
+void oracle_floor_i32(uint32_t n, const float *x, int32_t *out) {
+    for (uint32_t i = 0; i < n; ++i) out[i] = floor_as_i32(x[i]);
+}
+
+// rows (v, n, e, cosine, r0) -> unit_vector(v), reflect(v, n), refract(v, n, e), Schlick's
+// reflectance at the given r0 (material.rs:75-80 after its r0), Onb::new(n).transform(v)
+void oracle_vec_f32(uint32_t n, const float *in, float *out) {
+    using T = float;
+    for (uint32_t i = 0; i < n; ++i) {
+        const float *x = in + 9 * (size_t)i;
+        float *r = out + 13 * (size_t)i;
+        const Vec3<T> v = mk(x[0], x[1], x[2]), nn = mk(x[3], x[4], x[5]);
+        const Vec3<T> a = unit_vector(v), b = reflect(v, nn), c = refract(v, nn, x[6]), d = onb_transform(nn, v);
+        for (int k = 0; k < 3; ++k) r[k] = a[k], r[3 + k] = b[k], r[6 + k] = c[k], r[10 + k] = d[k];
+        r[9] = schlick_at_r0<T>(x[7], x[8]);
+    }
+}
+
+// rows (o, d, tmin, closest, quad index) -> Quad::hit over [tmin, closest]: hit, t (0 on a miss)
+void oracle_quad_hit_f32(uint32_t n_quads, const RrtQuad *quads, uint32_t n, const float *in, uint32_t *hit, float *t_out) {
+    using T = float;
+    std::vector<QuadT<T>> qs;
+    for (uint32_t j = 0; j < n_quads; ++j) qs.push_back(make_quad<T>(quads[j]));
+    for (uint32_t i = 0; i < n; ++i) {
+        const float *x = in + 9 * (size_t)i;
+        const uint32_t j = (uint32_t)x[8];
+        T t = T(0);
+        const bool h = j < n_quads && World<T>::quad_hit(qs[j], mk(x[0], x[1], x[2]), mk(x[3], x[4], x[5]), Interval<T>{x[6], x[7]}, t);
+        hit[i] = h ? 1u : 0u;
+        t_out[i] = h ? t : T(0);
+    }
+}
+
+// rows (o, d, c, r, closest) -> Sphere::hit (r < 0 taken as 0, as the scene builders store it): over
+// (0.001, inf) as a book-1 and as a book-2 sphere (zero motion, time 0), over (0.001, closest) for
+// both, and the static-sphere root over (0.001, inf) of the light pdf. hit: 5 per row, t: 4 per row
+// (0 on a miss).
+void oracle_sphere_hit_f32(uint32_t n, const float *in, uint32_t *hit, float *t_out) {
+    using T = float;
+    const T inf = std::numeric_limits<T>::infinity();
+    World<T> w;
+    w.spheres.push_back(Sphere<T>{});
+    for (uint32_t i = 0; i < n; ++i) {
+        const float *x = in + 11 * (size_t)i;
+        const Vec3<T> O = mk(x[0], x[1], x[2]), D = mk(x[3], x[4], x[5]), c = mk(x[6], x[7], x[8]);
+        const T r = std::max(x[9], T(0));
+        w.spheres[0] = Sphere<T>{c, r, 0, from_points(c - mk(r, r, r), c + mk(r, r, r)), mk(T(0), T(0), T(0))};
+        for (int k = 0; k < 4; ++k) {
+            w.book2 = (k & 1) != 0;
+            T t = T(0);
+            const bool h = w.hit_sphere(0, O, D, T(0), Interval<T>{T(0.001f), k < 2 ? inf : x[10]}, t, nullptr);
+            hit[5 * (size_t)i + k] = h ? 1u : 0u;
+            t_out[4 * (size_t)i + k] = h ? t : T(0);
+        }
+        T t;
+        hit[5 * (size_t)i + 4] = World<T>::sphere_root(c, r, O, D, Interval<T>{T(0.001f), inf}, t) ? 1u : 0u;
+    }
 }
 
 }  // extern "C"

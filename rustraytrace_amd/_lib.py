@@ -84,7 +84,16 @@ EXPORTED_SYMBOLS = (
     "rrt_testing_recip_check",
     "rrt_testing_trig32_check",
     "rrt_testing_sqrt64_check",
+    "rrt_testing_device_ops",
+    "rrt_testing_div_check",
 )
+
+# == RrtDeviceOp (include/rrt_hip.h, test support): op -> (code, f32 columns in, 32-bit words out)
+DEVICE_OPS = {
+    "SIN": (0, 1, 1), "COS": (1, 1, 1), "LOG": (2, 1, 1), "ACOS": (3, 1, 1), "ATAN2": (4, 2, 1),
+    "DIV_A": (5, 2, 4), "DIV_CONST": (6, 1, 4), "FLOOR_I32": (7, 1, 1), "CHECKER": (8, 4, 1),
+    "PERLIN": (9, 3, 8), "VEC": (10, 9, 13), "QUAD": (11, 9, 2), "SPHERE": (12, 11, 13),
+}
 
 
 class RrtTexture(ctypes.Structure):
@@ -214,6 +223,35 @@ def launch_plan(**query) -> dict:
     return out.as_dict()
 
 
+def device_ops(op: str, rows, quads=None, perlin=None, scale=0.0) -> np.ndarray:
+    """rrt_testing_device_ops (test support): the f32 kernel's building block `op` (a DEVICE_OPS
+    name) on each row of `rows` (float32, n x columns in); returns the n x words-out results as
+    uint32 (view as float32 where the op returns floats). quads: QUAD_DTYPE records for QUAD;
+    perlin: one PERLIN_DTYPE table and `scale` for PERLIN."""
+    code, cin, cout = DEVICE_OPS[op]
+    x = np.ascontiguousarray(rows, dtype=np.float32).reshape(-1, cin)
+    out = np.zeros((len(x), cout), dtype=np.uint32)
+    aux = None
+    if op == "QUAD":
+        q = np.ascontiguousarray(quads, dtype=QUAD_DTYPE)
+        aux = np.zeros(16 + q.nbytes, dtype=np.uint8)
+        aux[:4] = np.frombuffer(np.uint32(len(q)).tobytes(), dtype=np.uint8)
+        aux[16:] = np.frombuffer(q.tobytes(), dtype=np.uint8)
+    elif op == "PERLIN":
+        t = np.ascontiguousarray(perlin, dtype=PERLIN_DTYPE).reshape(-1)[:1]
+        aux = np.frombuffer(t.tobytes() + np.float32(scale).tobytes(), dtype=np.uint8).copy()
+    check(load().rrt_testing_device_ops(code, len(x), ptr(x), ptr(out), ptr(aux)))
+    return out
+
+
+def div_check(a_values) -> list:
+    """rrt_testing_div_check (test support): the eight counters for the divisors a_values."""
+    a = np.ascontiguousarray(a_values, dtype=np.float32).ravel()
+    out = (ctypes.c_uint64 * 8)(*([7] * 8))
+    check(load().rrt_testing_div_check(ptr(a), len(a), out))
+    return [int(v) for v in out]
+
+
 class RrtError(RuntimeError):
     """A non-zero return of the C-ABI (the Rust shim's Err(rrt_hip_last_error()))."""
 
@@ -291,6 +329,8 @@ def load() -> ctypes.CDLL:
         "rrt_testing_recip_check": (c_int32, [P]),
         "rrt_testing_trig32_check": (c_int32, [P]),
         "rrt_testing_sqrt64_check": (c_int32, [P]),
+        "rrt_testing_device_ops": (c_int32, [c_uint32, c_uint32, P, P, P]),
+        "rrt_testing_div_check": (c_int32, [P, c_uint32, P]),
     }
     experiment = "RRT_LIB_PATH" in os.environ  # A/B of older builds: tolerate symbols they lack
     for name, (res, args) in sig.items():

@@ -1176,6 +1176,35 @@ int32_t rrt_device_count(int32_t *count) {
 
 }  // extern "C"
 
+// A quad with its derived plane (quad.rs:21-37 in f64: n = cross(u, v), normal = n * (1/|n|),
+// D = dot(normal, q), w = n * (1/dot(n, n)); Vec3 / f64 is `(1/rhs) * v`, vec3.rs:142-148), rounded
+// to the device record. Scene creation and rrt_testing_device_ops form their records here.
+static rrt::GQuad form_gquad(const RrtQuad &qd) {
+    const D3 q = d3(qd.q[0], qd.q[1], qd.q[2]), u = d3(qd.u[0], qd.u[1], qd.u[2]), v = d3(qd.v[0], qd.v[1], qd.v[2]);
+    const D3 n = cross(u, v);
+    const double nn = n.x * n.x + n.y * n.y + n.z * n.z;
+    const D3 normal = n * (1.0 / std::sqrt(nn));
+    const double dd = normal.x * q.x + normal.y * q.y + normal.z * q.z;
+    const D3 w = n * (1.0 / nn);
+    rrt::GQuad g;
+    g.q = make_float4(qd.q[0], qd.q[1], qd.q[2], (float)dd);
+    g.u = make_float4(qd.u[0], qd.u[1], qd.u[2], 0.0f);
+    g.v = make_float4(qd.v[0], qd.v[1], qd.v[2], 0.0f);
+    g.n = make_float4((float)normal.x, (float)normal.y, (float)normal.z, 0.0f);
+    g.w = make_float4((float)w.x, (float)w.y, (float)w.z, 0.0f);
+    return g;
+}
+
+// A Perlin table packed for the device (GPerlin); false when a permutation entry exceeds 255.
+static bool pack_perlin(const RrtPerlin &src, rrt::GPerlin &dst) {
+    for (int i = 0; i < 256; ++i) {
+        if (src.perm_x[i] > 255 || src.perm_y[i] > 255 || src.perm_z[i] > 255) return false;
+        dst.randvec[i] = make_float4(src.randvec[i][0], src.randvec[i][1], src.randvec[i][2], 0.0f);
+        dst.perm[i] = (uint32_t)src.perm_x[i] | ((uint32_t)src.perm_y[i] << 8) | ((uint32_t)src.perm_z[i] << 16);
+    }
+    return true;
+}
+
 static int32_t scene_create(const RrtCamera *cam, const RrtSphere *spheres, uint32_t n_spheres,
                             const RrtMaterial *materials, uint32_t n_materials, const RrtTexture *textures,
                             uint32_t n_textures, const RrtSceneExt *ext, uint32_t flags, int32_t device,
@@ -1304,8 +1333,7 @@ static int32_t scene_create(const RrtCamera *cam, const RrtSphere *spheres, uint
     }
     // Spheres in BVH leaf order, each with a copy of its material record: a hit reads one
     // 32-B record at the primitive's index (no dependent material-index fetch).
-    // Quads with their derived plane (quad.rs:21-37 in f64: n = cross(u, v), normal = n * (1/|n|),
-    // D = dot(normal, q), w = n * (1/dot(n, n)); Vec3 / f64 is `(1/rhs) * v`, vec3.rs:142-148).
+    // Quads with their derived plane (form_gquad).
     // GQuad array: the scene's quads, media boundary quads, book-3 light quads
     std::vector<RrtQuad> light_quads;
     std::vector<rrt::GLight> glights(book3 ? ex.n_lights : 0);
@@ -1328,18 +1356,7 @@ static int32_t scene_create(const RrtCamera *cam, const RrtSphere *spheres, uint
         const RrtQuad &qd = j < n_quads ? quads[j]
                             : j < n_quads + ex.n_bquads ? ex.bquads[j - n_quads]
                                                         : light_quads[j - n_quads - ex.n_bquads];
-        const D3 q = d3(qd.q[0], qd.q[1], qd.q[2]), u = d3(qd.u[0], qd.u[1], qd.u[2]), v = d3(qd.v[0], qd.v[1], qd.v[2]);
-        const D3 n = cross(u, v);
-        const double nn = n.x * n.x + n.y * n.y + n.z * n.z;
-        const D3 normal = n * (1.0 / std::sqrt(nn));
-        const double dd = normal.x * q.x + normal.y * q.y + normal.z * q.z;
-        const D3 w = n * (1.0 / nn);
-        rrt::GQuad &g = gquads[j];
-        g.q = make_float4(qd.q[0], qd.q[1], qd.q[2], (float)dd);
-        g.u = make_float4(qd.u[0], qd.u[1], qd.u[2], 0.0f);
-        g.v = make_float4(qd.v[0], qd.v[1], qd.v[2], 0.0f);
-        g.n = make_float4((float)normal.x, (float)normal.y, (float)normal.z, 0.0f);
-        g.w = make_float4((float)w.x, (float)w.y, (float)w.z, 0.0f);
+        gquads[j] = form_gquad(qd);
     }
     // Primitives in BVH leaf order (spheres, then quads as index n_spheres + j), each with a
     // copy of its material record: a hit reads one 32-B record at the primitive's index.
@@ -1395,13 +1412,7 @@ static int32_t scene_create(const RrtCamera *cam, const RrtSphere *spheres, uint
     }
     std::vector<rrt::GPerlin> perlin(n_perlin);
     for (uint32_t t = 0; t < n_perlin; ++t) {
-        const RrtPerlin &src = ext->perlin[t];
-        for (int i = 0; i < 256; ++i) {
-            if (src.perm_x[i] > 255 || src.perm_y[i] > 255 || src.perm_z[i] > 255)
-                return fail(RRT_E_INVALID, "Perlin permutation entry > 255");
-            perlin[t].randvec[i] = make_float4(src.randvec[i][0], src.randvec[i][1], src.randvec[i][2], 0.0f);
-            perlin[t].perm[i] = (uint32_t)src.perm_x[i] | ((uint32_t)src.perm_y[i] << 8) | ((uint32_t)src.perm_z[i] << 16);
-        }
+        if (!pack_perlin(ext->perlin[t], perlin[t])) return fail(RRT_E_INVALID, "Perlin permutation entry > 255");
     }
     std::vector<rrt::GTexture> texs(n_textures);
     size_t pool = 0;
@@ -1896,6 +1907,85 @@ extern "C" int32_t rrt_testing_trig32_check(double *out) {
     std::memcpy(&out[1], &h[1], sizeof(double));
     out[2] = bounds[0];
     out[3] = bounds[1];
+    return RRT_OK;
+}
+
+// Test support (rrt_testing_device_ops): rows in, rows out; the aux records are formed by the code
+// scene creation uses (form_gquad, pack_perlin).
+extern "C" int32_t rrt_testing_device_ops(uint32_t op, uint32_t n, const void *in, void *out, const void *aux) {
+    uint32_t cin = 0, cout = 0;
+    rrt::device_op_columns(op, cin, cout);
+    if (cin == 0) return fail(RRT_E_INVALID, "rrt_testing_device_ops: unknown op " + std::to_string(op));
+    if (n == 0) return RRT_OK;
+    if (!in || !out) return fail(RRT_E_INVALID, "rrt_testing_device_ops: null in or out");
+    if ((uint64_t)n * std::max(cin, cout) >= (1ull << 31)) return fail(RRT_E_INVALID, "rrt_testing_device_ops: too many rows");
+    std::vector<uint8_t> aux_bytes;
+    uint32_t n_aux = 0;
+    float scale = 0.0f;
+    if (op == RRT_OP_PERLIN) {
+        if (!aux) return fail(RRT_E_INVALID, "rrt_testing_device_ops: PERLIN needs a table");
+        RrtPerlin table;
+        std::memcpy(&table, aux, sizeof(table));
+        std::memcpy(&scale, static_cast<const uint8_t *>(aux) + sizeof(RrtPerlin), sizeof(float));
+        rrt::GPerlin g;
+        if (!pack_perlin(table, g)) return fail(RRT_E_INVALID, "Perlin permutation entry > 255");
+        aux_bytes.resize(sizeof(g));
+        std::memcpy(aux_bytes.data(), &g, sizeof(g));
+        n_aux = 1;
+    } else if (op == RRT_OP_QUAD) {
+        if (!aux) return fail(RRT_E_INVALID, "rrt_testing_device_ops: QUAD needs quads");
+        std::memcpy(&n_aux, aux, sizeof(uint32_t));
+        if (n_aux == 0 || n_aux > 65536u) return fail(RRT_E_INVALID, "rrt_testing_device_ops: quad count");
+        aux_bytes.resize((size_t)n_aux * sizeof(rrt::GQuad));
+        for (uint32_t j = 0; j < n_aux; ++j) {
+            RrtQuad qd;
+            std::memcpy(&qd, static_cast<const uint8_t *>(aux) + 16 + (size_t)j * sizeof(RrtQuad), sizeof(qd));
+            const rrt::GQuad g = form_gquad(qd);
+            std::memcpy(aux_bytes.data() + (size_t)j * sizeof(g), &g, sizeof(g));
+        }
+        const float *rows = static_cast<const float *>(in);
+        for (uint32_t i = 0; i < n; ++i) {
+            const float j = rows[(size_t)i * cin + 8];
+            if (!(j >= 0.0f && j < (float)n_aux)) return fail(RRT_E_INVALID, "rrt_testing_device_ops: quad index out of range");
+        }
+    }
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count < 1) return fail(RRT_E_NODEV, "no HIP device");
+    const size_t in_bytes = (size_t)n * cin * 4u, out_bytes = (size_t)n * cout * 4u;
+    void *d_in = nullptr, *d_out = nullptr, *d_aux = nullptr;
+    hipError_t e = hipMalloc(&d_in, in_bytes);
+    if (e == hipSuccess) e = hipMalloc(&d_out, out_bytes);
+    if (e == hipSuccess && !aux_bytes.empty()) e = hipMalloc(&d_aux, aux_bytes.size());
+    if (e == hipSuccess) e = hipMemcpy(d_in, in, in_bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess && d_aux) e = hipMemcpy(d_aux, aux_bytes.data(), aux_bytes.size(), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(d_out, 0, out_bytes);
+    if (e == hipSuccess)
+        e = rrt::launch_device_ops(op, n, static_cast<const float *>(d_in), static_cast<uint32_t *>(d_out), d_aux, n_aux,
+                                   scale, nullptr);
+    if (e == hipSuccess) e = hipMemcpy(out, d_out, out_bytes, hipMemcpyDeviceToHost);
+    (void)hipFree(d_in);
+    (void)hipFree(d_out);
+    (void)hipFree(d_aux);
+    if (e != hipSuccess) return fail(RRT_E_HIP, std::string("rrt_testing_device_ops: ") + hipGetErrorString(e));
+    return RRT_OK;
+}
+
+extern "C" int32_t rrt_testing_div_check(const float *a_values, uint32_t n_a, uint64_t *out) {
+    if (!a_values || !out) return fail(RRT_E_INVALID, "null a_values or out");
+    if (n_a == 0 || n_a > 48u) return fail(RRT_E_INVALID, "rrt_testing_div_check: 1 to 48 divisors");
+    float *d_a = nullptr;
+    unsigned long long *d = nullptr;
+    hipError_t e = hipMalloc((void **)&d_a, n_a * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void **)&d, 8 * sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMemcpy(d_a, a_values, n_a * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(d, 0, 8 * sizeof(unsigned long long));
+    if (e == hipSuccess) e = rrt::launch_div_check(d_a, n_a, d, nullptr);
+    unsigned long long h[8] = {};
+    if (e == hipSuccess) e = hipMemcpy(h, d, sizeof(h), hipMemcpyDeviceToHost);
+    (void)hipFree(d_a);
+    (void)hipFree(d);
+    if (e != hipSuccess) return fail(RRT_E_HIP, std::string("rrt_testing_div_check: ") + hipGetErrorString(e));
+    for (int i = 0; i < 8; ++i) out[i] = h[i];
     return RRT_OK;
 }
 static bool device_wrap() { return g_device_wrap.load(); }

@@ -356,6 +356,16 @@ hipError_t launch_quantize(const float *d_accum, uint8_t *d_rgb8, uint32_t n_pix
 // quotient (and sqrt_rn_big against the IEEE sqrt) over every f32 bit pattern; d_out: 3 zeroed u64
 // mismatch counters
 hipError_t launch_recip_check(unsigned long long *d_out, hipStream_t stream);
+// Test support (rrt_testing_device_ops): the f32 kernel's own building blocks applied elementwise.
+// device_op_columns: the 32-bit words per row of `in` and `out` for an RrtDeviceOp (0, 0: no such
+// op). d_aux: one GPerlin table (PERLIN, with `scale`) or n_aux GQuad records (QUAD).
+void device_op_columns(uint32_t op, uint32_t &cols_in, uint32_t &cols_out);
+hipError_t launch_device_ops(uint32_t op, uint32_t n, const float *d_in, uint32_t *d_out, const void *d_aux,
+                             uint32_t n_aux, float scale, hipStream_t stream);
+// Test support (rrt_testing_div_check): div_by_a on refine_ra(a) against the IEEE quotient over every
+// f32 numerator for each of the n_a divisors, and div_by_const over x = 0 and [2^-100, 8]; d_out: 8
+// zeroed u64 counters
+hipError_t launch_div_check(const float *d_a, uint32_t n_a, unsigned long long *d_out, hipStream_t stream);
 // Test support (rrt_testing_trig32_check, rrt_books64.hip): the largest errors of the device's acosf
 // over [-1, 1] and atanf over [0, 1] against its f64 acos / atan (d_out: 2 zeroed u64 holding f64
 // bits), and the error bounds the f64 kernel's texel enclosures assume (bounds[2])

@@ -23,6 +23,7 @@
 // (T <- T*att[*1/p]); the reference multiplies back-to-front through its recursion —
 // equal in exact arithmetic (documented in DESIGN.md).
 #include "rrt_internal.h"
+#include "../../include/rrt_hip.h"  // RrtDeviceOp (the test-only rrt_device_ops kernel)
 
 #include <algorithm>
 #include <cstdio>
@@ -376,13 +377,26 @@ __device__ __forceinline__ RayK ray_consts(V3 o, V3 d) {
 
 // n / a, correctly rounded: the quotient steps of the compiler's IEEE f32 division expansion
 // (q = n*r, two remainder corrections by fma) on the per-ray reciprocal. For a in
-// [2^-64, 2^64] the expansion's v_div_scale / v_div_fmas / v_div_fixup are identities except
-// when |n| < 2^-103, where both results are below the 0.001 acceptance bound, so every
-// accept/reject decision and every accepted root equals the IEEE quotient (the oracle's).
+// [2^-64, 2^64] the expansion's v_div_scale / v_div_fmas / v_div_fixup are identities while the
+// remainders are exact and the first quotient is finite. Two ends are not: below |n| = 2^-102 a
+// remainder loses bits to underflow (the last ulp of quotients under 2^-38, found on the device for
+// n in [2^-103, 2^-102)), and a quotient that rounds to the largest float can have n * ra = inf
+// (ra rounded up), which the corrections turn into NaN where IEEE accepts 3.4e38. So a first quotient
+// outside [2^-30, inf) — zero, tiny, infinite, NaN, and every n when ra = 0 (a outside the range) —
+// takes the IEEE division instead: a branch no ray of a sane scene takes (roots below 1e-9 or above
+// 3.4e38). The remainders are exact from |q0| >= 2^-38 on (a * q0 is a multiple of 2^-148 there);
+// the bound leaves eight binades above that. With it the result is the IEEE quotient (the oracle's)
+// for every f32 n, bit for bit: exhaustive over n on the device for 48 divisors, rrt_testing_div_check,
+// tests/test_gpu_device_ops.py. Since the guard, kFast no longer changes anything: div_by_a<true> and
+// div_by_a<false> are the same function (before it, <false> tested ra == 0 and <true> took no
+// branch). The parameter stays because exact_root / test_range pass their kFastDiv through and the
+// lazy roots (RRT_LAZY_ROOT) still tell the two apart; the device checks run both instantiations,
+// which now can only agree.
 template <bool kFast = false>
 __device__ __forceinline__ float div_by_a(float n, const RayK &rk) {
-    if (!kFast && rk.ra == 0.0f) return n / rk.a;
     const float q0 = n * rk.ra;
+    const float m = __builtin_fabsf(q0);
+    if (!(m >= 0x1.0p-30f && m < __builtin_inff())) return n / rk.a;
     const float e0 = __builtin_fmaf(-rk.a, q0, n);
     const float q1 = __builtin_fmaf(e0, rk.ra, q0);
     const float e1 = __builtin_fmaf(-rk.a, q1, n);
@@ -643,8 +657,8 @@ __device__ __forceinline__ void lazy_finish(const PR &prim_cr, V3 o, V3 d, const
 // `skip` is the primitive the ray is leaving (exit_skip): it can never be accepted, so it is left
 // out of the loop — a lane whose range holds it runs one iteration less — but the counting
 // variant still counts it as a test, like the oracle's hit_prim (tests count every primitive of
-// the range). kFastDiv: every active lane's |d|^2 is in the range of the per-ray reciprocal (the
-// caller checked it wave-wide), so the root divisions take no branch.
+// the range). kFastDiv: with the lazy roots, every active lane's |d|^2 is in the range of the per-ray
+// reciprocal (the caller checked it wave-wide); otherwise always set: div_by_a guards itself.
 template <bool kCount, bool kFastDiv, class PR>
 __device__ __forceinline__ void test_range(const PR &prim_cr, int first, int count, V3 o, V3 d, const RayK &rk,
                                            int skip, float &closest, int &hit_prim, float &lo, Counters &cnt) {
@@ -867,11 +881,16 @@ __device__ __forceinline__ void trav_leaves(const PR &prims, Leaves lv, V3 o, V3
     RayK rk = rk_;
     if (!kHoldRa) rk.ra = refine_ra(rk.a);
     const int first = (int)(lv & kLinkFirstMask), count = (int)(lv >> kLinkCountShift);
-    if (__ballot(rk.ra == 0.0f) == 0) {
-        test_range<kCount, true>(prims, first, count, o, d, rk, skip, t.closest, t.hit_prim, t.lo, cnt);
-        return;
+    // div_by_a guards itself (an out-of-range a has ra = 0 and takes the IEEE division there), so only
+    // the lazy roots' interval arithmetic (RRT_LAZY_ROOT builds) still needs the wave-wide range test
+    // and the kFastDiv = false loop; the shipped build has the one loop
+    if constexpr (RRT_LAZY_ROOT) {
+        if (__ballot(rk.ra == 0.0f) != 0) {
+            test_range<kCount, false>(prims, first, count, o, d, rk, skip, t.closest, t.hit_prim, t.lo, cnt);
+            return;
+        }
     }
-    test_range<kCount, false>(prims, first, count, o, d, rk, skip, t.closest, t.hit_prim, t.lo, cnt);
+    test_range<kCount, true>(prims, first, count, o, d, rk, skip, t.closest, t.hit_prim, t.lo, cnt);
 }
 
 // BVH4 step: test the 4 child boxes, test leaf children's spheres in place, then descend
@@ -1014,7 +1033,11 @@ __device__ __forceinline__ RngState path_rng(const KParams &P, uint32_t x, uint3
 // ---- book-2 procedural textures (the_next_week/texture.rs:39-77, 111-126; perlin.rs) --------
 // f32 sin with only + - * and truncation, bit-reproducible by the oracle: Cephes sinf (octant
 // reduction by 4/pi with the three-part pi/4 of DP1..DP3, minimax polynomials on [0, pi/4]).
-// Arguments >= 2^24 - 1 return 0 (Cephes' total-loss bound); NaN propagates.
+// Arguments >= 2^24 - 1 return 0 (Cephes' total-loss bound); NaN propagates. The accurate domain
+// ends at 8192 (2e-7 absolute below it): above, Cephes reduces by a one-part pi/4 and the error
+// reaches 0.8, so only bit parity with the oracle is claimed there. The callers stay far inside it:
+// phi = 2 pi u < 6.3 (cosine directions, light sampling) and noise_value's scale * p.z + 10 * turb,
+// below 4100 in the committed scenes (|p.z| <= 1000 on perlin_spheres' ground at scale 4, turb < 2).
 __device__ __forceinline__ float rrt_sinf(float xx) {
     float x = xx;
     float sign = 1.0f;
@@ -1155,14 +1178,14 @@ __device__ __forceinline__ float perlin_noise(PP pt, V3 p) {
 #else
 #define RRT_NOISE_FN __forceinline__
 #endif
-template <class PP>
+template <class PP, bool kUnroll = RRT_NOISE_UNROLL>
 __device__ RRT_NOISE_FN float noise_value(PP pt, float scale, V3 p) {
     if (RRT_DEBUG_NOISE_FIXED) return 0.5f + p.z * 0x1.0p-30f;
     float accum = 0.0f, weight = 1.0f;
     V3 tp = p;
 #pragma unroll 1
     for (int o = 0; o < 7; ++o) {
-        accum = accum + weight * perlin_noise(pt, tp);
+        accum = accum + weight * perlin_noise<PP, kUnroll>(pt, tp);
         weight = weight * 0.5f;
         tp = muls(tp, 2.0f);
     }
@@ -2397,10 +2420,207 @@ __global__ __launch_bounds__(256) void rrt_recip_check(unsigned long long *out) 
     if (bad1) atomicAdd(&out[1], (unsigned long long)bad1);
     if (bad2) atomicAdd(&out[2], (unsigned long long)bad2);
 }
+
+// Test support (rrt_testing_device_ops): one of the kernel's own f32 building blocks applied to the
+// rows of `in`, results as 32-bit words in the rows of `out` (columns per op: include/rrt_hip.h
+// RrtDeviceOp, device_op_columns). The functions themselves, in this translation unit, with the
+// megakernel's flags. PERLIN: aux = one GPerlin table, staged into LDS for the LdsPerlin variants as
+// the render stages it; QUAD: aux = n_aux GQuad records.
+__device__ __forceinline__ V3 ld3(const float *p) { return v3(p[0], p[1], p[2]); }
+__device__ __forceinline__ void st3(uint32_t *p, V3 v) {
+    p[0] = __float_as_uint(v.x);
+    p[1] = __float_as_uint(v.y);
+    p[2] = __float_as_uint(v.z);
+}
+// one sphere as a one-record Prims: exact_root in both divisions, and the leaf loop's decision
+// against `closest` (test_range, both divisions)
+template <int kBook2>
+__device__ __forceinline__ void sphere_ops(float4 rec, V3 o, V3 d, const RayK &rk, float closest, uint32_t *r) {
+    const float4 still = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    Prims<kBook2> pr{};
+    pr.cr = &rec;
+    pr.mo = &still;
+    pr.time = 0.0f;
+    const bool fast = rk.ra != 0.0f;
+    const float slow_root = exact_root<false>(pr, 0, o, d, rk);
+    r[0] = __float_as_uint(slow_root);
+    r[1] = __float_as_uint(fast ? exact_root<true>(pr, 0, o, d, rk) : slow_root);
+    Counters cnt{};
+    float t = closest, lo = closest;
+    int prim = -1;
+    test_range<false, false>(pr, 0, 1, o, d, rk, -1, t, prim, lo, cnt);
+    r[2] = prim == 0 ? 1u : 0u;
+    r[3] = __float_as_uint(t);
+    if (fast) {
+        t = lo = closest;
+        prim = -1;
+        test_range<false, true>(pr, 0, 1, o, d, rk, -1, t, prim, lo, cnt);
+    }
+    r[4] = prim == 0 ? 1u : 0u;
+    r[5] = __float_as_uint(t);
+}
+__global__ __launch_bounds__(256) void rrt_device_ops(uint32_t op, uint32_t n, uint32_t cin, uint32_t cout,
+                                                      const float *__restrict__ in, uint32_t *__restrict__ out,
+                                                      const void *__restrict__ aux, uint32_t n_aux, float scale) {
+    __shared__ GPerlin lds_table;
+    if (op == RRT_OP_PERLIN) {
+        const uint32_t *src = reinterpret_cast<const uint32_t *>(aux);
+        uint32_t *dst = reinterpret_cast<uint32_t *>(&lds_table);
+        for (uint32_t k = threadIdx.x; k < sizeof(GPerlin) / 4u; k += 256u) dst[k] = src[k];
+        __syncthreads();
+    }
+    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n; i += gridDim.x * 256u) {
+        const float *x = in + (size_t)i * cin;
+        uint32_t *r = out + (size_t)i * cout;
+        switch (op) {
+        case RRT_OP_SIN: r[0] = __float_as_uint(rrt_sinf(x[0])); break;
+        case RRT_OP_COS: r[0] = __float_as_uint(rrt_cosf(x[0])); break;
+        case RRT_OP_LOG: r[0] = __float_as_uint(rrt_logf(x[0])); break;
+        case RRT_OP_ACOS: r[0] = __float_as_uint(rrt_acosf(x[0])); break;
+        case RRT_OP_ATAN2: r[0] = __float_as_uint(rrt_atan2f(x[0], x[1])); break;
+        case RRT_OP_DIV_A: {
+            RayK rk{};
+            rk.a = x[1];
+            rk.ra = refine_ra(rk.a);
+            const float slow = div_by_a<false>(x[0], rk);
+            r[0] = __float_as_uint(slow);
+            r[1] = __float_as_uint(rk.ra != 0.0f ? div_by_a<true>(x[0], rk) : slow);
+            r[2] = __float_as_uint(x[0] / x[1]);
+            r[3] = __float_as_uint(rk.ra);
+            break;
+        }
+        case RRT_OP_DIV_CONST:
+            r[0] = __float_as_uint(div_by_const(x[0], 2.0f * kPi));
+            r[1] = __float_as_uint(x[0] / (2.0f * kPi));
+            r[2] = __float_as_uint(div_by_const(x[0], kPi));
+            r[3] = __float_as_uint(x[0] / kPi);
+            break;
+        case RRT_OP_FLOOR_I32: r[0] = (uint32_t)floor_i32(x[0]); break;
+        case RRT_OP_CHECKER: r[0] = checker_even(x[0], ld3(x + 1)) ? 1u : 0u; break;
+        case RRT_OP_PERLIN: {
+            const V3 p = ld3(x);
+            const GPerlin *g = reinterpret_cast<const GPerlin *>(aux);
+            const GPerlin *staged = &lds_table;
+            const LdsPerlin l = (LdsPerlin)staged;
+            r[0] = __float_as_uint(perlin_noise<const GPerlin *, true>(g, p));
+            r[1] = __float_as_uint(noise_value<const GPerlin *, true>(g, scale, p));
+            r[2] = __float_as_uint(perlin_noise<const GPerlin *, false>(g, p));
+            r[3] = __float_as_uint(noise_value<const GPerlin *, false>(g, scale, p));
+            r[4] = __float_as_uint(perlin_noise<LdsPerlin, true>(l, p));
+            r[5] = __float_as_uint(noise_value<LdsPerlin, true>(l, scale, p));
+            r[6] = __float_as_uint(perlin_noise<LdsPerlin, false>(l, p));
+            r[7] = __float_as_uint(noise_value<LdsPerlin, false>(l, scale, p));
+            break;
+        }
+        case RRT_OP_VEC: {
+            const V3 v = ld3(x), nn = ld3(x + 3);
+            st3(r, unit(v));
+            st3(r + 3, reflect(v, nn));
+            st3(r + 6, refract(v, nn, x[6]));
+            r[9] = __float_as_uint(reflectance_r0(x[7], x[8]));
+            st3(r + 10, onb_transform(nn, v));
+            break;
+        }
+        case RRT_OP_QUAD: {
+            const uint32_t j = (uint32_t)x[8];
+            float t = 0.0f;
+            const bool hit = j < n_aux && quad_hit(reinterpret_cast<const GQuad *>(aux)[j], ld3(x), ld3(x + 3), x[6], x[7], t);
+            r[0] = hit ? 1u : 0u;
+            r[1] = __float_as_uint(hit ? t : 0.0f);
+            break;
+        }
+        case RRT_OP_SPHERE: {
+            const V3 o = ld3(x), d = ld3(x + 3);
+            const float rad = x[9] < 0.0f ? 0.0f : x[9];  // scene creation's max(r, 0)
+            const RayK rk = ray_consts(o, d);
+            sphere_ops<0>(make_float4(x[6], x[7], x[8], rad * rad), o, d, rk, x[10], r);  // book 1: r * r in w
+            sphere_ops<1>(make_float4(x[6], x[7], x[8], rad), o, d, rk, x[10], r + 6);     // book 2: r
+            r[12] = sphere_root(make_float4(x[6], x[7], x[8], rad), o, d, 0.001f) ? 1u : 0u;
+            break;
+        }
+        default: break;
+        }
+    }
+}
+
+// Test support (rrt_testing_div_check): the root division over every f32 numerator for each of the
+// n_a divisors, and div_by_const over its proved domain; the counters of include/rrt_hip.h.
+__global__ __launch_bounds__(256) void rrt_div_check(const float *__restrict__ a_values, uint32_t n_a,
+                                                     unsigned long long *out) {
+    auto same = [](float x, float y) { return __float_as_uint(x) == __float_as_uint(y) || (x != x && y != y); };
+    auto accepted = [](float t) { return 0.001f < t && t < __builtin_inff(); };
+    uint32_t c0 = 0, c1 = 0, c2 = 0, c3 = 0, c4 = 0, c5 = 0, pairs = 0, xs = 0;
+    const uint64_t first = blockIdx.x * 256ull + threadIdx.x, stride = (uint64_t)gridDim.x * 256ull;
+    for (uint32_t ai = 0; ai < n_a; ++ai) {
+        RayK rk{};
+        rk.a = a_values[ai];
+        rk.ra = refine_ra(rk.a);
+        for (uint64_t k = first; k < (1ull << 32); k += stride) {
+            const float n = __uint_as_float((uint32_t)k);
+            const float q = n / rk.a;
+            const float r = div_by_a<false>(n, rk);
+            ++pairs;
+            if (rk.ra == 0.0f) {
+                if (!same(r, q)) ++c2;
+                continue;
+            }
+            const float rf = div_by_a<true>(n, rk);
+            const float an = __builtin_fabsf(n), aq = __builtin_fabsf(q);
+            const bool differ = !same(r, q) || !same(rf, q);
+            if (an >= 0x1.0p-103f && an < __builtin_inff() && aq >= 0x1.0p-126f && aq < __builtin_inff() && differ) ++c0;
+            if (accepted(r) != accepted(q) || accepted(rf) != accepted(q) || (accepted(q) && differ)) ++c1;
+            if (aq < 0x1.0p-126f && (__float_as_uint(r) != __float_as_uint(q) || __float_as_uint(rf) != __float_as_uint(q))) ++c3;
+        }
+    }
+    // x = 0 (k = 0) and every f32 x in [2^-100, 8]
+    constexpr uint32_t kLo = 0x0d800000u, kHi = 0x41000000u;
+    for (uint64_t k = first; k <= (uint64_t)(kHi - kLo) + 1ull; k += stride) {
+        const float x = k == 0 ? 0.0f : __uint_as_float(kLo + (uint32_t)(k - 1ull));
+        ++xs;
+        if (!same(div_by_const(x, 2.0f * kPi), x / (2.0f * kPi))) ++c4;
+        if (!same(div_by_const(x, kPi), x / kPi)) ++c5;
+    }
+    const uint32_t c[8] = {c0, c1, c2, c3, c4, c5, pairs, xs};
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const uint32_t s = wave_sum_u32(c[i]);
+        if (s && __lane_id() == 0) atomicAdd(&out[i], (unsigned long long)s);
+    }
+}
 }  // namespace
 
 hipError_t launch_recip_check(unsigned long long *d_out, hipStream_t stream) {
     hipLaunchKernelGGL(rrt_recip_check, dim3(16384), dim3(256), 0, stream, d_out);
+    return hipGetLastError();
+}
+
+void device_op_columns(uint32_t op, uint32_t &cols_in, uint32_t &cols_out) {
+    switch (op) {
+    case RRT_OP_SIN: case RRT_OP_COS: case RRT_OP_LOG: case RRT_OP_ACOS: case RRT_OP_FLOOR_I32: cols_in = 1, cols_out = 1; break;
+    case RRT_OP_ATAN2: cols_in = 2, cols_out = 1; break;
+    case RRT_OP_DIV_A: cols_in = 2, cols_out = 4; break;
+    case RRT_OP_DIV_CONST: cols_in = 1, cols_out = 4; break;
+    case RRT_OP_CHECKER: cols_in = 4, cols_out = 1; break;
+    case RRT_OP_PERLIN: cols_in = 3, cols_out = 8; break;
+    case RRT_OP_VEC: cols_in = 9, cols_out = 13; break;
+    case RRT_OP_QUAD: cols_in = 9, cols_out = 2; break;
+    case RRT_OP_SPHERE: cols_in = 11, cols_out = 13; break;
+    default: cols_in = cols_out = 0; break;
+    }
+}
+
+hipError_t launch_device_ops(uint32_t op, uint32_t n, const float *d_in, uint32_t *d_out, const void *d_aux,
+                             uint32_t n_aux, float scale, hipStream_t stream) {
+    uint32_t cin = 0, cout = 0;
+    device_op_columns(op, cin, cout);
+    if (cin == 0 || n == 0) return hipErrorInvalidValue;
+    const uint32_t blocks = std::min((n + 255u) / 256u, 8192u);
+    hipLaunchKernelGGL(rrt_device_ops, dim3(blocks), dim3(256), 0, stream, op, n, cin, cout, d_in, d_out, d_aux, n_aux, scale);
+    return hipGetLastError();
+}
+
+hipError_t launch_div_check(const float *d_a, uint32_t n_a, unsigned long long *d_out, hipStream_t stream) {
+    hipLaunchKernelGGL(rrt_div_check, dim3(16384), dim3(256), 0, stream, d_a, n_a, d_out);
     return hipGetLastError();
 }
 
