@@ -678,6 +678,48 @@ int32_t rrt_testing_device_ops(uint32_t op, uint32_t n, const void *in, void *ou
  * (tests/test_gpu_device_ops.py: [0], [1], [2], [4], [5] are 0). */
 int32_t rrt_testing_div_check(const float *a_values, uint32_t n_a, uint64_t *out);
 
+/* Test support, not part of the drop-in (no reference counterpart; RRT_ABI_VERSION is unchanged and
+ * the Rust shim does not bind it): the f64 books kernel's own building blocks (rrt_books64.hip)
+ * applied elementwise on the device (tests/test_gpu_device_ops64.py compares every result bit for
+ * bit with the oracle's f64 path or with the IEEE operation). `in` holds n rows of f64 columns, `out`
+ * receives n rows of 64-bit words (f64 bits unless noted; i32 and flags zero-extended from 32 bits);
+ * host pointers, copied inside. Row i runs on lane i % 64 of wave i / 64. aux: none (pass NULL).
+ *   op           in columns                        out columns
+ *   ACOS64       x                                 rrt_acos64(x)
+ *   ATAN2_64     y, x                              rrt_atan2_64(y, x)
+ *   DIV_A64      n, a                              div_a64(n, a, ra) on ra = recip_a64(a), the IEEE n / a, ra
+ *   DIV_CONST64  x                                 div_by_const64(x, 2 pi), IEEE x / (2 pi), div_by_const64(x, pi), IEEE x / pi
+ *   SQRT64       x                                 sqrt64(x): the wave-uniform choice between sqrt64_big and the
+ *                                                  library root is taken over the 64 rows of the lane's wave
+ *   AS_I32       x                                 as_i32_rs(x) (i32)
+ *   ATT64        word, bytes                       att_decode(word) for the u32 `word` (an f32 bit pattern or a texel
+ *                                                  tag), texel_value64(bytes) 3 for bytes = r | g << 8 | b << 16 or
+ *                                                  0x1000000 (no image data); both columns hold whole numbers
+ *   VEC64        v.xyz, n.xyz, e, cosine, r0       unit_vector(v) 3, reflect(v, n) 3, refract(v, n, e) 3,
+ *                                                  reflectance_r0(cosine, r0), rr_probability64(v)
+ *   TEXEL64      outward.xyz, w, h                 the texel column i and row j of get_sphere_uv(outward) in a w x h
+ *                                                  image as the render chooses them (texel_index64), whether the
+ *                                                  column and the row were decided by the f32 enclosure (u32 0 / 1
+ *                                                  each), then i and j from the fdlibm angles alone. 1 <= w, h <= 2^30
+ *   SPHERE64     o.xyz, d.xyz, c.xyz, r, closest   (c and r f32-representable; r < 0 is taken as 0) for the f32 record
+ *                                                  (float4) and then the record widened as the LDS staging widens it
+ *                                                  (Sphere64): exact_root64, leaves64's decision over a one-sphere
+ *                                                  leaf against `closest` (hit u32, t: `closest` on a miss). 6 words.
+ * Every input, NaN and infinities included, is ordinary arithmetic. */
+enum RrtDeviceOp64 {
+    RRT_OP_ACOS64 = 0,
+    RRT_OP_ATAN2_64 = 1,
+    RRT_OP_DIV_A64 = 2,
+    RRT_OP_DIV_CONST64 = 3,
+    RRT_OP_SQRT64 = 4,
+    RRT_OP_AS_I32 = 5,
+    RRT_OP_ATT64 = 6,
+    RRT_OP_VEC64 = 7,
+    RRT_OP_TEXEL64 = 8,
+    RRT_OP_SPHERE64 = 9
+};
+int32_t rrt_testing_device_ops64(uint32_t op, uint32_t n, const void *in, void *out, const void *aux);
+
 #ifdef __cplusplus
 }
 #endif

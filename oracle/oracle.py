@@ -81,7 +81,10 @@ def load() -> ctypes.CDLL:
     for name, args in (("oracle_acos_f32", [c_uint32, P, P]), ("oracle_atan2_f32", [c_uint32, P, P]),
                        ("oracle_floor_i32", [c_uint32, P, P]), ("oracle_vec_f32", [c_uint32, P, P]),
                        ("oracle_quad_hit_f32", [c_uint32, P, c_uint32, P, P, P]),
-                       ("oracle_sphere_hit_f32", [c_uint32, P, P, P])):
+                       ("oracle_sphere_hit_f32", [c_uint32, P, P, P]),
+                       ("oracle_texel_index_f64", [c_uint32, P, P]), ("oracle_as_i32_f64", [c_uint32, P, P]),
+                       ("oracle_texel_channels_f64", [P]), ("oracle_vec_f64", [c_uint32, P, P]),
+                       ("oracle_sphere_hit_f64", [c_uint32, P, P, P])):
         getattr(lib, name).restype = None
         getattr(lib, name).argtypes = args
     _LIB = lib
@@ -375,6 +378,53 @@ def sphere_hit_f32(rows):
     r = _rows(rows, 11)
     hit, t = np.zeros((len(r), 5), np.uint32), np.zeros((len(r), 4), np.float32)
     load().oracle_sphere_hit_f32(len(r), _p(r), _p(hit), _p(t))
+    return hit, t
+
+
+def _rows64(x, cols):
+    return np.ascontiguousarray(x, dtype=np.float64).reshape(-1, cols)
+
+
+def texel_index_f64(rows):
+    """Rows (outward, width, height) -> (n, 2) int32: the texel (i, j) the books path's
+    texture_value reads at get_sphere_uv(outward) in a width x height image."""
+    r = _rows64(rows, 5)
+    out = np.zeros((len(r), 2), np.int32)
+    load().oracle_texel_index_f64(len(r), _p(r), _p(out))
+    return out
+
+
+def as_i32_f64(x):
+    """Rust's `x as i32` (saturating, NaN -> 0) at each f64 element of x."""
+    xs = _rows64(x, 1)
+    out = np.zeros(len(xs), np.int32)
+    load().oracle_as_i32_f64(len(xs), _p(xs), _p(out))
+    return out
+
+
+def texel_channels_f64():
+    """The f64 colour channel of each texel byte 0..255 as the books path's texture_value forms it."""
+    out = np.zeros(256, np.float64)
+    load().oracle_texel_channels_f64(_p(out))
+    return out
+
+
+def vec_f64(rows):
+    """Rows (v, n, e, cosine, r0) -> (n, 11): unit_vector(v), reflect(v, n), refract(v, n, e),
+    Schlick's reflectance at r0, the Russian-roulette probability of the attenuation v, in the books
+    path's f64 arithmetic."""
+    r = _rows64(rows, 9)
+    out = np.zeros((len(r), 11), np.float64)
+    load().oracle_vec_f64(len(r), _p(r), _p(out))
+    return out
+
+
+def sphere_hit_f64(rows):
+    """Rows (o, d, c, r, closest) -> hit (n, 2), t (n, 2): the books path's Sphere::hit over
+    (0.001, inf) and over (0.001, closest); t is 0 on a miss."""
+    r = _rows64(rows, 11)
+    hit, t = np.zeros((len(r), 2), np.uint32), np.zeros((len(r), 2), np.float64)
+    load().oracle_sphere_hit_f64(len(r), _p(r), _p(hit), _p(t))
     return hit, t
 
 

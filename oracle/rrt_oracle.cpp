@@ -1242,9 +1242,18 @@ bool world_hit(const World<T> &w, Vec3<T> o, Vec3<T> d, T time, uint64_t seg, Re
     return true;
 }
 
+// Rust `as i32`: saturating, NaN -> 0
+template <class T> int32_t as_i32_rs(T x) {
+    if (!(x == x)) return 0;
+    if (x <= (T)INT32_MIN) return INT32_MIN;
+    if (x >= (T)INT32_MAX) return INT32_MAX;
+    return (int32_t)x;
+}
+// get_sphere_uv (the_next_week/sphere.rs:46-52) and the texel (i, j) ImageTexture::value reads at it
+// in a width x height image (texture.rs:96-103, rtw_image.rs:51-52, 70-78). texture_value and the
+// array hook oracle_texel_index_f64 both call this.
 template <class T>
-Vec3<T> texture_value(const World<T> &w, uint32_t tex, Vec3<T> outward) {
-    // get_sphere_uv (the_next_week/sphere.rs:46-52)
+void sphere_texel(const World<T> &w, Vec3<T> outward, int32_t width, int32_t height, int32_t &i, int32_t &j) {
     T theta, phi;
     if (std::is_same_v<T, double> && w.libm_trig) {
         theta = (T)std::acos((double)-outward.y());
@@ -1255,26 +1264,30 @@ Vec3<T> texture_value(const World<T> &w, uint32_t tex, Vec3<T> outward) {
     }
     T u = phi / (T(2) * t_pi<T>());
     T v = theta / t_pi<T>();
-    const Texture &t = w.texs[tex];
-    if (t.height <= 0) return mk(T(0), T(1), T(1));  // texture.rs:91-93
     const Interval<T> unit{T(0), T(1)};
     u = unit.clamp(u);
     v = T(1) - unit.clamp(v);
-    auto to_i32 = [](T x) -> int32_t {  // Rust `as i32`: saturating, NaN -> 0
-        if (!(x == x)) return 0;
-        if (x <= (T)INT32_MIN) return INT32_MIN;
-        if (x >= (T)INT32_MAX) return INT32_MAX;
-        return (int32_t)x;
-    };
-    int32_t i = to_i32(u * (T)t.width);
-    int32_t j = to_i32(v * (T)t.height);
+    i = as_i32_rs(u * (T)width);
+    j = as_i32_rs(v * (T)height);
     auto clampi = [](int32_t x, int32_t lo, int32_t hi) { return x < lo ? lo : (x < hi ? x : hi - 1); };  // rtw_image.rs:51-52, 70-78
-    if (!t.data) return mk(T(1), T(0), T(1));  // rtw_image.rs:47-49
-    i = clampi(i, 0, t.width);
-    j = clampi(j, 0, t.height);
-    const uint8_t *px = t.data + ((size_t)j * t.width + i) * 3;
+    i = clampi(i, 0, width);
+    j = clampi(j, 0, height);
+}
+// rtw_image.rs:46-55 / texture.rs:105-108: a texel byte as a colour channel
+template <class T> T texel_channel(uint8_t b) {
     const T cs = T(1) / T(255);
-    return mk(cs * (T)px[0], cs * (T)px[1], cs * (T)px[2]);
+    return cs * (T)b;
+}
+
+template <class T>
+Vec3<T> texture_value(const World<T> &w, uint32_t tex, Vec3<T> outward) {
+    const Texture &t = w.texs[tex];
+    if (t.height <= 0) return mk(T(0), T(1), T(1));  // texture.rs:91-93
+    if (!t.data) return mk(T(1), T(0), T(1));        // rtw_image.rs:47-49
+    int32_t i, j;
+    sphere_texel(w, outward, t.width, t.height, i, j);
+    const uint8_t *px = t.data + ((size_t)j * t.width + i) * 3;
+    return mk(texel_channel<T>(px[0]), texel_channel<T>(px[1]), texel_channel<T>(px[2]));
 }
 
 // ---- book-2 procedural textures (the_next_week/texture.rs:39-77, 111-126; perlin.rs) -------
@@ -2145,6 +2158,63 @@ void oracle_sphere_hit_f32(uint32_t n, const float *in, uint32_t *hit, float *t_
         }
         T t;
         hit[5 * (size_t)i + 4] = World<T>::sphere_root(c, r, O, D, Interval<T>{T(0.001f), inf}, t) ? 1u : 0u;
+    }
+}
+
+// ---- array forms in the books path's f64 arithmetic, for the f64 kernel's elementwise checks
+// (tests/test_gpu_device_ops64.py; the row layouts are those of include/rrt_hip.h
+// rrt_testing_device_ops64). Each calls the functions the BOOKS render calls. -------------------------
+// rows (outward, width, height) -> the texel (i, j) of texture_value<double>
+void oracle_texel_index_f64(uint32_t n, const double *in, int32_t *ij) {
+    World<double> w;
+    for (uint32_t k = 0; k < n; ++k) {
+        const double *x = in + 5 * (size_t)k;
+        sphere_texel(w, mk(x[0], x[1], x[2]), (int32_t)x[3], (int32_t)x[4], ij[2 * (size_t)k], ij[2 * (size_t)k + 1]);
+    }
+}
+
+void oracle_as_i32_f64(uint32_t n, const double *x, int32_t *out) {
+    for (uint32_t i = 0; i < n; ++i) out[i] = as_i32_rs(x[i]);
+}
+
+// every byte's colour channel, 256 values
+void oracle_texel_channels_f64(double *out) {
+    for (int b = 0; b < 256; ++b) out[b] = texel_channel<double>((uint8_t)b);
+}
+
+// rows (v, n, e, cosine, r0) -> unit_vector(v), reflect(v, n), refract(v, n, e), Schlick's reflectance
+// at the given r0, the Russian-roulette probability of the attenuation v
+void oracle_vec_f64(uint32_t n, const double *in, double *out) {
+    using T = double;
+    for (uint32_t i = 0; i < n; ++i) {
+        const double *x = in + 9 * (size_t)i;
+        double *r = out + 11 * (size_t)i;
+        const Vec3<T> v = mk(x[0], x[1], x[2]), nn = mk(x[3], x[4], x[5]);
+        const Vec3<T> a = unit_vector(v), b = reflect(v, nn), c = refract(v, nn, x[6]);
+        for (int k = 0; k < 3; ++k) r[k] = a[k], r[3 + k] = b[k], r[6 + k] = c[k];
+        r[9] = schlick_at_r0<T>(x[7], x[8]);
+        r[10] = rr_probability(v);
+    }
+}
+
+// rows (o, d, c, r, closest) -> Sphere::hit of the book-1 sphere (c, max(r, 0)) over (0.001, inf) and
+// over (0.001, closest): hit 2 per row, t 2 per row (0 on a miss)
+void oracle_sphere_hit_f64(uint32_t n, const double *in, uint32_t *hit, double *t_out) {
+    using T = double;
+    const T inf = std::numeric_limits<T>::infinity();
+    World<T> w;
+    w.spheres.push_back(Sphere<T>{});
+    for (uint32_t i = 0; i < n; ++i) {
+        const double *x = in + 11 * (size_t)i;
+        const Vec3<T> O = mk(x[0], x[1], x[2]), D = mk(x[3], x[4], x[5]), c = mk(x[6], x[7], x[8]);
+        const T r = std::max(x[9], T(0));
+        w.spheres[0] = Sphere<T>{c, r, 0, from_points(c - mk(r, r, r), c + mk(r, r, r)), mk(T(0), T(0), T(0))};
+        for (int k = 0; k < 2; ++k) {
+            T t = T(0);
+            const bool h = w.hit_sphere(0, O, D, T(0), Interval<T>{T(0.001), k == 0 ? inf : x[10]}, t, nullptr);
+            hit[2 * (size_t)i + k] = h ? 1u : 0u;
+            t_out[2 * (size_t)i + k] = h ? t : T(0);
+        }
     }
 }
 

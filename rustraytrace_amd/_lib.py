@@ -86,6 +86,7 @@ EXPORTED_SYMBOLS = (
     "rrt_testing_sqrt64_check",
     "rrt_testing_device_ops",
     "rrt_testing_div_check",
+    "rrt_testing_device_ops64",
 )
 
 # == RrtDeviceOp (include/rrt_hip.h, test support): op -> (code, f32 columns in, 32-bit words out)
@@ -93,6 +94,12 @@ DEVICE_OPS = {
     "SIN": (0, 1, 1), "COS": (1, 1, 1), "LOG": (2, 1, 1), "ACOS": (3, 1, 1), "ATAN2": (4, 2, 1),
     "DIV_A": (5, 2, 4), "DIV_CONST": (6, 1, 4), "FLOOR_I32": (7, 1, 1), "CHECKER": (8, 4, 1),
     "PERLIN": (9, 3, 8), "VEC": (10, 9, 13), "QUAD": (11, 9, 2), "SPHERE": (12, 11, 13),
+}
+
+# == RrtDeviceOp64 (include/rrt_hip.h, test support): op -> (code, f64 columns in, 64-bit words out)
+DEVICE_OPS64 = {
+    "ACOS64": (0, 1, 1), "ATAN2_64": (1, 2, 1), "DIV_A64": (2, 2, 3), "DIV_CONST64": (3, 1, 4), "SQRT64": (4, 1, 1),
+    "AS_I32": (5, 1, 1), "ATT64": (6, 2, 4), "VEC64": (7, 9, 11), "TEXEL64": (8, 5, 6), "SPHERE64": (9, 11, 6),
 }
 
 
@@ -244,6 +251,18 @@ def device_ops(op: str, rows, quads=None, perlin=None, scale=0.0) -> np.ndarray:
     return out
 
 
+def device_ops64(op: str, rows) -> np.ndarray:
+    """rrt_testing_device_ops64 (test support): the f64 books kernel's building block `op` (a
+    DEVICE_OPS64 name) on each row of `rows` (float64, n x columns in); returns the n x words-out
+    results as uint64 (view as float64 where the op returns doubles). Row i runs on lane i % 64 of
+    wave i / 64."""
+    code, cin, cout = DEVICE_OPS64[op]
+    x = np.ascontiguousarray(rows, dtype=np.float64).reshape(-1, cin)
+    out = np.zeros((len(x), cout), dtype=np.uint64)
+    check(load().rrt_testing_device_ops64(code, len(x), ptr(x), ptr(out), None))
+    return out
+
+
 def div_check(a_values) -> list:
     """rrt_testing_div_check (test support): the eight counters for the divisors a_values."""
     a = np.ascontiguousarray(a_values, dtype=np.float32).ravel()
@@ -330,6 +349,7 @@ def load() -> ctypes.CDLL:
         "rrt_testing_trig32_check": (c_int32, [P]),
         "rrt_testing_sqrt64_check": (c_int32, [P]),
         "rrt_testing_device_ops": (c_int32, [c_uint32, c_uint32, P, P, P]),
+        "rrt_testing_device_ops64": (c_int32, [c_uint32, c_uint32, P, P, P]),
         "rrt_testing_div_check": (c_int32, [P, c_uint32, P]),
     }
     experiment = "RRT_LIB_PATH" in os.environ  # A/B of older builds: tolerate symbols they lack

@@ -30,6 +30,7 @@
 // scene data with RRT_FLAG_F64. Same work queue, chunked accumulation order and BVH (f32 boxes,
 // rounded outward and grown by the f32 slab bound, tested in f64: conservative) as the f32 kernel.
 #include "rrt_internal.h"
+#include "../../include/rrt_hip.h"  // RrtDeviceOp64 (the test-only rrt_device_ops64 kernel)
 
 #include <atomic>
 #include <cstdlib>
@@ -457,6 +458,17 @@ __device__ __forceinline__ bool texel_row_decided(double c, double e, int h, int
     j = (int)f;
     return true;
 }
+// The texel (column i, row j) of get_sphere_uv(outward) in a w x h image: each index from its f32
+// enclosure when that decides it (kFast), else from the fdlibm angle. col_fast / row_fast: which of the
+// two was decided by the enclosure. The render and the test-only rrt_device_ops64 both call this.
+template <bool kFast>
+__device__ __forceinline__ void texel_index64(D3 outward, int w, int h, int &i, int &j, bool &col_fast, bool &row_fast) {
+    double c = 0.0, e = 0.0;
+    col_fast = kFast && phi_enclosure64(-outward.z, outward.x, c, e) && texel_col_decided(c, e, w, i);
+    if (!col_fast) i = texel_col64(rrt_atan2_64(-outward.z, outward.x) + kPiD, w);
+    row_fast = kFast && acos_enclosure64(-outward.y, c, e) && texel_row_decided(c, e, h, j);
+    if (!row_fast) j = texel_row64(rrt_acos64(-outward.y), h);
+}
 __device__ __forceinline__ uint32_t texel_bytes64(const KParams &P, int tex, D3 outward) {
     const GTexture t = P.texs[tex];
     if (t.height <= 0) return 0x1000000u;  // texture.rs:91-93: (0, 1, 1)
@@ -465,11 +477,8 @@ __device__ __forceinline__ uint32_t texel_bytes64(const KParams &P, int tex, D3 
         i = texel_col64(2.0 + outward.x * 0x1.0p-60, t.width);
         j = texel_row64(1.0 + outward.y * 0x1.0p-60, t.height);
     } else {
-        double c = 0.0, e = 0.0;
-        if (!(RRT_F64_TEXEL_FAST && phi_enclosure64(-outward.z, outward.x, c, e) && texel_col_decided(c, e, t.width, i)))
-            i = texel_col64(rrt_atan2_64(-outward.z, outward.x) + kPiD, t.width);
-        if (!(RRT_F64_TEXEL_FAST && acos_enclosure64(-outward.y, c, e) && texel_row_decided(c, e, t.height, j)))
-            j = texel_row64(rrt_acos64(-outward.y), t.height);
+        bool col_fast, row_fast;
+        texel_index64<RRT_F64_TEXEL_FAST != 0>(outward, t.width, t.height, i, j, col_fast, row_fast);
     }
     const uint8_t *px = P.tex_pool + t.offset + ((size_t)j * t.width + i) * 3;
     return (uint32_t)px[0] | ((uint32_t)px[1] << 8) | ((uint32_t)px[2] << 16);
@@ -732,10 +741,58 @@ __device__ __forceinline__ double recip_a64(double a) {
     e = __builtin_fma(-a, r, 1.0);
     return __builtin_fma(r, e, r);
 }
-__device__ __forceinline__ double div_a64(double n, double a, double ra) {
-    if (!RRT_F64_DIVA || ra == 0.0) return n / a;
+// Two ends are not the expansion's: a quotient that rounds to the largest finite double can have
+// n * ra = inf (ra rounded up), which the correction turns into NaN where IEEE accepts 1.8e308; and the
+// remainder n - a q is exact only while the last bit of a q, 2^(e_a + e_q - 104), is a double: for
+// a >= 2^-64 that holds from |q| >= 2^-906 on (below it the remainder loses bits to underflow, and a
+// subnormal q has lost its own). So a quotient outside the band [2^-896, inf] takes the IEEE division
+// instead: a branch no ray of a sane scene takes. The band is tested on the corrected quotient r, one
+// comparison that a NaN fails: r is within 2^-51 |q| + 2^-1011 of the first quotient q (the remainder is
+// below 2^-52 |n|, its underflow error below 2^-1075, ra <= 2^64), so |r| >= 2^-896 leaves q ten binades
+// above 2^-906; q = +-inf gives r = NaN (inf - inf); and ra = 0 (a outside the range) gives q = r = +-0,
+// or NaN for an infinite n, so the band covers the out-of-range rays as well and no test of ra is left.
+// r = +-inf from a finite q is the IEEE result (the fma rounds once, overflow included). With the band
+// div_a64 is the IEEE quotient for every n, bit for bit (tests/test_gpu_device_ops64.py, DIV_A64;
+// without it the largest finite quotients came out NaN: accepted roots rejected).
+// RRT_F64_DIVA_GUARD=0: the code before the band (ra == 0 alone takes the division).
+#ifndef RRT_F64_DIVA_GUARD
+#define RRT_F64_DIVA_GUARD 1
+#endif
+__device__ __forceinline__ double div_a64_short(double n, double a, double ra) {
     const double q = n * ra;
     return __builtin_fma(__builtin_fma(-a, q, n), ra, q);
+}
+__device__ __forceinline__ bool div_a64_in_band(double r, double ra) {
+    return RRT_F64_DIVA_GUARD ? __builtin_fabs(r) >= 0x1.0p-896 : ra != 0.0;
+}
+__device__ __forceinline__ double div_a64(double n, double a, double ra) {
+    if (!RRT_F64_DIVA) return n / a;
+    const double r = div_a64_short(n, a, ra);
+    return div_a64_in_band(r, ra) ? r : n / a;
+}
+// The root Sphere::hit tries over (0.001, closest): the near root (h - sq) / a if above 0.001, else the
+// far one. Both from the short division with one band test, on the root chosen: a near root above 0.001
+// is inside the band, hence the IEEE quotient; one at or below 0.001 was rightly passed over when it is
+// inside the band (it is the IEEE quotient), tiny or zero (so is the IEEE one) or NaN from n * ra = -inf
+// (the IEEE one is negative); and when it is NaN from n * ra = +inf, or zero from ra = 0, the far root's
+// n * ra, no smaller, gives NaN or zero as well: the chosen root fails the band and both are formed
+// again by the IEEE division (as they are for a NaN numerator). So the root, and the
+// choice between the two, are those of div_a64 applied to each (SPHERE64 in tests/test_gpu_device_ops64.py)
+// at one comparison per sphere test instead of one per division (same-box against a band test in each
+// division: C2 -2.5 % instead of -6.8 % against the code without the band).
+__device__ __forceinline__ double root64(double h, double sq, double a, double ra) {
+    const double n1 = h - sq, n2 = h + sq;
+    if (!RRT_F64_DIVA) {
+        const double root = n1 / a;
+        return 0.001 < root ? root : n2 / a;
+    }
+    double root = div_a64_short(n1, a, ra);
+    if (!(0.001 < root)) root = div_a64_short(n2, a, ra);
+    if (!div_a64_in_band(root, ra)) {
+        root = n1 / a;
+        if (!(0.001 < root)) root = n2 / a;
+    }
+    return root;
 }
 
 // A sphere record widened to f64 while the block stages the scene in LDS (kF64LdsWide): center and
@@ -748,6 +805,10 @@ __device__ __forceinline__ double div_a64(double n, double a, double ra) {
 struct alignas(16) Sphere64 {
     double cx, cy, cz, r2;  // r2 = r * r (RRT_F64_R2) or r
 };
+// the widening of an f32 record (center, r): the staging loop's, and the test-only rrt_device_ops64's
+__device__ __forceinline__ Sphere64 widen_sphere64(const float4 &c) {
+    return Sphere64{(double)c.x, (double)c.y, (double)c.z, RRT_F64_R2 ? (double)c.w * (double)c.w : (double)c.w};
+}
 __device__ __forceinline__ D3 center_of(const float4 &c) { return f2d(c.x, c.y, c.z); }
 __device__ __forceinline__ D3 center_of(const Sphere64 &c) { return d3(c.cx, c.cy, c.cz); }
 __device__ __forceinline__ double radius_of(const float4 &c) { return (double)c.w; }
@@ -791,10 +852,7 @@ __device__ __forceinline__ double exact_root64(const Rec *__restrict__ prims, in
     const double h = dot(d, oc);
     const double c = dot(oc, oc) - radius_sq_of(cr);
     const double disc = h * h - a * c;
-    const double sq = sqrt64(disc);
-    double root = div_a64(h - sq, a, ra);
-    if (!(0.001 < root)) root = div_a64(h + sq, a, ra);
-    return root;
+    return root64(h, sqrt64(disc), a, ra);
 }
 template <typename Rec>
 __device__ __forceinline__ void lazy_resolve64(const Rec *__restrict__ prims, int i, D3 o, D3 d, double a, double ra,
@@ -867,9 +925,7 @@ __device__ __forceinline__ void leaves64(const Rec *__restrict__ prims, const fl
             t.hit_prim = acc ? i : t.hit_prim;
             if (!(acc | rej)) lazy_resolve64(prims, i, o, d, a, ra, t);
         } else {
-            const double sq = sqrt64(disc);
-            double root = div_a64(h - sq, a, ra);
-            if (!(0.001 < root)) root = div_a64(h + sq, a, ra);
+            const double root = root64(h, sqrt64(disc), a, ra);
             if (0.001 < root && root < t.closest) {
                 if (RRT_F64_STATS == 3) cnt.d2++;
                 t.closest = root;
@@ -1138,8 +1194,7 @@ __device__ __forceinline__ void render64_body(const KParams &P) {
         for (uint32_t i = threadIdx.x; i < P.n_prims; i += kBlk) {
             const float4 c = P.prim_cr[i];
             if constexpr (kMode == kF64LdsWide)
-                reinterpret_cast<Sphere64 *>(dst + nn)[i] = Sphere64{(double)c.x, (double)c.y, (double)c.z,
-                                                                         RRT_F64_R2 ? (double)c.w * (double)c.w : (double)c.w};
+                reinterpret_cast<Sphere64 *>(dst + nn)[i] = widen_sphere64(c);
             else
                 reinterpret_cast<float4 *>(dst + nn)[i] = c;
         }
@@ -1485,8 +1540,6 @@ __global__ __launch_bounds__(256) void rrt_accum64_to_f32(const D4 *__restrict__
     a32[p] = make_float4((float)v.x, (float)v.y, (float)v.z, (float)v.w);
 }
 
-// LDS of the f64 kernel's block in each mode (stack, then the staged scene; the 1/r table when
-// p.inv_r_in_lds)
 // Test support (rrt_testing_trig32_check): the largest |acosf(x) - acos(x)| over every f32 x in
 // [-1, 1] and |atanf(t) - atan(t)| over every f32 t in [0, 1], against the device's f64 functions,
 // as f64 bit patterns (non-negative doubles order as their bits) in out[0], out[1].
@@ -1546,6 +1599,101 @@ __global__ __launch_bounds__(256) void rrt_sqrt64_check(unsigned long long *out)
     atomicAdd(&out[1], (unsigned long long)n);
 }
 
+// Test support (rrt_testing_device_ops64): one of this kernel's own f64 building blocks applied to the
+// rows of `in` (f64 columns), results as 64-bit words in the rows of `out` (columns per op:
+// include/rrt_hip.h RrtDeviceOp64, device_op64_columns). The functions themselves, in this translation
+// unit, with the f64 kernel's flags. Row i runs on thread i of the grid, so rows map to lanes in order
+// (SQRT64's wave-uniform choice sees 64 consecutive rows).
+__device__ __forceinline__ D3 ld3(const double *p) { return d3(p[0], p[1], p[2]); }
+__device__ __forceinline__ uint64_t bits64(double x) { return (uint64_t)__double_as_longlong(x); }
+__device__ __forceinline__ void st3(uint64_t *p, D3 v) {
+    p[0] = bits64(v.x);
+    p[1] = bits64(v.y);
+    p[2] = bits64(v.z);
+}
+// one sphere as a one-record leaf: exact_root64, and leaves64's decision against `closest`
+template <typename Rec>
+__device__ __forceinline__ void sphere_ops64(const Rec &rec, const float4 &rec32, D3 o, D3 d, double closest, uint64_t *r) {
+    const double a = dot(d, d);
+    r[0] = bits64(exact_root64(&rec, 0, o, d, a, RRT_F64_DIVA ? recip_a64(a) : 0.0));
+    Trav64 t;
+    t.closest = t.lo = closest;
+    t.closest32 = (float)closest;
+    t.hit_prim = -1;
+    t.node = -1;
+    t.sp = 0;
+    Counters cnt = {0, 0, 0, 0, 0, 0};
+    leaves64<false>(&rec, &rec32, (Leaves)(1u << kLinkCountShift), o, d, a, RaySphere32{}, false, t, cnt);
+    if (RRT_F64_LAZY) lazy_finish64(&rec, o, d, t);
+    r[1] = t.hit_prim == 0 ? 1u : 0u;
+    r[2] = bits64(t.closest);
+}
+__global__ __launch_bounds__(256) void rrt_device_ops64(uint32_t op, uint32_t n, uint32_t cin, uint32_t cout,
+                                                        const double *__restrict__ in, uint64_t *__restrict__ out) {
+    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n; i += gridDim.x * 256u) {
+        const double *x = in + (size_t)i * cin;
+        uint64_t *r = out + (size_t)i * cout;
+        switch (op) {
+        case RRT_OP_ACOS64: r[0] = bits64(rrt_acos64(x[0])); break;
+        case RRT_OP_ATAN2_64: r[0] = bits64(rrt_atan2_64(x[0], x[1])); break;
+        case RRT_OP_DIV_A64: {
+            const double ra = recip_a64(x[1]);
+            r[0] = bits64(div_a64(x[0], x[1], ra));
+            r[1] = bits64(x[0] / x[1]);
+            r[2] = bits64(ra);
+            break;
+        }
+        case RRT_OP_DIV_CONST64:
+            r[0] = bits64(div_by_const64(x[0], 2.0 * kPiD));
+            r[1] = bits64(x[0] / (2.0 * kPiD));
+            r[2] = bits64(div_by_const64(x[0], kPiD));
+            r[3] = bits64(x[0] / kPiD);
+            break;
+        case RRT_OP_SQRT64: r[0] = bits64(sqrt64(x[0])); break;
+        case RRT_OP_AS_I32: r[0] = (uint64_t)(uint32_t)as_i32_rs(x[0]); break;
+        case RRT_OP_ATT64: {
+            r[0] = bits64(att_decode((uint32_t)x[0]));
+            st3(r + 1, texel_value64((uint32_t)x[1]));
+            break;
+        }
+        case RRT_OP_VEC64: {
+            const D3 v = ld3(x), nn = ld3(x + 3);
+            st3(r, unit_vector(v));
+            st3(r + 3, reflect(v, nn));
+            st3(r + 6, refract(v, nn, x[6]));
+            r[9] = bits64(reflectance_r0(x[7], x[8]));
+            r[10] = bits64(rr_probability64(v));
+            break;
+        }
+        case RRT_OP_TEXEL64: {
+            const int w = (int)x[3], h = (int)x[4];
+            int ti = 0, tj = 0;
+            bool cf = false, rf = false;
+            texel_index64<RRT_F64_TEXEL_FAST != 0>(ld3(x), w, h, ti, tj, cf, rf);
+            r[0] = (uint64_t)(uint32_t)ti;
+            r[1] = (uint64_t)(uint32_t)tj;
+            r[2] = cf ? 1u : 0u;
+            r[3] = rf ? 1u : 0u;
+            texel_index64<false>(ld3(x), w, h, ti, tj, cf, rf);
+            r[4] = (uint64_t)(uint32_t)ti;
+            r[5] = (uint64_t)(uint32_t)tj;
+            break;
+        }
+        case RRT_OP_SPHERE64: {
+            const D3 o = ld3(x), d = ld3(x + 3);
+            const float rad = (float)x[9] < 0.0f ? 0.0f : (float)x[9];  // scene creation's max(r, 0)
+            const float4 rec = make_float4((float)x[6], (float)x[7], (float)x[8], rad);
+            sphere_ops64(rec, rec, o, d, x[10], r);
+            sphere_ops64(widen_sphere64(rec), rec, o, d, x[10], r + 3);
+            break;
+        }
+        default: break;
+        }
+    }
+}
+
+// LDS of the f64 kernel's block in each mode (stack, then the staged scene; the 1/r table when
+// p.inv_r_in_lds)
 size_t lds64_bytes(const KParams &p, int mode, int blk = kBlock64) {
     size_t lds = ((size_t)p.stack_depth * blk * sizeof(uint16_t) + 15u) / 16u * 16u;
     lds += (size_t)RRT_F64_LDS_HIST * blk * sizeof(HRec);  // the history ring
@@ -1723,6 +1871,29 @@ hipError_t launch_trig32_check(unsigned long long *d_out, double *bounds, hipStr
     bounds[0] = kAcos32Err;
     bounds[1] = kAtan32Err;
     hipLaunchKernelGGL(rrt_trig32_check, dim3(4096), dim3(256), 0, stream, d_out);
+    return hipGetLastError();
+}
+
+void device_op64_columns(uint32_t op, uint32_t &cols_in, uint32_t &cols_out) {
+    switch (op) {
+    case RRT_OP_ACOS64: case RRT_OP_SQRT64: case RRT_OP_AS_I32: cols_in = 1, cols_out = 1; break;
+    case RRT_OP_ATAN2_64: cols_in = 2, cols_out = 1; break;
+    case RRT_OP_DIV_A64: cols_in = 2, cols_out = 3; break;
+    case RRT_OP_DIV_CONST64: cols_in = 1, cols_out = 4; break;
+    case RRT_OP_ATT64: cols_in = 2, cols_out = 4; break;
+    case RRT_OP_VEC64: cols_in = 9, cols_out = 11; break;
+    case RRT_OP_TEXEL64: cols_in = 5, cols_out = 6; break;
+    case RRT_OP_SPHERE64: cols_in = 11, cols_out = 6; break;
+    default: cols_in = cols_out = 0; break;
+    }
+}
+
+hipError_t launch_device_ops64(uint32_t op, uint32_t n, const double *d_in, uint64_t *d_out, hipStream_t stream) {
+    uint32_t cin = 0, cout = 0;
+    device_op64_columns(op, cin, cout);
+    if (cin == 0 || n == 0) return hipErrorInvalidValue;
+    // one thread per row (a whole number of 256-thread blocks): row i is lane i % 64 of wave i / 64
+    hipLaunchKernelGGL(rrt_device_ops64, dim3((n + 255u) / 256u), dim3(256), 0, stream, op, n, cin, cout, d_in, d_out);
     return hipGetLastError();
 }
 

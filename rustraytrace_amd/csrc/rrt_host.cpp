@@ -1970,6 +1970,42 @@ extern "C" int32_t rrt_testing_device_ops(uint32_t op, uint32_t n, const void *i
     return RRT_OK;
 }
 
+// Test support (rrt_testing_device_ops64): rows of f64 in, rows of 64-bit words out. The integer
+// columns (ATT64's word and bytes, TEXEL64's image size) are checked here, so the kernel converts
+// only values in range.
+extern "C" int32_t rrt_testing_device_ops64(uint32_t op, uint32_t n, const void *in, void *out, const void *aux) {
+    (void)aux;  // no op takes auxiliary records yet
+    uint32_t cin = 0, cout = 0;
+    rrt::device_op64_columns(op, cin, cout);
+    if (cin == 0) return fail(RRT_E_INVALID, "rrt_testing_device_ops64: unknown op " + std::to_string(op));
+    if (n == 0) return RRT_OK;
+    if (!in || !out) return fail(RRT_E_INVALID, "rrt_testing_device_ops64: null in or out");
+    if ((uint64_t)n * std::max(cin, cout) >= (1ull << 28)) return fail(RRT_E_INVALID, "rrt_testing_device_ops64: too many rows");
+    const double *rows = static_cast<const double *>(in);
+    auto whole = [](double v, double lo, double hi) { return v >= lo && v <= hi && v == std::floor(v); };
+    for (uint32_t i = 0; i < n; ++i) {
+        const double *x = rows + (size_t)i * cin;
+        if (op == RRT_OP_ATT64 && !(whole(x[0], 0.0, 4294967295.0) && whole(x[1], 0.0, 16777216.0)))
+            return fail(RRT_E_INVALID, "rrt_testing_device_ops64: ATT64 takes a u32 word and bytes <= 0x1000000");
+        if (op == RRT_OP_TEXEL64 && !(whole(x[3], 1.0, 1073741824.0) && whole(x[4], 1.0, 1073741824.0)))
+            return fail(RRT_E_INVALID, "rrt_testing_device_ops64: TEXEL64 image size outside [1, 2^30]");
+    }
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count < 1) return fail(RRT_E_NODEV, "no HIP device");
+    const size_t in_bytes = (size_t)n * cin * 8u, out_bytes = (size_t)n * cout * 8u;
+    void *d_in = nullptr, *d_out = nullptr;
+    hipError_t e = hipMalloc(&d_in, in_bytes);
+    if (e == hipSuccess) e = hipMalloc(&d_out, out_bytes);
+    if (e == hipSuccess) e = hipMemcpy(d_in, in, in_bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(d_out, 0, out_bytes);
+    if (e == hipSuccess) e = rrt::launch_device_ops64(op, n, static_cast<const double *>(d_in), static_cast<uint64_t *>(d_out), nullptr);
+    if (e == hipSuccess) e = hipMemcpy(out, d_out, out_bytes, hipMemcpyDeviceToHost);
+    (void)hipFree(d_in);
+    (void)hipFree(d_out);
+    if (e != hipSuccess) return fail(RRT_E_HIP, std::string("rrt_testing_device_ops64: ") + hipGetErrorString(e));
+    return RRT_OK;
+}
+
 extern "C" int32_t rrt_testing_div_check(const float *a_values, uint32_t n_a, uint64_t *out) {
     if (!a_values || !out) return fail(RRT_E_INVALID, "null a_values or out");
     if (n_a == 0 || n_a > 48u) return fail(RRT_E_INVALID, "rrt_testing_div_check: 1 to 48 divisors");

@@ -371,6 +371,11 @@ hipError_t launch_div_check(const float *d_a, uint32_t n_a, unsigned long long *
 // bits), and the error bounds the f64 kernel's texel enclosures assume (bounds[2])
 hipError_t launch_trig32_check(unsigned long long *d_out, double *bounds, hipStream_t stream);
 hipError_t launch_sqrt64_check(unsigned long long *d_out, hipStream_t stream);
+// Test support (rrt_testing_device_ops64, rrt_books64.hip): the f64 kernel's own building blocks applied
+// elementwise. device_op64_columns: the f64 columns per row of `in` and the 64-bit words per row of
+// `out` for an RrtDeviceOp64 (0, 0: no such op).
+void device_op64_columns(uint32_t op, uint32_t &cols_in, uint32_t &cols_out);
+hipError_t launch_device_ops64(uint32_t op, uint32_t n, const double *d_in, uint64_t *d_out, hipStream_t stream);
 // Implemented in rrt_books64.hip: one sample pass of the f64 books kernel (+ its chunk combine)
 // into p.accum64, and the f64 sums rounded to the f32 RGBA accum of the ABI.
 hipError_t launch_render_pass_f64(const KParams &p, bool count, hipStream_t stream);
