@@ -540,6 +540,34 @@ int32_t rrt_hip_render_rgb8_ex(const RrtCamera *cam,
 int32_t rrt_quantize_accum_async(uint32_t n_pixels, const float *d_accum, uint32_t samples_per_pixel,
                                  uint8_t *d_rgb8, void *stream);
 
+/* ---- the same output step for the books path (color.rs:6-32 on the device) ----------------
+ * The RRT_FLAG_F64 kernel's f64 sums are 32 B/pixel; these entries quantise them where they are
+ * and move 3 B/pixel. */
+
+/* Enqueue the books path's quantiser (rrt_quantize_accum_books) on `stream` (hipStream_t, NULL =
+ * default): d_accum = n_pixels float4 on the device (RGB sums; w is not read), d_rgb8 = n_pixels*3
+ * bytes on the device (4-byte aligned, as hipMalloc returns it), scale 1.0 / samples_per_pixel in
+ * f64. Asynchronous; byte-identical to rrt_quantize_accum_books. samples_per_pixel = 0 or a null
+ * pointer with n_pixels > 0: RRT_E_INVALID; n_pixels = 0 enqueues nothing. */
+int32_t rrt_quantize_accum_books_async(uint32_t n_pixels, const float *d_accum, uint32_t samples_per_pixel,
+                                       uint8_t *d_rgb8, void *stream);
+/* The same over f64 sums: d_accum = n_pixels x 4 doubles (rrt_render_tile_f64_async's rows).
+ * Byte-identical to rrt_quantize_accum_books_f64. */
+int32_t rrt_quantize_accum_books_f64_async(uint32_t n_pixels, const double *d_accum, uint32_t samples_per_pixel,
+                                           uint8_t *d_rgb8, void *stream);
+
+/* rrt_hip_render_f64 (RRT_FLAG_F64 is implied; book-1 scenes), then the books path's quantiser on
+ * each device: rgb8_out[3*W*H] holds the bytes camera.rs:87-94 prints through color.rs — identical
+ * to rrt_quantize_accum_books_f64 of rrt_hip_render_f64's accum_out with samples_per_pixel =
+ * total_spp. Format them with rrt_format_pnm_from_rgb8. There is no _ex form: the f64 kernel takes
+ * no RrtSceneExt. */
+int32_t rrt_hip_render_f64_rgb8(const RrtCamera *cam,
+                                const RrtSphere *spheres, uint32_t n_spheres,
+                                const RrtMaterial *materials, uint32_t n_materials,
+                                const RrtTexture *textures, uint32_t n_textures,
+                                uint32_t total_spp, uint32_t n_gpus, uint32_t flags,
+                                uint8_t *rgb8_out);
+
 /* PNM from quantised pixels: binary = 0 -> P3 text byte-identical to
  * rrt_format_ppm_from_accum of the same image; binary = 1 -> P6 ("P6\nW H\n255\n" + rgb8).
  * *written = bytes needed (call with cap 0 to size). */

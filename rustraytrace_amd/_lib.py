@@ -78,6 +78,9 @@ EXPORTED_SYMBOLS = (
     "rrt_hip_render_f64",
     "rrt_render_tile_f64_async",
     "rrt_quantize_accum_books_f64",
+    "rrt_quantize_accum_books_async",
+    "rrt_quantize_accum_books_f64_async",
+    "rrt_hip_render_f64_rgb8",
     "rrt_testing_device_wrap",
     "rrt_testing_f64_layout",
     "rrt_testing_launch_plan",
@@ -342,6 +345,10 @@ def load() -> ctypes.CDLL:
         "rrt_hip_render_f64": (c_int32, [P, P, c_uint32, P, c_uint32, P, c_uint32, c_uint32, c_uint32, c_uint32, P]),
         "rrt_render_tile_f64_async": (c_int32, [P, P, P, P]),
         "rrt_quantize_accum_books_f64": (c_int32, [c_uint32, c_uint32, P, c_uint32, P]),
+        "rrt_quantize_accum_books_async": (c_int32, [c_uint32, P, c_uint32, P, P]),
+        "rrt_quantize_accum_books_f64_async": (c_int32, [c_uint32, P, c_uint32, P, P]),
+        "rrt_hip_render_f64_rgb8": (c_int32, [P, P, c_uint32, P, c_uint32, P, c_uint32, c_uint32, c_uint32, c_uint32,
+                                              P]),
         "rrt_testing_device_wrap": (None, [c_int32]),
         "rrt_testing_f64_layout": (None, [c_int32]),
         "rrt_testing_launch_plan": (c_int32, [P, P]),

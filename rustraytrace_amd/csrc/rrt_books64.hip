@@ -1540,6 +1540,69 @@ __global__ __launch_bounds__(256) void rrt_accum64_to_f32(const D4 *__restrict__
     a32[p] = make_float4((float)v.x, (float)v.y, (float)v.z, (float)v.w);
 }
 
+// color.rs:6-32 write_color on the device, the books path's quantiser: the host's books_channel
+// (rrt_host.cpp) operation for operation, so the bytes are identical. x = scale * sum in f64 (scale =
+// 1 / spp formed on the host), the IEEE square root of a positive x (the compiler's own expansion,
+// correctly rounded over the whole range, subnormals included: sqrt64's shortcut is not), else 0; the
+// Interval(0, 0.999) clamp as its two comparisons, which a NaN passes; 256 * x `as i32`, a NaN
+// tested for and mapped to 0 as Rust's cast does.
+__device__ __forceinline__ uint32_t books_channel(double sum, double scale) {
+    double x = scale * sum;
+    x = x > 0.0 ? __builtin_sqrt(x) : 0.0;
+    if (x < 0.0) x = 0.0;
+    if (x > 0.999) x = 0.999;
+    const double v = 256.0 * x;
+    return v != v ? 0u : (uint32_t)(int32_t)v & 0xffu;
+}
+
+// A pixel's RGB sums out of its 4-element record (T = double: D4, 32 B; float: float4): x, y as one
+// load of two elements (16 B of a D4, the widest a lane issues), z as one element; w is not read.
+template <class T>
+struct Pair;
+template <>
+struct Pair<double> {
+    using type = double2;
+};
+template <>
+struct Pair<float> {
+    using type = float2;
+};
+template <class T>
+__device__ __forceinline__ void books_pixel(const T *__restrict__ accum, size_t p, double scale, uint32_t *b) {
+    const typename Pair<T>::type xy = *reinterpret_cast<const typename Pair<T>::type *>(accum + 4u * p);
+    const T z = accum[4u * p + 2u];
+    b[0] = books_channel((double)xy.x, scale);
+    b[1] = books_channel((double)xy.y, scale);
+    b[2] = books_channel((double)z, scale);
+}
+
+// One thread per group of 4 pixels, as rrt_quantize (rrt_kernel.hip): the 12 bytes of a whole group
+// as 3 dwords (the group's first byte is at 12 * q: dword aligned), a ragged last group byte by
+// byte, so nothing past 3 * n_pixels is written.
+template <class T>
+__global__ __launch_bounds__(256) void rrt_quantize_books(const T *__restrict__ accum, uint8_t *__restrict__ rgb8,
+                                                           uint32_t n_pixels, double scale) {
+    const size_t p0 = ((size_t)blockIdx.x * 256u + threadIdx.x) * 4u;
+    if (p0 >= n_pixels) return;
+    if (p0 + 4u <= n_pixels) {
+        uint32_t b[12];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) books_pixel(accum, p0 + k, scale, b + 3 * k);
+        uint32_t *dst = reinterpret_cast<uint32_t *>(rgb8 + p0 * 3u);
+#pragma unroll
+        for (int w = 0; w < 3; ++w)
+            dst[w] = b[4 * w] | (b[4 * w + 1] << 8) | (b[4 * w + 2] << 16) | (b[4 * w + 3] << 24);
+    } else {
+        for (size_t p = p0; p < n_pixels; ++p) {
+            uint32_t b[3];
+            books_pixel(accum, p, scale, b);
+            rgb8[p * 3u + 0] = (uint8_t)b[0];
+            rgb8[p * 3u + 1] = (uint8_t)b[1];
+            rgb8[p * 3u + 2] = (uint8_t)b[2];
+        }
+    }
+}
+
 // Test support (rrt_testing_trig32_check): the largest |acosf(x) - acos(x)| over every f32 x in
 // [-1, 1] and |atanf(t) - atan(t)| over every f32 t in [0, 1], against the device's f64 functions,
 // as f64 bit patterns (non-negative doubles order as their bits) in out[0], out[1].
@@ -1934,6 +1997,27 @@ hipError_t launch_accum64_to_f32(const D4 *d_accum64, float4 *d_accum, uint32_t 
     hipLaunchKernelGGL(rrt_accum64_to_f32, dim3((n_pixels + 255) / 256), dim3(256), 0, stream, d_accum64, d_accum,
                        n_pixels);
     return hipGetLastError();
+}
+
+namespace {
+template <class T>
+hipError_t launch_books(const T *d_accum, uint8_t *d_rgb8, uint32_t n_pixels, double scale, hipStream_t stream) {
+    if (n_pixels == 0) return hipSuccess;
+    const uint32_t groups = n_pixels / 4u + (n_pixels % 4u ? 1u : 0u);
+    hipLaunchKernelGGL(rrt_quantize_books<T>, dim3((groups + 255u) / 256u), dim3(256), 0, stream, d_accum, d_rgb8,
+                       n_pixels, scale);
+    return hipGetLastError();
+}
+}  // namespace
+
+hipError_t launch_quantize_books(const float *d_accum, uint8_t *d_rgb8, uint32_t n_pixels, double scale,
+                                 hipStream_t stream) {
+    return launch_books(d_accum, d_rgb8, n_pixels, scale, stream);
+}
+
+hipError_t launch_quantize_books_f64(const double *d_accum, uint8_t *d_rgb8, uint32_t n_pixels, double scale,
+                                     hipStream_t stream) {
+    return launch_books(d_accum, d_rgb8, n_pixels, scale, stream);
 }
 
 }  // namespace rrt

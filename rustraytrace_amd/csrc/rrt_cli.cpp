@@ -100,9 +100,12 @@ static void usage() {
                  "Usage: rrt [--backend hip|cuda|gpu] <book> [scene] [--image_width N] [--samples_per_pixel N]\n"
                  "           [--max_depth N] [--aspect_ratio X] [--vfov X] [--lookfrom x,y,z] [--lookat x,y,z]\n"
                  "           [--vup x,y,z] [--defocus_angle X] [--focus_dist X] [--background r,g,b]\n"
-                 "           [--gpus N] [--seed S] [--grid_half G] [--p6] [--host-quantise] [-o out.ppm]\n"
+                 "           [--gpus N] [--seed S] [--grid_half G] [--p6] [--host-quantise] [--books-f64] [-o out.ppm]\n"
                  "  --p6             binary P6 instead of render_io.rs's P3 text\n"
                  "  --host-quantise  copy the float accum and quantise on the host (same bytes)\n"
+                 "  --books-f64      the f64 books kernel (RRT_FLAG_F64, in_one_weekend) and the books path's own\n"
+                 "                   quantiser (color.rs) on the device: the P3 camera.rs prints; with\n"
+                 "                   --host-quantise the f64 sums are copied and quantised on the host (same bytes)\n"
                  "books: in_one_weekend, the_next_week [1-9, other = final_scene(400, 250, 4)], "
                  "the_rest_of_your_life\n");
 }
@@ -140,7 +143,7 @@ int main(int argc, char **argv) {
     uint64_t seed = 0x5EED1234ull;
     int grid_half = 11;
     std::string out = "-";
-    bool p6 = false, host_quantise = false, seed_set = false;
+    bool p6 = false, host_quantise = false, seed_set = false, books_f64 = false;
 
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
@@ -172,6 +175,7 @@ int main(int argc, char **argv) {
         else if (a == "-o") out = next("-o");
         else if (a == "--p6") p6 = true;
         else if (a == "--host-quantise") host_quantise = true;
+        else if (a == "--books-f64") books_f64 = true;
         else if (a == "-h" || a == "--help") { usage(); return 0; }
         else positional.push_back(a);
     }
@@ -287,7 +291,27 @@ int main(int argc, char **argv) {
     std::vector<float> accum;
     std::vector<uint8_t> rgb8;
     int rc;
-    if (host_quantise && !p6) {  // float accum -> render_io on the host (rrt_hip_render_ex)
+    if (books_f64) {  // the f64 books kernel and color.rs's quantiser: the books path's own PPM
+        const RrtTexture *tex = n_tex ? &earth : nullptr;
+        rc = RRT_OK;
+        if (!book1) {  // book-2/3 data: the library's refusal (the f64 one-shot entries take no RrtSceneExt)
+            RrtScene *refused = nullptr;
+            rc = rrt_scene_create_ex(&cam, spheres.data(), n, materials.data(), n_mat, tex, n_tex, &ext,
+                                     flags | RRT_FLAG_F64, 0, &refused);
+            if (!rc) rrt_scene_destroy(refused);
+        }
+        rgb8.resize((size_t)w * h * 3);
+        if (rc) {  // refused: reported below like every failed render
+        } else if (host_quantise) {  // 32 B/pixel of f64 sums to the host, write_color there
+            std::vector<double> accum64((size_t)w * h * 4);
+            rc = rrt_hip_render_f64(&cam, spheres.data(), n, materials.data(), n_mat, tex, n_tex, spp, gpus, flags,
+                                    accum64.data());
+            if (!rc) rc = rrt_quantize_accum_books_f64(w, h, accum64.data(), spp, rgb8.data());
+        } else {  // quantised on the device, 3 B/pixel to the host
+            rc = rrt_hip_render_f64_rgb8(&cam, spheres.data(), n, materials.data(), n_mat, tex, n_tex, spp, gpus, flags,
+                                         rgb8.data());
+        }
+    } else if (host_quantise && !p6) {  // float accum -> render_io on the host (rrt_hip_render_ex)
         accum.resize((size_t)w * h * 4);
         rc = rrt_hip_render_ex(&cam, spheres.data(), n, materials.data(), n_mat, n_tex ? &earth : nullptr, n_tex, &ext,
                                spp, gpus, flags, accum.data());

@@ -2027,14 +2027,17 @@ extern "C" int32_t rrt_testing_div_check(const float *a_values, uint32_t n_a, ui
 static bool device_wrap() { return g_device_wrap.load(); }
 
 // One-shot frame on n_gpus devices: float accum rows (accum_out), f64 accum rows (accum64_out, the
-// RRT_FLAG_F64 kernel) or render_io-quantised rows (rgb8_out, quantised on the device) assembled
-// into the caller's image.
+// RRT_FLAG_F64 kernel) or quantised rows (rgb8_out, quantised on the device: the float accum by the
+// render_io quantiser, or with books_rgb8 the RRT_FLAG_F64 kernel's f64 sums by the books path's
+// own, color.rs) assembled into the caller's image.
 static int32_t render_frame(const RrtCamera *cam, const RrtSphere *spheres, uint32_t n_spheres,
                             const RrtMaterial *materials, uint32_t n_materials, const RrtTexture *textures,
                             uint32_t n_textures, const RrtSceneExt *ext, uint32_t total_spp, uint32_t n_gpus,
-                            uint32_t flags, float *accum_out, uint8_t *rgb8_out, double *accum64_out = nullptr) {
+                            uint32_t flags, float *accum_out, uint8_t *rgb8_out, double *accum64_out = nullptr,
+                            bool books_rgb8 = false) {
     if (!cam || (!accum_out && !rgb8_out && !accum64_out)) return fail(RRT_E_INVALID, "null camera or output buffer");
-    if (accum64_out) flags |= RRT_FLAG_F64;
+    const bool f64 = accum64_out || books_rgb8;  // the device accum is D4 rows of f64 sums
+    if (f64) flags |= RRT_FLAG_F64;
     if (total_spp == 0) total_spp = (uint32_t)std::max(cam->params_f[3], 1.0f);  // cuda/mod.rs:384
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(RRT_E_NODEV, "no HIP device available");
@@ -2066,7 +2069,7 @@ static int32_t render_frame(const RrtCamera *cam, const RrtSphere *spheres, uint
         const RrtTile tile{16u, g, n_gpus, 0u, total_spp};
         const uint32_t rows = tile_rows_of(height, tile);
         const size_t n_px = (size_t)rows * width;
-        const size_t px_bytes = accum64_out ? sizeof(rrt::D4) : sizeof(float4);
+        const size_t px_bytes = f64 ? sizeof(rrt::D4) : sizeof(float4);
         const size_t row_bytes = rgb8_out ? (size_t)width * 3 : (size_t)width * px_bytes;
         float *d_accum = nullptr;
         uint8_t *d_rgb8 = nullptr;
@@ -2078,8 +2081,8 @@ static int32_t render_frame(const RrtCamera *cam, const RrtSphere *spheres, uint
             g_err = std::string("hipMalloc output failed: ") + hipGetErrorString(e);
             return set_err(RRT_E_NOMEM);
         }
-        rc = accum64_out ? rrt_render_tile_f64_async(scene, &tile, reinterpret_cast<double *>(d_accum), nullptr)
-                         : rrt_render_tile_async(scene, &tile, d_accum, nullptr);
+        rc = f64 ? rrt_render_tile_f64_async(scene, &tile, reinterpret_cast<double *>(d_accum), nullptr)
+                 : rrt_render_tile_async(scene, &tile, d_accum, nullptr);
         if (!rc && !(flags & RRT_FLAG_QUIET)) {
             // within-GPU progress (the reference prints one line per sample pass, cuda/mod.rs:426-431):
             // poll the work-queue heads every 100 ms while the kernel runs
@@ -2118,7 +2121,9 @@ static int32_t render_frame(const RrtCamera *cam, const RrtSphere *spheres, uint
         }
         if (!rc && rgb8_out) {
             const float scale = 1.0f / (float)total_spp;  // render_io.rs:10
-            e = rrt::launch_quantize(d_accum, d_rgb8, (uint32_t)n_px, scale, nullptr);
+            e = f64 ? rrt::launch_quantize_books_f64(reinterpret_cast<const double *>(d_accum), d_rgb8, (uint32_t)n_px,
+                                                     1.0 / (double)total_spp /* camera.rs:107 */, nullptr)
+                    : rrt::launch_quantize(d_accum, d_rgb8, (uint32_t)n_px, scale, nullptr);
             if (e != hipSuccess) {
                 g_err = std::string("quantise launch failed: ") + hipGetErrorString(e);
                 rc = RRT_E_HIP;
@@ -2176,6 +2181,18 @@ static int32_t render_frame(const RrtCamera *cam, const RrtSphere *spheres, uint
     return RRT_OK;
 }
 
+// The books quantiser (color.rs) enqueued on `stream`: T = float (float4 records) or double (D4);
+// the checks and messages of the host entries (rrt_quantize_accum_books[_f64]).
+template <class T>
+static int32_t quantize_books_async(uint32_t n_pixels, const T *d_accum, uint32_t spp, uint8_t *d_rgb8, void *stream,
+                                    hipError_t (*launch)(const T *, uint8_t *, uint32_t, double, hipStream_t)) {
+    if (n_pixels && (!d_accum || !d_rgb8)) return fail(RRT_E_INVALID, "null accum or rgb8");
+    if (spp == 0) return fail(RRT_E_INVALID, "samples_per_pixel must be >= 1 (camera.rs pixel_samples_scale)");
+    const hipError_t e = launch(d_accum, d_rgb8, n_pixels, 1.0 / (double)spp, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(RRT_E_HIP, std::string("quantise launch failed: ") + hipGetErrorString(e));
+    return RRT_OK;
+}
+
 extern "C" {
 
 int32_t rrt_hip_render(const RrtCamera *cam, const RrtSphere *spheres, uint32_t n_spheres,
@@ -2221,6 +2238,25 @@ int32_t rrt_hip_render_rgb8_ex(const RrtCamera *cam, const RrtSphere *spheres, u
     if (!rgb8_out) return fail(RRT_E_INVALID, "null camera or rgb8_out");
     return render_frame(cam, spheres, n_spheres, materials, n_materials, textures, n_textures, ext, total_spp,
                         n_gpus, flags, nullptr, rgb8_out);
+}
+
+int32_t rrt_hip_render_f64_rgb8(const RrtCamera *cam, const RrtSphere *spheres, uint32_t n_spheres,
+                                const RrtMaterial *materials, uint32_t n_materials, const RrtTexture *textures,
+                                uint32_t n_textures, uint32_t total_spp, uint32_t n_gpus, uint32_t flags,
+                                uint8_t *rgb8_out) {
+    if (!rgb8_out) return fail(RRT_E_INVALID, "null camera or rgb8_out");
+    return render_frame(cam, spheres, n_spheres, materials, n_materials, textures, n_textures, nullptr, total_spp,
+                        n_gpus, flags | RRT_FLAG_F64, nullptr, rgb8_out, nullptr, true);
+}
+
+int32_t rrt_quantize_accum_books_async(uint32_t n_pixels, const float *d_accum, uint32_t samples_per_pixel,
+                                       uint8_t *d_rgb8, void *stream) {
+    return quantize_books_async(n_pixels, d_accum, samples_per_pixel, d_rgb8, stream, rrt::launch_quantize_books);
+}
+
+int32_t rrt_quantize_accum_books_f64_async(uint32_t n_pixels, const double *d_accum, uint32_t samples_per_pixel,
+                                           uint8_t *d_rgb8, void *stream) {
+    return quantize_books_async(n_pixels, d_accum, samples_per_pixel, d_rgb8, stream, rrt::launch_quantize_books_f64);
 }
 
 int32_t rrt_quantize_accum_async(uint32_t n_pixels, const float *d_accum, uint32_t samples_per_pixel, uint8_t *d_rgb8,

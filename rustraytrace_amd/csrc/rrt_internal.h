@@ -352,6 +352,12 @@ hipError_t launch_render(const KParams &p, hipStream_t stream);
 hipError_t launch_render_counting(const KParams &p, hipStream_t stream);
 // render_io quantiser on the device (d_accum: n_pixels x float4; d_rgb8: n_pixels x 3 B).
 hipError_t launch_quantize(const float *d_accum, uint8_t *d_rgb8, uint32_t n_pixels, float scale, hipStream_t stream);
+// The books path's quantiser (color.rs write_color) on the device, implemented in rrt_books64.hip:
+// d_accum = n_pixels x float4, or n_pixels x D4 of f64 sums; scale = 1 / spp in f64; d_rgb8 as above.
+hipError_t launch_quantize_books(const float *d_accum, uint8_t *d_rgb8, uint32_t n_pixels, double scale,
+                                 hipStream_t stream);
+hipError_t launch_quantize_books_f64(const double *d_accum, uint8_t *d_rgb8, uint32_t n_pixels, double scale,
+                                     hipStream_t stream);
 // Test support (rrt_testing_recip_check): the kernel's recip_rn / clamped_slope against the IEEE
 // quotient (and sqrt_rn_big against the IEEE sqrt) over every f32 bit pattern; d_out: 3 zeroed u64
 // mismatch counters

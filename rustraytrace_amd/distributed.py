@@ -68,7 +68,8 @@ def sample_range(spp_per_rank: int, rank: int) -> tuple:
 
 
 def gather_rows(local, height: int, band: int, dist, group=None, dst: int = 0):
-    """Gather every rank's row-band accum (rows_r, W, 4) to `dst` and reassemble (H, W, 4).
+    """Gather every rank's row-band tile (rows_r, W, C) to `dst` and reassemble (H, W, C): C = 4 for
+    an accum (float32 or float64), 3 for rows quantised on the device (uint8).
 
     `local` is a torch tensor on the rank's device (cuda for RCCL, cpu for gloo). Ranks own
     different row counts; tiles are padded to the max so one gather moves them all."""
@@ -77,14 +78,14 @@ def gather_rows(local, height: int, band: int, dist, group=None, dst: int = 0):
     rank, world = dist.get_rank(group), dist.get_world_size(group)
     counts = [len(band_rows(height, band, r, world)) for r in range(world)]
     rmax = max(counts)
-    W = local.shape[1]
-    padded = torch.zeros((rmax, W, 4), dtype=local.dtype, device=local.device)
+    W, C = local.shape[1], local.shape[2]
+    padded = torch.zeros((rmax, W, C), dtype=local.dtype, device=local.device)
     padded[: local.shape[0]] = local
     bufs = [torch.empty_like(padded) for _ in range(world)] if rank == dst else None
     dist.gather(padded, gather_list=bufs, dst=dst, group=group)
     if rank != dst:
         return None
-    img = torch.empty((height, W, 4), dtype=local.dtype, device=local.device)
+    img = torch.empty((height, W, C), dtype=local.dtype, device=local.device)
     for r in range(world):
         idx = torch.as_tensor(band_rows(height, band, r, world), device=local.device)
         img[idx] = bufs[r][: counts[r]]

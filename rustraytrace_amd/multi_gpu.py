@@ -15,6 +15,11 @@ one JSON line: the slowest rank's kernel time, the gather time, Mrays/s over all
 `--f64` renders with the f64 books kernel (RRT_FLAG_F64) and gathers f64 tiles; the PPM then comes
 from the books path's own quantiser (color.rs), and the frame equals the 1-GPU f64 frame bit for bit.
 
+`--gather rgb8` (default `accum`: the gathers above) has each rank quantise its tile on the device, on
+the render's stream — the books quantiser with `--f64`, render_io's without — and gathers (rows, W, 3)
+uint8 tiles, 3 B/pixel instead of 16 or 32; rank 0 writes the PNM from the gathered bytes, the same
+file. Its JSON line carries "gather": "rgb8" and "gather_bytes".
+
 `--backend gloo` gathers host copies instead of device tensors (ranks may then share a GPU:
 device = local rank mod device count); it is the test path on a one-GPU box.
 """
@@ -42,7 +47,14 @@ def parse(argv=None):
     ap.add_argument("--f64", action="store_true",
                     help="the f64 books kernel (RRT_FLAG_F64): f64 tiles gathered, the PPM by the books path's own "
                          "quantiser (color.rs), bit-identical to the 1-GPU f64 frame")
-    return ap.parse_args(argv)
+    ap.add_argument("--gather", choices=("accum", "rgb8"), default="accum",
+                    help="what the ranks gather: their accum tiles (16 B/pixel, 32 with --f64), or rgb8: each rank "
+                         "quantises its tile on the device (the books quantiser with --f64, render_io's without) and "
+                         "3 B/pixel are gathered; the same PNM bytes")
+    args = ap.parse_args(argv)
+    if args.gather == "rgb8" and args.save_accum:
+        ap.error("--save-accum needs the gathered accum: not with --gather rgb8")
+    return args
 
 
 def main(argv=None) -> int:
@@ -99,12 +111,20 @@ def main(argv=None) -> int:
     if rows:
         render(tile, accum.data_ptr(), stream.cuda_stream)
     end.record(stream)
+    rgb8_gather = args.gather == "rgb8"
+    if rgb8_gather:  # the tile's bytes, quantised where the sums are, behind the render on its stream
+        tile_rgb8 = torch.empty((max(rows, 1), W, 3), dtype=torch.uint8, device=f"cuda:{device}")
+        if args.f64:
+            rrt.quantize_accum_books_async(rows * W, accum.data_ptr(), S, tile_rgb8.data_ptr(), stream.cuda_stream,
+                                           f64=True)
+        else:
+            rrt.quantize_accum_async(rows * W, accum.data_ptr(), S, tile_rgb8.data_ptr(), stream.cuda_stream)
     torch.cuda.synchronize()
     kernel_ms = start.elapsed_time(end)
     rays = ds.counters()["rays"]
     ds.close()
 
-    local_rows = accum[:rows]
+    local_rows = tile_rgb8[:rows] if rgb8_gather else accum[:rows]
     t = time.perf_counter()
     if use_dist:
         src = local_rows if backend == "nccl" else local_rows.cpu()
@@ -127,7 +147,9 @@ def main(argv=None) -> int:
         host = img.cpu().numpy()
         if args.save_accum:
             np.save(args.save_accum, host)
-        if args.out and args.f64:  # the books path's PPM (camera.rs:87-94 through color.rs:6-32)
+        if args.out and rgb8_gather:  # the ranks' own bytes: color.rs's with --f64, render_io's without
+            rrt.write_pnm_from_rgb8(W, H, host, args.p6, args.out)
+        elif args.out and args.f64:  # the books path's PPM (camera.rs:87-94 through color.rs:6-32)
             rgb8 = rrt.quantize_accum_books_f64(W, H, host, S)
             rrt.write_pnm_from_rgb8(W, H, rgb8, args.p6, args.out)
         elif args.out:
@@ -136,12 +158,15 @@ def main(argv=None) -> int:
                 rrt.write_pnm_from_rgb8(W, H, rgb8, True, args.out)
             else:
                 rrt.write_ppm_from_accum(W, H, host, S, args.out)
-        print(json.dumps({
+        line = {
             "config": args.config, "image": [W, H], "spp": S, "ranks": world, "backend": backend if use_dist else None,
             "dtype": "f64" if args.f64 else "f32",
             "split": f"{args.band}-row bands dealt in serpentine order", "kernel_ms_max_over_ranks": round(kernel_ms, 3),
             "gather_ms": round(gather_ms, 3), "rays": rays, "mrays_per_s": round(rays / kernel_ms / 1e3, 2),
-        }), file=sys.stderr if args.out == "-" else sys.stdout, flush=True)
+        }
+        if rgb8_gather:  # gather_bytes: the image's rows as gathered, 3 B/pixel
+            line.update(gather="rgb8", gather_bytes=int(host.nbytes))
+        print(json.dumps(line), file=sys.stderr if args.out == "-" else sys.stdout, flush=True)
     if use_dist:
         dist.destroy_process_group()
     return 0

@@ -130,6 +130,34 @@ def quantize_accum_async(n_pixels: int, d_accum_ptr: int, samples_per_pixel: int
                                                     ctypes.c_void_p(d_rgb8_ptr), ctypes.c_void_p(stream_ptr)))
 
 
+def render_f64_rgb8(scene: SceneData, spp: Optional[int] = None, n_gpus: int = 1, quiet: bool = True) -> np.ndarray:
+    """rrt_hip_render_f64_rgb8: the f64 books kernel (RRT_FLAG_F64, book-1 scenes), then the books
+    path's quantiser (color.rs) on the device; returns (H, W, 3) uint8, identical to
+    quantize_accum_books_f64(render_f64(scene)) at the same spp."""
+    lib = _lib.load()
+    if getattr(scene, "motion", None) is not None or getattr(scene, "quads", None) is not None:
+        raise ValueError("render_f64_rgb8: book-1 scenes only (RRT_FLAG_F64)")
+    out = np.zeros((scene.height, scene.width, 3), dtype=np.uint8)
+    tex, ntex, keep = _textures(scene)
+    flags = scene.flags | _lib.FLAG_F64 | (_lib.FLAG_QUIET if quiet else 0)
+    _lib.check(lib.rrt_hip_render_f64_rgb8(_lib.ptr(scene.camera), _lib.ptr(scene.spheres), len(scene.spheres),
+                                           _lib.ptr(scene.materials), len(scene.materials),
+                                           ctypes.cast(tex, ctypes.c_void_p) if tex is not None else None, ntex,
+                                           int(spp or 0), int(n_gpus), flags, _lib.ptr(out)))
+    del keep
+    return out
+
+
+def quantize_accum_books_async(n_pixels: int, d_accum_ptr: int, samples_per_pixel: int, d_rgb8_ptr: int,
+                               stream_ptr: int = 0, f64: bool = False) -> None:
+    """rrt_quantize_accum_books_async (float4 records) or, with f64=True, rrt_quantize_accum_books_f64_async
+    (4 doubles per pixel) on device pointers: the books path's quantiser (color.rs) enqueued on the stream."""
+    lib = _lib.load()
+    fn = lib.rrt_quantize_accum_books_f64_async if f64 else lib.rrt_quantize_accum_books_async
+    _lib.check(fn(int(n_pixels), ctypes.c_void_p(d_accum_ptr), int(samples_per_pixel), ctypes.c_void_p(d_rgb8_ptr),
+                  ctypes.c_void_p(stream_ptr)))
+
+
 def format_pnm_from_rgb8(width: int, height: int, rgb8: np.ndarray, binary: bool = False) -> bytes:
     """P3 (byte-identical to format_ppm_from_accum of the same image) or binary P6."""
     lib = _lib.load()
