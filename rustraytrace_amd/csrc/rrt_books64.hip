@@ -21,9 +21,9 @@
 // the f32 kernel (rrt_device.h: every draw is a 24-bit value, exact in f32 and f64). Every path
 // decision — which sphere a ray hits, the rejection loops, the Russian-roulette draw against this
 // bounce's attenuation — depends only on ray geometry, the draws and the attenuation, so the f64
-// paths follow the books path's exactly; only the throughput product's association differs (the
-// reference multiplies back to front through its recursion, this kernel front to back), which moves
-// a pixel's f64 sum by a few ulps. No exit_skip: in f64 a ray leaving a surface never re-hits it.
+// paths follow the books path's exactly, and the throughput product is formed back to front as the
+// reference's recursion forms it (fold_back64), so each sample's radiance is the books path's bit
+// for bit. No exit_skip: in f64 a ray leaving a surface never re-hits it.
 //
 // Scope: book-1 scenes (the BASELINE configs C1, C2, C4, C5: Lambertian, metal, dielectric,
 // image-textured Lambertian, diffuse light; sky or constant background). The host rejects book-2/3
@@ -78,24 +78,8 @@ __device__ __forceinline__ D3 mul(D3 a, D3 b) { return d3(a.x * b.x, a.y * b.y, 
 __device__ __forceinline__ D3 muls(D3 a, double s) { return d3(a.x * s, a.y * s, a.z * s); }
 // vec3.rs:156-158 dot = u0*v0 + u1*v1 + u2*v2 (left to right, unfused)
 __device__ __forceinline__ double dot(D3 a, D3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-// 1 / x, the IEEE quotient, in 6 instructions instead of the expansion's 11 for x in [2^-64, 2^64]:
-// there the expansion's v_div_scale steps are identities (numerator 1, quotient in [2^-64, 2^64]) and
-// its v_div_fixup passes the v_div_fmas result through, so what remains is its own reciprocal
-// (v_rcp_f64 + two Newton steps) and final step fma(fma(-x, r, 1), r, r) — the same operations the
-// f64 root divisions use (recip_a64 / div_a64, below). Outside the range: the IEEE division. Off by
-// default: same-box within noise (C2 +-0.5 %, C4 -1 %, `profiles/r5_f64_ab_batch5.log`).
-#ifndef RRT_F64_FASTRCP
-#define RRT_F64_FASTRCP 0
-#endif
-__device__ __forceinline__ double recip64(double x) {
-    if (!RRT_F64_FASTRCP || !(x >= 0x1.0p-64 && x <= 0x1.0p64)) return 1.0 / x;
-    double r = __builtin_amdgcn_rcp(x);
-    double e = __builtin_fma(-x, r, 1.0);
-    r = __builtin_fma(r, e, r);
-    e = __builtin_fma(-x, r, 1.0);
-    r = __builtin_fma(r, e, r);
-    return __builtin_fma(__builtin_fma(-x, r, 1.0), r, r);
-}
+// 1 / x, the IEEE quotient (Div<f64> is (1/rhs) * v, vec3.rs:142-148)
+__device__ __forceinline__ double recip64(double x) { return 1.0 / x; }
 // sqrt(x), the IEEE root: LLVM's AMDGPU f64 expansion (v_rsq_f64, a Goldschmidt step, two remainder
 // corrections, a class check for +-0 and +inf) without its scaling of small arguments. The expansion
 // multiplies x by 2^256 when x < 2^-767 and the root by 2^-128 after; for every other x both
@@ -104,10 +88,7 @@ __device__ __forceinline__ double recip64(double x) {
 // when no active lane of the wave holds a nonzero x below 2^-767 (a wave-uniform branch, the f32
 // kernel's sqrt_rn); saves two v_ldexp_f64, a compare and two selects per root. Taken in the leaf
 // loop's root only (at the shading sites the second inlined sequence costs more registers than it
-// saves). RRT_F64_SQRT=0: the library sequence everywhere.
-#ifndef RRT_F64_SQRT
-#define RRT_F64_SQRT 1
-#endif
+// saves).
 __device__ __forceinline__ double sqrt64_big(double x) {
     const double y = __builtin_amdgcn_rsq(x);
     double g = x * y;
@@ -123,7 +104,6 @@ __device__ __forceinline__ double sqrt64_big(double x) {
 }
 __device__ __forceinline__ bool sqrt64_small(double x) { return x < 0x1.0p-767 && x != 0.0; }
 __device__ __forceinline__ double sqrt64(double x) {
-    if (!RRT_F64_SQRT) return __builtin_sqrt(x);
     if (__ballot(sqrt64_small(x)) == 0) return sqrt64_big(x);
     return __builtin_sqrt(x);
 }
@@ -342,12 +322,8 @@ __device__ double rrt_atan2_64(double y, double x) {
 // x / c for the constant divisors 2 pi and pi (rrt_kernel.hip div_by_const in f64): q = x RN(1/c)
 // and Markstein's fma correction, the IEEE quotient away from underflow (8e8 random f64 arguments
 // in [2^-60, 8) against the CPU's division, tests/test_div_const.py); phi and theta are 0 or
-// far above it. RRT_DIV_CONST=0: the IEEE division.
-#ifndef RRT_DIV_CONST
-#define RRT_DIV_CONST 1
-#endif
+// far above it.
 __device__ __forceinline__ double div_by_const64(double x, double c) {
-    if (!RRT_DIV_CONST) return x / c;
     const double rc = 1.0 / c;  // folded: RN(1/c)
     const double q = x * rc;
     return __builtin_fma(__builtin_fma(-q, c, x), rc, q);
@@ -392,11 +368,8 @@ __device__ __forceinline__ int texel_row64(double theta, int h) {
 // angle itself (a few lookups in ten thousand on C4). The error bounds are at least twice the largest
 // error of acosf over every f32 in [-1, 1] and of atanf over every f32 in [0, 1] against the device's
 // f64 acos / atan (rrt_testing_trig32_check, tests/test_gpu_trig32.py); kLibm64Err covers fdlibm's
-// f64 error (< 1 ulp, < 2^-51 for these angles) many times over. RRT_F64_TEXEL_FAST=0: the fdlibm
-// angles always. Without image data no angle is needed (texture.rs:91-93).
-#ifndef RRT_F64_TEXEL_FAST
-#define RRT_F64_TEXEL_FAST 1
-#endif
+// f64 error (< 1 ulp, < 2^-51 for these angles) many times over. Without image data no angle is
+// needed (texture.rs:91-93).
 constexpr double kAcos32Err = 0x1.0p-20;
 constexpr double kAtan32Err = 0x1.0p-21;
 constexpr double kLibm64Err = 0x1.0p-40;
@@ -460,7 +433,8 @@ __device__ __forceinline__ bool texel_row_decided(double c, double e, int h, int
 }
 // The texel (column i, row j) of get_sphere_uv(outward) in a w x h image: each index from its f32
 // enclosure when that decides it (kFast), else from the fdlibm angle. col_fast / row_fast: which of the
-// two was decided by the enclosure. The render and the test-only rrt_device_ops64 both call this.
+// two was decided by the enclosure. The render calls it with kFast; the test-only rrt_device_ops64
+// also without, to compare the two.
 template <bool kFast>
 __device__ __forceinline__ void texel_index64(D3 outward, int w, int h, int &i, int &j, bool &col_fast, bool &row_fast) {
     double c = 0.0, e = 0.0;
@@ -478,7 +452,7 @@ __device__ __forceinline__ uint32_t texel_bytes64(const KParams &P, int tex, D3 
         j = texel_row64(1.0 + outward.y * 0x1.0p-60, t.height);
     } else {
         bool col_fast, row_fast;
-        texel_index64<RRT_F64_TEXEL_FAST != 0>(outward, t.width, t.height, i, j, col_fast, row_fast);
+        texel_index64<true>(outward, t.width, t.height, i, j, col_fast, row_fast);
     }
     const uint8_t *px = P.tex_pool + t.offset + ((size_t)j * t.width + i) * 3;
     return (uint32_t)px[0] | ((uint32_t)px[1] << 8) | ((uint32_t)px[2] << 16);
@@ -500,10 +474,7 @@ __device__ __forceinline__ D3 texel_value64(uint32_t bytes) {
 // pattern kTexelTag + b, a signalling NaN no albedo can hold: the host canonicalises NaN albedos to
 // the quiet NaN, rrt_host.cpp canonical_albedo) and the product is formed back to front when a path ends with radiance (sky, background or
 // a light). The same roundings as the recursion, in the same order: the kernel's per-sample radiance
-// equals BOOKS' bit for bit. RRT_F64_B2F=0: the throughput carried front to back (a few ulps off).
-#ifndef RRT_F64_B2F
-#define RRT_F64_B2F 1
-#endif
+// equals BOOKS' bit for bit.
 // the record's words are f32 bit patterns, kept as integers so that no move can quieten a tag
 struct Att32 {
     uint32_t x, y, z;
@@ -515,55 +486,19 @@ constexpr uint32_t kTexelTag = 0x7F800001u;
 __device__ __forceinline__ double att_decode(uint32_t f) {
     return f - kTexelTag < 256u ? texel_channel64(f - kTexelTag) : (double)__uint_as_float(f);
 }
-// RRT_F64_REC4 = 1: a 4-B record instead — the primitive index (its material's albedo), kRecOne for a
-// dielectric's (1, 1, 1), or kRecTexel | the texel's bytes (kRecTexel | 0x1000000: the no-data
-// texture's (0, 1, 1)); the fold reads the albedo back from the material record.
-#ifndef RRT_F64_REC4
-#define RRT_F64_REC4 0
-#endif
-[[maybe_unused]] constexpr uint32_t kRecOne = 0xFFFFFFFEu, kRecTexel = 0x80000000u;
-#if RRT_F64_REC4
-using HRec = uint32_t;
-#else
-using HRec = Att32;
-#endif
-__device__ __forceinline__ HRec rec_albedo(int prim, const GMaterial &m) {
-#if RRT_F64_REC4
-    (void)m;
-    return (uint32_t)prim;
-#else
-    (void)prim;
+__device__ __forceinline__ Att32 rec_albedo(const GMaterial &m) {
     return Att32{__float_as_uint(m.a.x), __float_as_uint(m.a.y), __float_as_uint(m.a.z)};
-#endif
 }
-__device__ __forceinline__ HRec rec_one() {
-#if RRT_F64_REC4
-    return kRecOne;
-#else
-    return Att32{0x3F800000u, 0x3F800000u, 0x3F800000u};
-#endif
-}
-__device__ __forceinline__ HRec rec_texel(uint32_t b) {
-#if RRT_F64_REC4
-    return kRecTexel | b;
-#else
+__device__ __forceinline__ Att32 rec_one() { return Att32{0x3F800000u, 0x3F800000u, 0x3F800000u}; }
+__device__ __forceinline__ Att32 rec_texel(uint32_t b) {
     if (b == 0x1000000u) return Att32{0u, 0x3F800000u, 0x3F800000u};
     return Att32{kTexelTag + (b & 0xffu), kTexelTag + ((b >> 8) & 0xffu), kTexelTag + (b >> 16)};
-#endif
 }
 // the attenuation a record stands for (kTex: the class has image textures)
 template <bool kTex>
-__device__ __forceinline__ D3 rec_att(const HRec &r, const GMaterial *__restrict__ mtl) {
-#if RRT_F64_REC4
-    if (r == kRecOne) return d3(1.0, 1.0, 1.0);
-    if (kTex && (r & kRecTexel)) return texel_value64(r & 0x1ffffffu);
-    const float4 a = mtl[r].a;
-    return f2d(a.x, a.y, a.z);
-#else
-    (void)mtl;
+__device__ __forceinline__ D3 rec_att(const Att32 &r) {
     return kTex ? d3(att_decode(r.x), att_decode(r.y), att_decode(r.z))
                 : f2d(__uint_as_float(r.x), __uint_as_float(r.y), __uint_as_float(r.z));
-#endif
 }
 // camera.rs:191-195: max of the attenuation's components, clamped to [0.05, 0.95]
 __device__ __forceinline__ double rr_probability64(D3 att) {
@@ -574,53 +509,34 @@ __device__ __forceinline__ double rr_probability64(D3 att) {
     if (pr > 0.95) pr = 0.95;
     return pr;
 }
-// The first RRT_F64_LDS_HIST records of a lane's history live in an LDS ring beside the traversal
-// stack ([bounce][thread], 12 B), the rest in global memory ([bounce][lane slot]): most paths are
-// short (C2: 2.6 rays per path), so their records never leave the CU.
-#ifndef RRT_F64_LDS_HIST
-#define RRT_F64_LDS_HIST 0
-#endif
+// A lane's history in global memory, [bounce][lane slot], 12 B a record.
 struct Hist64 {
-    HRec *ring;      // LDS: RRT_F64_LDS_HIST x block threads
-    HRec *global;    // P.hist
+    Att32 *global;   // P.hist
     uint32_t lanes;  // P.hist_lanes
     uint32_t slot;   // the lane's global slot
-    uint32_t tid;    // threadIdx.x
-    uint32_t blk;    // block threads
-    __device__ __forceinline__ void store(uint32_t k, const HRec &r) const {
-        if (RRT_F64_LDS_HIST > 0 && k < (uint32_t)RRT_F64_LDS_HIST) ring[k * blk + tid] = r;
-        else global[(size_t)k * lanes + slot] = r;
-    }
-    __device__ __forceinline__ HRec load(uint32_t k) const {
-        if (RRT_F64_LDS_HIST > 0 && k < (uint32_t)RRT_F64_LDS_HIST) return ring[k * blk + tid];
-        return global[(size_t)k * lanes + slot];
-    }
+    __device__ __forceinline__ void store(uint32_t k, const Att32 &r) const { global[(size_t)k * lanes + slot] = r; }
+    __device__ __forceinline__ Att32 load(uint32_t k) const { return global[(size_t)k * lanes + slot]; }
 };
 
-// Debug builds only (RRT_F64_B2F_MODE): 1 = the records stored but the radiance carried front to
-// back (prices the stores), 2 = the fold without its loads (prices the loads); wrong images.
-#ifndef RRT_F64_B2F_MODE
-#define RRT_F64_B2F_MODE 0
-#endif
 // Back to front in groups of RRT_F64_FOLD_GROUP records: a group's loads issue together, then its
 // products in order.
 #ifndef RRT_F64_FOLD_GROUP
 #define RRT_F64_FOLD_GROUP 4
 #endif
 template <bool kTex>
-__device__ __forceinline__ D3 fold_back64(const Hist64 &hist, const GMaterial *__restrict__ mtl, uint32_t n, D3 L) {
+__device__ __forceinline__ D3 fold_back64(const Hist64 &hist, uint32_t n, D3 L) {
     constexpr uint32_t G = RRT_F64_FOLD_GROUP;
     uint32_t k = n;
     while (k > 0u) {
         const uint32_t m = k < G ? k : G;
-        HRec a[G];
+        Att32 a[G];
 #pragma unroll
         for (uint32_t j = 0; j < G; ++j)
-            if (j < m) a[j] = RRT_F64_B2F_MODE == 2 ? rec_one() : hist.load(k - 1u - j);
+            if (j < m) a[j] = hist.load(k - 1u - j);
         D3 at[G];
 #pragma unroll
         for (uint32_t j = 0; j < G; ++j)
-            if (j < m) at[j] = rec_att<kTex>(a[j], mtl);
+            if (j < m) at[j] = rec_att<kTex>(a[j]);
 #pragma unroll
         for (uint32_t j = 0; j < G; ++j) {
             if (j < m) {
@@ -659,8 +575,7 @@ __device__ __forceinline__ RayK64 ray_consts64(D3 o, D3 d) {
 }
 
 struct Trav64 {
-    double closest;   // the best hit's root, or (lazy roots) an upper bound of it
-    double lo;        // lazy roots: a lower bound of the best hit's root (== closest when exact)
+    double closest;   // the best hit's root
     float closest32;  // fl32(closest): the box test's exit bound (rrt_box32.h)
     int hit_prim;
     int node;
@@ -725,9 +640,6 @@ __device__ __forceinline__ bool trav_node64(const Node *__restrict__ nodes, Stac
 // c = |oc|^2 - r*r, disc = h*h - a*c, roots (h -+ sqrt(disc)) / a in the open (0.001, closest).
 // (h + sq) / a >= (h - sq) / a, so the far root is tried only when the near one is <= 0.001 (or
 // NaN), exactly the roots the reference's surrounds() tests accept.
-#ifndef RRT_F64_DIVA
-#define RRT_F64_DIVA 1
-#endif
 // Per-ray reciprocal of a = |d|^2 for the root divisions: the reciprocal steps of the compiler's
 // IEEE f64 division expansion (v_rcp_f64 + two Newton steps) once per ray instead of per division.
 // For a in [2^-64, 2^64] v_div_scale is an identity on a, and on any numerator whose quotient is
@@ -754,21 +666,14 @@ __device__ __forceinline__ double recip_a64(double a) {
 // r = +-inf from a finite q is the IEEE result (the fma rounds once, overflow included). With the band
 // div_a64 is the IEEE quotient for every n, bit for bit (tests/test_gpu_device_ops64.py, DIV_A64;
 // without it the largest finite quotients came out NaN: accepted roots rejected).
-// RRT_F64_DIVA_GUARD=0: the code before the band (ra == 0 alone takes the division).
-#ifndef RRT_F64_DIVA_GUARD
-#define RRT_F64_DIVA_GUARD 1
-#endif
 __device__ __forceinline__ double div_a64_short(double n, double a, double ra) {
     const double q = n * ra;
     return __builtin_fma(__builtin_fma(-a, q, n), ra, q);
 }
-__device__ __forceinline__ bool div_a64_in_band(double r, double ra) {
-    return RRT_F64_DIVA_GUARD ? __builtin_fabs(r) >= 0x1.0p-896 : ra != 0.0;
-}
+__device__ __forceinline__ bool div_a64_in_band(double r) { return __builtin_fabs(r) >= 0x1.0p-896; }
 __device__ __forceinline__ double div_a64(double n, double a, double ra) {
-    if (!RRT_F64_DIVA) return n / a;
     const double r = div_a64_short(n, a, ra);
-    return div_a64_in_band(r, ra) ? r : n / a;
+    return div_a64_in_band(r) ? r : n / a;
 }
 // The root Sphere::hit tries over (0.001, closest): the near root (h - sq) / a if above 0.001, else the
 // far one. Both from the short division with one band test, on the root chosen: a near root above 0.001
@@ -782,13 +687,9 @@ __device__ __forceinline__ double div_a64(double n, double a, double ra) {
 // division: C2 -2.5 % instead of -6.8 % against the code without the band).
 __device__ __forceinline__ double root64(double h, double sq, double a, double ra) {
     const double n1 = h - sq, n2 = h + sq;
-    if (!RRT_F64_DIVA) {
-        const double root = n1 / a;
-        return 0.001 < root ? root : n2 / a;
-    }
     double root = div_a64_short(n1, a, ra);
     if (!(0.001 < root)) root = div_a64_short(n2, a, ra);
-    if (!div_a64_in_band(root, ra)) {
+    if (!div_a64_in_band(root)) {
         root = n1 / a;
         if (!(0.001 < root)) root = n2 / a;
     }
@@ -797,24 +698,18 @@ __device__ __forceinline__ double root64(double h, double sq, double a, double r
 
 // A sphere record widened to f64 while the block stages the scene in LDS (kF64LdsWide): center and
 // r * r formed once instead of four f32 -> f64 conversions and a product per sphere test. The f32
-// radius squared is exact in f64 (48 significant bits), so r2 is the reference's r * r, and
-// sqrt(r2) its r again (a correctly rounded root of an exact square).
-#ifndef RRT_F64_R2
-#define RRT_F64_R2 1
-#endif
+// radius squared is exact in f64 (48 significant bits), so r2 is the reference's r * r.
 struct alignas(16) Sphere64 {
-    double cx, cy, cz, r2;  // r2 = r * r (RRT_F64_R2) or r
+    double cx, cy, cz, r2;  // r2 = r * r
 };
 // the widening of an f32 record (center, r): the staging loop's, and the test-only rrt_device_ops64's
 __device__ __forceinline__ Sphere64 widen_sphere64(const float4 &c) {
-    return Sphere64{(double)c.x, (double)c.y, (double)c.z, RRT_F64_R2 ? (double)c.w * (double)c.w : (double)c.w};
+    return Sphere64{(double)c.x, (double)c.y, (double)c.z, (double)c.w * (double)c.w};
 }
 __device__ __forceinline__ D3 center_of(const float4 &c) { return f2d(c.x, c.y, c.z); }
 __device__ __forceinline__ D3 center_of(const Sphere64 &c) { return d3(c.cx, c.cy, c.cz); }
-__device__ __forceinline__ double radius_of(const float4 &c) { return (double)c.w; }
-__device__ __forceinline__ double radius_of(const Sphere64 &c) { return RRT_F64_R2 ? __builtin_sqrt(c.r2) : c.r2; }
 __device__ __forceinline__ double radius_sq_of(const float4 &c) { return (double)c.w * (double)c.w; }
-__device__ __forceinline__ double radius_sq_of(const Sphere64 &c) { return RRT_F64_R2 ? c.r2 : c.r2 * c.r2; }
+__device__ __forceinline__ double radius_sq_of(const Sphere64 &c) { return c.r2; }
 
 // The f32 pre-test (rrt_sphere32.h) over the lane's range first: it marks the spheres whose f64
 // discriminant may be >= 0, and the f64 test runs over the marked ones only, in index order (the
@@ -826,25 +721,8 @@ __device__ __forceinline__ double radius_sq_of(const Sphere64 &c) { return RRT_F
 #ifndef RRT_F64_SPHERE32
 #define RRT_F64_SPHERE32 0
 #endif
-#ifndef RRT_F64_S32_HOLD
-#define RRT_F64_S32_HOLD 0
-#endif
-// ---- lazy exact roots (rrt_kernel.hip's RRT_LAZY_ROOT, for the f64 roots) ----------------------------
-// Each root is bracketed from the f32 square root of fl32(disc) and the per-ray reciprocal: the best
-// candidate is kept as an interval [lo, closest], a candidate wholly below lo replaces it, one wholly at
-// or above closest is rejected (both the exact loop's decisions: strictly less, the first of equal
-// roots wins), and an overlap — or a root near tmin, a ray inside the sphere, disc outside
-// [2^-96, 2^126], a NaN — is decided on the exact roots. The winner's exact root is formed once, when
-// the query ends (lazy_finish64). The box tests prune with the upper bound, a superset of the exact
-// walk in the same order. So every decision and every t equal the exact loop's (tests/test_gpu_books64.py
-// green with it on). Measured and left off (round 6, same-box, profiles/r6_f64_sqrt_lazy_ab.log): C2
-// -8 %, C5 -5.5 %, C4 -10 % — the winner's exact root at each query's end, the held interval (a
-// double more: 4 VGPRs spilled at the 128-VGPR bound) and the bookkeeping cost more than the sparse
-// exact roots did. RRT_F64_LAZY=1 turns it on.
-#ifndef RRT_F64_LAZY
-#define RRT_F64_LAZY 0
-#endif
-// The exact root leaves64 forms for primitive i: the near root if above tmin, else the far.
+// The exact root leaves64 forms for primitive i: the near root if above tmin, else the far (the
+// test-only rrt_device_ops64 kernel compares it with leaves64's decision).
 template <typename Rec>
 __device__ __forceinline__ double exact_root64(const Rec *__restrict__ prims, int i, D3 o, D3 d, double a, double ra) {
     const Rec cr = prims[i];
@@ -854,36 +732,16 @@ __device__ __forceinline__ double exact_root64(const Rec *__restrict__ prims, in
     const double disc = h * h - a * c;
     return root64(h, sqrt64(disc), a, ra);
 }
-template <typename Rec>
-__device__ __forceinline__ void lazy_resolve64(const Rec *__restrict__ prims, int i, D3 o, D3 d, double a, double ra,
-                                               Trav64 &t) {
-    const double rc = exact_root64(prims, i, o, d, a, ra);
-    if (0.001 < rc && rc < t.closest) {  // else rc >= closest >= the best's root: rejected
-        const double rb = (t.hit_prim >= 0 && t.lo != t.closest) ? exact_root64(prims, t.hit_prim, o, d, a, ra) : t.closest;
-        if (rc < rb) t.hit_prim = i;
-        t.lo = t.closest = rc < rb ? rc : rb;
-        t.closest32 = (float)t.closest;
-    }
-}
-template <typename Rec>
-__device__ __forceinline__ void lazy_finish64(const Rec *__restrict__ prims, D3 o, D3 d, Trav64 &t) {
-    if (t.hit_prim >= 0 && t.lo != t.closest) {
-        const double a = dot(d, d);
-        t.lo = t.closest = exact_root64(prims, t.hit_prim, o, d, a, RRT_F64_DIVA ? recip_a64(a) : 0.0);
-    }
-}
-
 template <bool kCount, typename Rec>
 __device__ __forceinline__ void leaves64(const Rec *__restrict__ prims, const float4 *__restrict__ recs32, Leaves lv,
-                                         D3 o, D3 d, double a, const RaySphere32 &r32, bool pre, Trav64 &t,
-                                         Counters &cnt) {
-    const double ra = RRT_F64_DIVA ? recip_a64(a) : 0.0;
+                                         D3 o, D3 d, double a, bool pre, Trav64 &t, Counters &cnt) {
+    const double ra = recip_a64(a);
     const int first = (int)(lv & kLinkFirstMask), count = (int)(lv >> kLinkCountShift);
     uint32_t todo = (1u << count) - 1u;
     if (RRT_F64_SPHERE32 && pre) {
-        // the ray's f32 constants: held from the ray start, or formed here per batch (fewer VGPRs
-        // live across the node steps)
-        const RaySphere32 rs = RRT_F64_S32_HOLD ? r32 : sphere32_ray(o.x, o.y, o.z, d.x, d.y, d.z);
+        // the ray's f32 constants, formed here per batch (held from the ray start they cost VGPRs
+        // across the node steps)
+        const RaySphere32 rs = sphere32_ray(o.x, o.y, o.z, d.x, d.y, d.z);
         todo = 0;
         for (int j = 0; j < count; ++j) {
             const float4 c = recs32[first + j];
@@ -906,42 +764,18 @@ __device__ __forceinline__ void leaves64(const Rec *__restrict__ prims, const fl
         if (RRT_F64_STATS == 3) cnt.d0++;
         if (disc < 0.0) continue;
         if (RRT_F64_STATS == 2 || RRT_F64_STATS == 3 || RRT_F64_STATS == 5) cnt.d1++;
-        if constexpr (RRT_F64_LAZY && !kCount && RRT_F64_DIVA) {
-            // |sv - sqrt(disc)| <= 2^-22.2 sqrt(disc): fl32(disc) moves the root by 2^-25 relative, and
-            // v_sqrt_f32 is within 1.5 ulp (the f32 kernel's exhaustive device check); so
-            // |q - r0| <= 2^-21.9 sv ra + 2^-50 (|h| + sv) ra, and e = 2^-20 (sv + |h|) ra bounds it
-            // with 3.7x to spare (the f64 roundings of e and of q -+ e are ~2^-52 relative)
-            const float df = (float)disc;
-            const double sv = (double)__builtin_amdgcn_sqrtf(df);
-            const double q = (h - sv) * ra;
-            const double e = (sv + __builtin_fabs(h)) * (ra * 0x1.0p-20);
-            const double l = q - e, u = q + e;
-            const bool valid = (df >= 0x1.0p-96f) & (df <= 0x1.0p126f) & (l > 0.001);
-            const bool acc = valid & (u < t.lo);
-            const bool rej = valid & (l >= t.closest);
-            t.lo = acc ? l : t.lo;
-            t.closest = acc ? u : t.closest;
-            t.closest32 = acc ? (float)u : t.closest32;
-            t.hit_prim = acc ? i : t.hit_prim;
-            if (!(acc | rej)) lazy_resolve64(prims, i, o, d, a, ra, t);
-        } else {
-            const double root = root64(h, sqrt64(disc), a, ra);
-            if (0.001 < root && root < t.closest) {
-                if (RRT_F64_STATS == 3) cnt.d2++;
-                t.closest = root;
-                t.lo = root;
-                t.closest32 = (float)root;
-                t.hit_prim = i;
-            }
+        const double root = root64(h, sqrt64(disc), a, ra);
+        if (0.001 < root && root < t.closest) {
+            if (RRT_F64_STATS == 3) cnt.d2++;
+            t.closest = root;
+            t.closest32 = (float)root;
+            t.hit_prim = i;
         }
     }
 }
 
 struct Path64 {
     D3 o, d;
-#if !RRT_F64_B2F || RRT_F64_B2F_MODE == 1
-    D3 T;
-#endif
     RngState rng;
     uint32_t k;  // bounce index (camera ray = 0)
 };
@@ -953,20 +787,10 @@ __device__ __forceinline__ void camera_ray64(uint32_t x, uint32_t y, Path64 &ps)
     const auto &C = *kernarg_params();
     const double ox = rnd64(ps.rng) - 0.5, oy = rnd64(ps.rng) - 0.5;  // sample_square
     const double fi = (double)x + ox, fj = (double)y + oy;
-#ifndef RRT_F64_CAM64
-#define RRT_F64_CAM64 1
-#endif
-#if !RRT_F64_CAM64
-    const D3 sample = d3(((double)C.p00[0] + (double)C.du[0] * fi) + (double)C.dv[0] * fj,
-                         ((double)C.p00[1] + (double)C.du[1] * fi) + (double)C.dv[1] * fj,
-                         ((double)C.p00[2] + (double)C.du[2] * fi) + (double)C.dv[2] * fj);
-    D3 origin = f2d(C.center[0], C.center[1], C.center[2]);
-#else
     const D3 sample = d3((C.cam64[0][0] + C.cam64[1][0] * fi) + C.cam64[2][0] * fj,
                          (C.cam64[0][1] + C.cam64[1][1] * fi) + C.cam64[2][1] * fj,
                          (C.cam64[0][2] + C.cam64[1][2] * fi) + C.cam64[2][2] * fj);
     D3 origin = d3(C.cam64[3][0], C.cam64[3][1], C.cam64[3][2]);
-#endif
     if (C.defocus_radius > 0.0f) {
         int32_t a, b;
         for (;;) {  // vec3.rs:172-179 random_in_unit_disk, decided on integers (random_unit_vector)
@@ -982,9 +806,6 @@ __device__ __forceinline__ void camera_ray64(uint32_t x, uint32_t y, Path64 &ps)
     if (C.flags & 0x1u) (void)rnd64(ps.rng);  // RRT_FLAG_RAY_TIME: the time draw (the_next_week/camera.rs:160)
     ps.o = origin;
     ps.d = sub(sample, origin);
-#if !RRT_F64_B2F || RRT_F64_B2F_MODE == 1
-    ps.T = d3(1.0, 1.0, 1.0);
-#endif
     ps.k = 0;
 }
 
@@ -997,19 +818,9 @@ __device__ __forceinline__ void camera_ray64(uint32_t x, uint32_t y, Path64 &ps)
 // atan2 / texel path compiled out), kF64Diffuse (Lambertian and emissive only: metal and dielectric
 // compiled out), chosen per scene by launch_render_pass_f64 like the f32 kernel's classes.
 constexpr int kF64Full = 0, kF64Untextured = 1, kF64Diffuse = 2;
-// RRT_F64_DEFER = n > 0: a Lambertian scatter's rejection loop (random_unit_vector) draws at most n
-// candidates per pass of the work loop; a lane whose candidates all fail stays at its hit (ps.o = the
-// hit point, ps.d = the normal, `prec` = the attenuation record, `pend` = 1), takes no closest-hit
-// query, and draws on in the next pass. The same draws in the same order (candidates, then Russian
-// roulette's), so the same path: only the wave's schedule changes. The wave no longer runs the
-// loop until its unluckiest lane accepts (~5.6 wave-iterations for ~1.9 candidates per lane).
-#ifndef RRT_F64_DEFER
-#define RRT_F64_DEFER 0
-#endif
 template <int kClass, typename Rec>
 __device__ __forceinline__ bool shade64(const KParams &P, const Rec *prims, const GMaterial *mtl, const double *inv_r,
-                                        Path64 &ps, double t, int prim, D3 &Le, const Hist64 &hist, uint32_t &pend,
-                                        HRec &prec) {
+                                        Path64 &ps, double t, int prim, D3 &Le, const Hist64 &hist) {
     Le = d3(0.0, 0.0, 0.0);
     if (prim < 0) {
         D3 bg;
@@ -1020,35 +831,24 @@ __device__ __forceinline__ bool shade64(const KParams &P, const Rec *prims, cons
             const double a = 0.5 * (ud.y + 1.0);
             bg = d3((1.0 - a) * 1.0 + a * 0.5, (1.0 - a) * 1.0 + a * 0.7, (1.0 - a) * 1.0 + a * 1.0);
         }
-#if RRT_F64_B2F && RRT_F64_B2F_MODE != 1
         Le = bg;
-#else
-        Le = mul(ps.T, bg);
-#endif
         return true;
     }
     const Rec cr = prims[prim];
     const D3 p = add(ps.o, muls(ps.d, t));  // Ray::at = orig + t * dir
-#ifndef RRT_F64_HOST_INVR
-#define RRT_F64_HOST_INVR 1
-#endif
-    // (p - center) / r = (1/r) * v (vec3.rs:142-148)
-    const D3 outward = muls(sub(p, center_of(cr)), RRT_F64_HOST_INVR ? inv_r[prim] : 1.0 / radius_of(cr));
+    // (p - center) / r = (1/r) * v (vec3.rs:142-148), 1 / r from the host's table
+    const D3 outward = muls(sub(p, center_of(cr)), inv_r[prim]);
     const bool front = dot(ps.d, outward) < 0.0;
     const D3 nrm = front ? outward : d3(-outward.x, -outward.y, -outward.z);
     const GMaterial m = mtl[prim];
     const int kind = m.b.x;
     const D3 albedo = f2d(m.a.x, m.a.y, m.a.z);
     if (kind == 4) {  // DiffuseLight: emitted, scatter None
-#if RRT_F64_B2F && RRT_F64_B2F_MODE != 1
         Le = albedo;
-#else
-        Le = mul(ps.T, albedo);
-#endif
         return true;
     }
     D3 att, dir;
-    HRec rec = rec_albedo(prim, m);  // the attenuation's history record
+    Att32 rec = rec_albedo(m);  // the attenuation's history record
     if (kClass != kF64Diffuse && kind == 1) {  // Metal (material.rs:53-64): unit(reflect) + fuzz * random_unit_vector
         const D3 refl = unit_vector(reflect(ps.d, nrm));
         dir = add(refl, muls(random_unit_vector(ps.rng), (double)m.a.w));
@@ -1056,19 +856,10 @@ __device__ __forceinline__ bool shade64(const KParams &P, const Rec *prims, cons
         att = albedo;
     } else if (kClass != kF64Diffuse && kind == 2) {  // Dielectric (material.rs:83-102)
         const double eta = (double)__int_as_float(m.b.y);
-#ifndef RRT_F64_DIEL_HOST
-#define RRT_F64_DIEL_HOST 1
-#endif
-        double ri, r0;
-        if (RRT_F64_DIEL_HOST) {  // 1 / eta and both r0 formed on the host (rrt_host.cpp dielectric_consts64)
-            const double4 k = P.prim_diel64[prim];
-            ri = front ? k.x : eta;
-            r0 = front ? k.y : k.z;
-        } else {
-            ri = front ? 1.0 / eta : eta;
-            r0 = (1.0 - ri) / (1.0 + ri);
-            r0 = r0 * r0;
-        }
+        // 1 / eta and both r0 formed on the host (rrt_host.cpp dielectric_consts64)
+        const double4 k = P.prim_diel64[prim];
+        const double ri = front ? k.x : eta;
+        const double r0 = front ? k.y : k.z;
         const D3 ud = unit_vector(ps.d);
         const double c = rmin(-dot(ud, nrm), 1.0);
         const double sn = __builtin_sqrt(1.0 - c * c);
@@ -1084,67 +875,18 @@ __device__ __forceinline__ bool shade64(const KParams &P, const Rec *prims, cons
             att = texel_value64(b);
             rec = rec_texel(b);
         }
-        if (RRT_F64_DEFER) {  // the scatter direction is drawn by the work loop (lambert_draw64)
-            ps.o = p;
-            ps.d = nrm;
-            prec = rec;
-            pend = 1;
-            return false;
-        }
         dir = add(nrm, random_unit_vector(ps.rng));
         if (__builtin_fabs(dir.x) < 1e-8 && __builtin_fabs(dir.y) < 1e-8 && __builtin_fabs(dir.z) < 1e-8) dir = nrm;
     }
     if (ps.k >= 5u) {  // camera.rs:189-200
         const double pr = rr_probability64(att);
         if (rnd64(ps.rng) > pr) return true;
-#if !RRT_F64_B2F || RRT_F64_B2F_MODE == 1
-        ps.T = muls(mul(ps.T, att), recip64(pr));
-    } else {
-        ps.T = mul(ps.T, att);
-#endif
     }
-#if RRT_F64_B2F
     hist.store(ps.k, rec);
-#else
-    (void)rec;
-    (void)hist;
-#endif
     ps.o = p;
     ps.d = dir;
     ps.k++;
     return false;
-}
-
-// A pending Lambertian scatter (RRT_F64_DEFER): up to RRT_F64_DEFER candidates of random_unit_vector
-// (vec3.rs:181-189, decided on integers); on acceptance the scatter completes as in shade64 —
-// direction nrm + unit, near_zero (material.rs:33-35), Russian roulette (camera.rs:189-200) and the
-// history record. Returns 1 when the path ended (Russian roulette), 0 otherwise; pend = 0 once done.
-template <int kClass>
-__device__ __forceinline__ uint32_t lambert_draw64(const KParams &P, Path64 &ps, const Hist64 &hist, uint32_t &pend,
-                                                   const HRec &prec, const GMaterial *mtl) {
-    int32_t a = 0, b = 0, c = 0;
-    bool ok = false;
-    for (int it = 0; it < (RRT_F64_DEFER > 0 ? RRT_F64_DEFER : 1) && !ok; ++it) {
-        a = draw_centred(ps.rng);
-        b = draw_centred(ps.rng);
-        c = draw_centred(ps.rng);
-        ok = in_ball<false>(a, b, c);  // 0 < S <= 2^46
-    }
-    if (!ok) return 0u;
-    pend = 0;
-    const double x = centred_to_pm1(a), y = centred_to_pm1(b), z = centred_to_pm1(c);
-    const double lensq = x * x + y * y + z * z;
-    const D3 nrm = ps.d;
-    D3 dir = add(nrm, muls(d3(x, y, z), recip64(__builtin_sqrt(lensq))));
-    if (__builtin_fabs(dir.x) < 1e-8 && __builtin_fabs(dir.y) < 1e-8 && __builtin_fabs(dir.z) < 1e-8) dir = nrm;
-    if (ps.k >= 5u) {
-        const D3 att = rec_att<kClass != kF64Untextured>(prec, mtl);
-        if (rnd64(ps.rng) > rr_probability64(att)) return 1u;
-    }
-    hist.store(ps.k, prec);
-    ps.d = dir;
-    ps.k++;
-    return 0u;
 }
 
 // The persistent work loop of rrt_kernel.hip's render_body (same queue, units, chunk order,
@@ -1166,9 +908,8 @@ __device__ __forceinline__ void render64_body(const KParams &P) {
     const double *inv_r = P.prim_inv_r64;
     const float4 *recs32 = P.prim_cr;  // the pre-test's f32 records (center, r)
     const uint32_t stack16 = (P.stack_depth * kBlk * sizeof(uint16_t) + 15u) / 16u;
-    constexpr uint32_t kRing16 = (uint32_t)RRT_F64_LDS_HIST * kBlk * (uint32_t)sizeof(HRec) / 16u;  // kBlk: a multiple of 64
     if constexpr (kLds) {  // stage nodes + spheres (+ 1/r) once per block
-        uint4 *dst = lds_dyn + stack16 + kRing16;
+        uint4 *dst = lds_dyn + stack16;
         // Node112: each 80-B GNode re-laid as 112 B whose axis a holds both children's (lo, hi), then
         // both (hi, lo), and the links at 96 — one ds_read_b128 per axis at the ray's sign offset
         // reads both children's (entry, exit) pairs (4 LDS cycles, against 8 for two ds_read2_b32):
@@ -1230,10 +971,7 @@ __device__ __forceinline__ void render64_body(const KParams &P) {
     uint32_t tail = 0;       // the unit is a tail chunk: its samples' radiances go to seq64 one by one
     uint32_t tcidx = 0;      // a tail unit's chunk index within the pass
     uint32_t tmask = 0;      // a tail unit's samples with nonzero radiance (bit = sample - its first)
-    uint32_t pend = 0;       // RRT_F64_DEFER: a Lambertian scatter waits for an accepted candidate
-    HRec prec{};
-    const Hist64 hist{reinterpret_cast<HRec *>(lds_dyn + stack16), reinterpret_cast<HRec *>(P.hist), P.hist_lanes,
-                      blockIdx.x * (uint32_t)kBlk + threadIdx.x, threadIdx.x, (uint32_t)kBlk};
+    const Hist64 hist{reinterpret_cast<Att32 *>(P.hist), P.hist_lanes, blockIdx.x * (uint32_t)kBlk + threadIdx.x};
     uint64_t pkey = 0;
     D3 sum = d3(0.0, 0.0, 0.0);
     Path64 ps;
@@ -1307,7 +1045,6 @@ __device__ __forceinline__ void render64_body(const KParams &P) {
                 seg_done = 1;
             } else {
                 tr.closest = __builtin_inf();  // Interval(0.001, INFINITY)
-                tr.lo = __builtin_inf();
                 tr.closest32 = __builtin_inff();
                 tr.hit_prim = -1;
                 tr.node = 0;
@@ -1326,11 +1063,9 @@ __device__ __forceinline__ void render64_body(const KParams &P) {
             tp = t;
         }
         RayK64 rk;
-        RaySphere32 r32;
         double a = 0.0;
         if (tr.node >= 0) {
             rk = ray_consts64(ps.o, ps.d);
-            if (RRT_F64_SPHERE32 && RRT_F64_S32_HOLD) r32 = sphere32_ray(ps.o.x, ps.o.y, ps.o.z, ps.d.x, ps.d.y, ps.d.z);
             a = dot(ps.d, ps.d);  // sphere.rs:27 r.direction().length_squared()
         }
         __builtin_amdgcn_s_setprio(kPrioNode);
@@ -1355,7 +1090,7 @@ __device__ __forceinline__ void render64_body(const KParams &P) {
                 __builtin_amdgcn_s_setprio(kPrioLeaf);
                 [[maybe_unused]] const uint32_t n_l = lv >> kLinkCountShift, s_l = cnt.d1;
                 if (lv != 0) {
-                    leaves64<kCount>(prims, recs32, lv, ps.o, ps.d, a, r32, P.sphere32 != 0u, tr, cnt);
+                    leaves64<kCount>(prims, recs32, lv, ps.o, ps.d, a, P.sphere32 != 0u, tr, cnt);
                     lv = 0;
                 }
                 if constexpr (RRT_F64_STATS == 2) {
@@ -1375,23 +1110,16 @@ __device__ __forceinline__ void render64_body(const KParams &P) {
         }
         __builtin_amdgcn_s_setprio(kPrioShade);
         D3 Le = d3(0.0, 0.0, 0.0);
-        if (has && !need_ray && tr.node < 0 && !pend) {
+        if (has && !(need_ray || tr.node >= 0)) {  // the lane's query ended this pass
             need_ray = 1;
-            if constexpr (RRT_F64_LAZY && !kCount && RRT_F64_DIVA) lazy_finish64(prims, ps.o, ps.d, tr);
-            seg_done = shade64<kClass>(P, prims, mtl, inv_r, ps, tr.closest, tr.hit_prim, Le, hist, pend, prec) ? 1u : 0u;
-        }
-        if (RRT_F64_DEFER && pend) {
-            seg_done = lambert_draw64<kClass>(P, ps, hist, pend, prec, mtl);
-            need_ray = pend ? 0u : 1u;
+            seg_done = shade64<kClass>(P, prims, mtl, inv_r, ps, tr.closest, tr.hit_prim, Le, hist) ? 1u : 0u;
         }
         w_paths += (uint32_t)__popcll(__ballot(seg_done));
         if (seg_done) {  // pixel_color += ray_color(..) (camera.rs:72-76)
-#if RRT_F64_B2F && RRT_F64_B2F_MODE != 1
             // the radiance at the path's end carried back through its scatters; a path that ended
             // with none (absorbed, Russian roulette, max_depth) adds an exact 0
             if (Le.x != 0.0 || Le.y != 0.0 || Le.z != 0.0)
-                Le = fold_back64<kClass != kF64Untextured>(hist, mtl, ps.k, Le);
-#endif
+                Le = fold_back64<kClass != kF64Untextured>(hist, ps.k, Le);
             const auto &Q = *kernarg_params();
             if (tail) {  // a tail sample: its radiance, folded into the pixel's sum in order later
                 // only nonzero radiances are kept (an exact 0 leaves BOOKS' sum unchanged), packed in
@@ -1400,18 +1128,11 @@ __device__ __forceinline__ void render64_body(const KParams &P) {
                     const size_t npx = (size_t)Q.tile_rows * Q.width;
                     const uint32_t j = (uint32_t)__popc(tmask);
                     double *o = Q.seq64 + 3u * (((size_t)tcidx * Q.chunk_small + j) * npx + px);
-#ifndef RRT_F64_SEQ_NT
-#define RRT_F64_SEQ_NT 1
-#endif
-                    if (RRT_F64_SEQ_NT) {  // streamed (read once, by the fold after the pass): kept
-                        __builtin_nontemporal_store(Le.x, o);  // from evicting the history's lines in L2
-                        __builtin_nontemporal_store(Le.y, o + 1);
-                        __builtin_nontemporal_store(Le.z, o + 2);
-                    } else {
-                        o[0] = Le.x;
-                        o[1] = Le.y;
-                        o[2] = Le.z;
-                    }
+                    // streamed (read once, by the fold after the pass): kept from evicting the
+                    // history's lines in L2
+                    __builtin_nontemporal_store(Le.x, o);
+                    __builtin_nontemporal_store(Le.y, o + 1);
+                    __builtin_nontemporal_store(Le.z, o + 2);
                     tmask |= 1u << (s - Q.sample_begin - Q.seq_first - tcidx * Q.chunk_small);
                 }
             } else {
@@ -1678,16 +1399,15 @@ __device__ __forceinline__ void st3(uint64_t *p, D3 v) {
 template <typename Rec>
 __device__ __forceinline__ void sphere_ops64(const Rec &rec, const float4 &rec32, D3 o, D3 d, double closest, uint64_t *r) {
     const double a = dot(d, d);
-    r[0] = bits64(exact_root64(&rec, 0, o, d, a, RRT_F64_DIVA ? recip_a64(a) : 0.0));
+    r[0] = bits64(exact_root64(&rec, 0, o, d, a, recip_a64(a)));
     Trav64 t;
-    t.closest = t.lo = closest;
+    t.closest = closest;
     t.closest32 = (float)closest;
     t.hit_prim = -1;
     t.node = -1;
     t.sp = 0;
     Counters cnt = {0, 0, 0, 0, 0, 0};
-    leaves64<false>(&rec, &rec32, (Leaves)(1u << kLinkCountShift), o, d, a, RaySphere32{}, false, t, cnt);
-    if (RRT_F64_LAZY) lazy_finish64(&rec, o, d, t);
+    leaves64<false>(&rec, &rec32, (Leaves)(1u << kLinkCountShift), o, d, a, false, t, cnt);
     r[1] = t.hit_prim == 0 ? 1u : 0u;
     r[2] = bits64(t.closest);
 }
@@ -1732,7 +1452,7 @@ __global__ __launch_bounds__(256) void rrt_device_ops64(uint32_t op, uint32_t n,
             const int w = (int)x[3], h = (int)x[4];
             int ti = 0, tj = 0;
             bool cf = false, rf = false;
-            texel_index64<RRT_F64_TEXEL_FAST != 0>(ld3(x), w, h, ti, tj, cf, rf);
+            texel_index64<true>(ld3(x), w, h, ti, tj, cf, rf);
             r[0] = (uint64_t)(uint32_t)ti;
             r[1] = (uint64_t)(uint32_t)tj;
             r[2] = cf ? 1u : 0u;
@@ -1759,7 +1479,6 @@ __global__ __launch_bounds__(256) void rrt_device_ops64(uint32_t op, uint32_t n,
 // p.inv_r_in_lds)
 size_t lds64_bytes(const KParams &p, int mode, int blk = kBlock64) {
     size_t lds = ((size_t)p.stack_depth * blk * sizeof(uint16_t) + 15u) / 16u * 16u;
-    lds += (size_t)RRT_F64_LDS_HIST * blk * sizeof(HRec);  // the history ring
     if (mode != kF64Global)
         lds += (size_t)p.n_nodes * 112u +
                (size_t)p.n_prims * ((mode == kF64LdsWide ? sizeof(Sphere64) : sizeof(float4)) +
@@ -1778,9 +1497,9 @@ size_t f64_lds_min_bytes(uint32_t n_nodes, uint32_t n_prims, uint32_t stack_dept
     p.stack_depth = stack_depth;
     p.inv_r_in_lds = 0u;
     p.rec32_in_lds = 0u;
-    // the host's staging rule (rrt_host.cpp scene_bvh): the 512-thread block's layout without the
-    // history ring within 64 KB, whatever block the classes launch
-    return lds64_bytes(p, kF64Lds, 512) - (size_t)RRT_F64_LDS_HIST * 512u * sizeof(HRec);
+    // the host's staging rule (rrt_host.cpp scene_bvh): the 512-thread block's layout within 64 KB,
+    // whatever block the classes launch
+    return lds64_bytes(p, kF64Lds, 512);
 }
 
 namespace {
@@ -1788,16 +1507,6 @@ namespace {
 // rrt_testing_f64_layout: a forced LDS layout (bit 0: widened Sphere64 records, bit 1: the 1/r table,
 // bit 2: the f32 pre-test records beside widened ones), or -1 for the automatic choice below
 std::atomic<int> g_f64_layout{-1};
-
-#ifndef RRT_F64_CLASSES
-#define RRT_F64_CLASSES 1
-#endif
-#ifndef RRT_F64_WIDE_SPHERES
-#define RRT_F64_WIDE_SPHERES 1
-#endif
-#ifndef RRT_F64_PREFER_F32REC
-#define RRT_F64_PREFER_F32REC 0
-#endif
 
 }  // namespace
 
@@ -1809,7 +1518,7 @@ LaunchPlan plan_launch_f64(const KParams &p) {
     pl.f64 = 1u;
     if (p.bvh_width != 2 || p.prim_motion || p.stack_depth > (uint32_t)kMaxStackDepth || p.n_nodes > 65535u)
         return pl;  // the host builds a 16-bit-stack BVH2 for book-1 scenes
-    const int cls = RRT_F64_CLASSES && !p.specular ? kF64Diffuse : RRT_F64_CLASSES && !p.image_tex ? kF64Untextured : kF64Full;
+    const int cls = !p.specular ? kF64Diffuse : !p.image_tex ? kF64Untextured : kF64Full;
     const int B = blk64(cls);
     KParams q = p;
     q.rec32_in_lds = 0u;
@@ -1826,15 +1535,13 @@ LaunchPlan plan_launch_f64(const KParams &p) {
             // the widened sphere records and the 1/r table join the staged scene while the block stays
             // within the LDS it may declare (lds_budget64)
             // (widened records before the 1/r table: a sphere test reads a record, a hit reads 1/r)
-            if (RRT_F64_WIDE_SPHERES && !(RRT_F64_PREFER_F32REC && p.sphere32)) {
-                // with the pre-test: the f32 records staged too, or read from global memory (L1 / L2)
-                for (const uint32_t rec32 : {p.sphere32 && RRT_F64_SPHERE32 ? 1u : 0u, 0u}) {
-                    for (const uint32_t inv_r : {1u, 0u}) {
-                        if (mode >= 0) break;
-                        q.rec32_in_lds = rec32;
-                        q.inv_r_in_lds = inv_r;
-                        if (lds64_bytes(q, kF64LdsWide, B) <= lds_budget64(B)) mode = kF64LdsWide;
-                    }
+            // with the pre-test: the f32 records staged too, or read from global memory (L1 / L2)
+            for (const uint32_t rec32 : {p.sphere32 && RRT_F64_SPHERE32 ? 1u : 0u, 0u}) {
+                for (const uint32_t inv_r : {1u, 0u}) {
+                    if (mode >= 0) break;
+                    q.rec32_in_lds = rec32;
+                    q.inv_r_in_lds = inv_r;
+                    if (lds64_bytes(q, kF64LdsWide, B) <= lds_budget64(B)) mode = kF64LdsWide;
                 }
             }
             if (mode < 0) {
@@ -1884,10 +1591,9 @@ hipError_t launch64(const KParams &p, const LaunchPlan &pl, bool count, hipStrea
     if (per_cu < 1) per_cu = 1;
     const uint32_t want = (q.n_units + B - 1) / B;
     uint32_t blocks = std::max<uint32_t>(std::min<uint32_t>(want, (uint32_t)per_cu * q.n_cus), kQueues);
-    if (RRT_F64_B2F) {  // every lane needs a history slot
-        if (!q.hist || q.hist_lanes < kQueues * (uint32_t)B) return hipErrorInvalidValue;
-        blocks = std::min<uint32_t>(blocks, q.hist_lanes / (uint32_t)B);
-    }
+    // every lane needs a history slot
+    if (!q.hist || q.hist_lanes < kQueues * (uint32_t)B) return hipErrorInvalidValue;
+    blocks = std::min<uint32_t>(blocks, q.hist_lanes / (uint32_t)B);
     e = hipMemsetAsync(q.unit_counter, 0, kQueues * 32u * sizeof(uint32_t), stream);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(kernel, dim3(blocks), dim3(B), lds, stream, q);
@@ -1922,9 +1628,6 @@ hipError_t launch_render_pass_f64(const KParams &p, bool count, hipStream_t stre
 
 void set_f64_layout(int layout) { g_f64_layout.store(layout < 0 ? -1 : layout & 7); }
 
-// Passes of the sequential-sum schedule: the first holds the prefix chunk (chunk 0) and up to
-// pass_chunks tail chunks, each later one up to pass_chunks tail chunks; after a pass its tail samples
-// are folded into accum64 in order.
 hipError_t launch_sqrt64_check(unsigned long long *d_out, hipStream_t stream) {
     hipLaunchKernelGGL(rrt_sqrt64_check, dim3(8192), dim3(256), 0, stream, d_out);
     return hipGetLastError();
@@ -1960,6 +1663,9 @@ hipError_t launch_device_ops64(uint32_t op, uint32_t n, const double *d_in, uint
     return hipGetLastError();
 }
 
+// Passes of the sequential-sum schedule: the first holds the prefix chunk (chunk 0) and up to
+// pass_chunks tail chunks, each later one up to pass_chunks tail chunks; after a pass its tail samples
+// are folded into accum64 in order.
 hipError_t launch_render_f64_seq(const KParams &p, bool count, hipStream_t stream) {
     const uint32_t n_tail = p.n_chunks > 0 ? p.n_chunks - 1u : 0u, m = std::max(1u, p.pass_chunks);
     const uint32_t n_pixels = p.tile_rows * p.width;

@@ -615,10 +615,7 @@ uint32_t max_leaf_global() { return (uint32_t)std::max(1.0, env_or("RRT_MAX_LEAF
 // the material and the face only, so the host forms them once, in the same correctly rounded f32
 // operations in the same order (no contraction: volatile stores round each step), into the
 // dielectric's unused albedo slots: a = (1 / eta, r0(1 / eta), r0(eta), fuzz). The f64 kernel
-// ignores them. RRT_DIEL_HOST=0: the kernel divides (A/B).
-#ifndef RRT_DIEL_HOST
-#define RRT_DIEL_HOST 1
-#endif
+// ignores them.
 void dielectric_consts(float eta, float &inv_eta, float &r0_front, float &r0_back) {
     auto r0sq = [](float ri) {
         volatile float num = 1.0f - ri, den = 1.0f + ri;
@@ -636,9 +633,6 @@ void dielectric_consts(float eta, float &inv_eta, float &r0_front, float &r0_bac
 // (a plain Lambertian's or a metal's albedo): pr = max component clamped to [0.05, 0.95], then the
 // f32 quotient the kernel would form. Only the f32 book-1 kernel reads it (b.y); the f64 kernel and
 // book-2 materials keep b.y's own meaning.
-#ifndef RRT_PR_HOST
-#define RRT_PR_HOST 1
-#endif
 // An albedo as the f64 kernel's attenuation history may hold it: any NaN becomes the quiet NaN, so
 // no albedo carries the signalling-NaN patterns that tag texel bytes there (its value is NaN either
 // way: BOOKS propagates NaN whatever its payload).
@@ -993,9 +987,6 @@ size_t seq_budget(int device) {
     if (std::getenv("RRT_PARTIAL_MB")) return partial_budget();
     return std::min((size_t)8192 << 20, std::max(device_free_bytes(device) / 2, (size_t)64 << 20));
 }
-#ifndef RRT_F64_SEQ
-#define RRT_F64_SEQ 1
-#endif
 #ifndef RRT_F64_TAIL_DIV
 #define RRT_F64_TAIL_DIV 4
 #endif
@@ -1044,7 +1035,7 @@ int fill_params(RrtScene *s, const RrtTile *t, float *d_accum, rrt::KParams &p) 
     const uint32_t tail = S - p.n_big * p.chunk;
     p.n_chunks = S ? p.n_big + (tail + p.chunk_small - 1u) / p.chunk_small : 0u;
     p.seq = 0u;
-    if (s->f64 && RRT_F64_SEQ && S) {
+    if (s->f64 && S) {
         // The f64 books path sums each pixel's samples in camera.rs:72-76's order: one prefix chunk
         // of S - T samples (summed in the lane from 0), then T tail samples in chunks of K/8 whose
         // radiances are kept one by one and folded in after the pass. T = S/4 in whole tail chunks
@@ -1321,11 +1312,11 @@ static int32_t scene_create(const RrtCamera *cam, const RrtSphere *spheres, uint
             mats[i].a.z = canonical_albedo(mats[i].a.z);
         }
         mats[i].b = make_int4((int)m.kind, ref_bits, (int)m._pad[0], (int)m._pad[1]);
-        if ((m.kind == RRT_MAT_LAMBERTIAN || m.kind == RRT_MAT_METAL) && RRT_PR_HOST) {
+        if (m.kind == RRT_MAT_LAMBERTIAN || m.kind == RRT_MAT_METAL) {
             const float inv_pr = rr_inv_pr(m.albedo_fuzz[0], m.albedo_fuzz[1], m.albedo_fuzz[2]);
             std::memcpy(&mats[i].b.y, &inv_pr, sizeof(float));  // ref_idx: a dielectric's only
         }
-        if (m.kind == RRT_MAT_DIELECTRIC && RRT_DIEL_HOST) {  // the f32 kernel's per-material constants
+        if (m.kind == RRT_MAT_DIELECTRIC) {  // the f32 kernel's per-material constants
             float inv_eta, r0_front, r0_back;
             dielectric_consts(m.ref_idx, inv_eta, r0_front, r0_back);
             mats[i].a = make_float4(inv_eta, r0_front, r0_back, fuzz);
@@ -1381,12 +1372,9 @@ static int32_t scene_create(const RrtCamera *cam, const RrtSphere *spheres, uint
         if (book2 || f64) {  // the f64 kernel forms r * r in f64 (sphere.rs:29)
             prim_cr[i] = make_float4(sp.center_radius[0], sp.center_radius[1], sp.center_radius[2], r);
         } else {  // book-1 kernel layout: r * r in the record (one multiply less per test), 1 / r in b.w
-#ifndef RRT_INVR_HOST
-#define RRT_INVR_HOST 1
-#endif
             const volatile float r2 = r * r;  // f32, rounded once like the kernel's r * r
-            const volatile float inv_r = 1.0f / r;  // the kernel's correctly rounded quotient
-            const float bw = RRT_INVR_HOST ? (float)inv_r : r;
+            const volatile float inv_r = 1.0f / r;  // the correctly rounded quotient of sphere.rs:48
+            const float bw = inv_r;
             prim_cr[i] = make_float4(sp.center_radius[0], sp.center_radius[1], sp.center_radius[2], r2);
             std::memcpy(&prim_mtl[i].b.w, &bw, sizeof(float));
         }
@@ -1394,7 +1382,7 @@ static int32_t scene_create(const RrtCamera *cam, const RrtSphere *spheres, uint
             const float *m = motion + 4 * (size_t)order[i];
             prim_motion[i] = make_float4(m[0], m[1], m[2], 0.0f);
         }
-        if (book2 && RRT_INVR_HOST) {  // books 2 / 3: 1 / r in the motion record's w (xyz: the motion)
+        if (book2) {  // books 2 / 3: 1 / r in the motion record's w (xyz: the motion)
             const volatile float inv_r = 1.0f / r;
             prim_motion[i].w = inv_r;
         }

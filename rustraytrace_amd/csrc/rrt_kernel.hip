@@ -95,12 +95,7 @@ __device__ __forceinline__ V3 cross(V3 a, V3 b) {  // vec3.rs cross
 // 2^126) (exhaustive on the device: rrt_testing_recip_check, tests/test_gpu_recip.py); for s = +-0,
 // +-inf and NaN the step's residual is NaN and the estimate, exact there, is kept. The kernel takes
 // it for reciprocals of square roots of |v|^2 (>= 2^-75) and of probabilities in [0.05, 0.95].
-// RRT_RCP=0: the IEEE division.
-#ifndef RRT_RCP
-#define RRT_RCP 1
-#endif
 __device__ __forceinline__ float recip_rn(float s) {
-    if (!RRT_RCP) return 1.0f / s;
     const float r = __builtin_amdgcn_rcpf(s);
     const float e = __builtin_fmaf(-s, r, 1.0f);
     return e == e ? __builtin_fmaf(e, r, r) : r;
@@ -110,9 +105,8 @@ __device__ __forceinline__ float recip_rn(float s) {
 // between its one-ulp neighbours by the sign of the fma remainders — the compiler's own correction
 // without the rescaling of small arguments (exhaustive on the device, rrt_testing_recip_check). The
 // kernel takes it where the argument is provably 0 or >= 2^-46: |p|^2 of the rejection loop, and
-// 1 - c^2 / |1 - |perp|^2| (0 or multiples of 2^-24 near 1). RRT_RCP=0: the library sqrt.
+// 1 - c^2 / |1 - |perp|^2| (0 or multiples of 2^-24 near 1).
 __device__ __forceinline__ float sqrt_rn_big(float x) {
-    if (!RRT_RCP) return __builtin_sqrtf(x);
     float s = __builtin_amdgcn_sqrtf(x);
     const float sm = __uint_as_float(__float_as_uint(s) - 1u), sp = __uint_as_float(__float_as_uint(s) + 1u);
     const float rm = __builtin_fmaf(-sm, s, x), rp = __builtin_fmaf(-sp, s, x);
@@ -124,7 +118,6 @@ __device__ __forceinline__ float sqrt_rn_big(float x) {
 // nonzero |x| < 2^-96 (a wave-uniform branch to the library sequence; sqrt_rn_big differs from the
 // IEEE root only on positive and negative arguments below 2^-96 other than +-0, per the device check)
 __device__ __forceinline__ float sqrt_rn(float x) {
-    if (!RRT_RCP) return __builtin_sqrtf(x);
     if (__ballot(__builtin_fabsf(x) < 0x1.0p-96f && x != 0.0f) == 0) return sqrt_rn_big(x);
     return __builtin_sqrtf(x);
 }
@@ -177,20 +170,11 @@ __device__ __forceinline__ float reflectance_r0(float cosine, float r0) {
 }
 
 // A dielectric hit's (ri, r0): from the material record the host formed (rrt_host.cpp
-// dielectric_consts: a = (1 / eta, r0(1 / eta), r0(eta)), the same f32 operations), or divided here
-#ifndef RRT_DIEL_HOST
-#define RRT_DIEL_HOST 1
-#endif
+// dielectric_consts: a = (1 / eta, r0(1 / eta), r0(eta)), in the reference's f32 operations)
 __device__ __forceinline__ void dielectric_ri_r0(const GMaterial &m, bool front, float &ri, float &r0) {
     const float eta = __int_as_float(m.b.y);
-    if (RRT_DIEL_HOST) {
-        ri = front ? m.a.x : eta;
-        r0 = front ? m.a.y : m.a.z;
-    } else {
-        ri = front ? (1.0f / eta) : eta;
-        const float q = (1.0f - ri) / (1.0f + ri);
-        r0 = q * q;
-    }
+    ri = front ? m.a.x : eta;
+    r0 = front ? m.a.y : m.a.z;
 }
 
 // ---- deterministic f32 acos / atan2 for sphere UV (sphere.rs:46-52) -------------------------
@@ -203,12 +187,8 @@ constexpr float kPiO4 = 0.78539816339744830962f;
 // against the IEEE expansion's ten. It returns the IEEE quotient for x = 0 and every f32 x in
 // [2^-100, 8] (exhaustive for both divisors, tests/test_div_const.py; over all positive floats the
 // only differences lie below 3.1e-32, where the remainder underflows); phi is 0 or >= 2^-22
-// (atan2 + pi), theta 0 or >= 3e-4 (acos). RRT_DIV_CONST=0: the IEEE division.
-#ifndef RRT_DIV_CONST
-#define RRT_DIV_CONST 1
-#endif
+// (atan2 + pi), theta 0 or >= 3e-4 (acos).
 __device__ __forceinline__ float div_by_const(float x, float c) {
-    if (!RRT_DIV_CONST) return x / c;
     const float rc = 1.0f / c;  // folded: RN(1/c)
     const float q = x * rc;
     return __builtin_fmaf(__builtin_fmaf(-q, c, x), rc, q);
@@ -303,17 +283,13 @@ __device__ __forceinline__ float clamp_inv(float v) { return __builtin_fmaxf(__b
 // estimate is flushed) has |1 / s| > 2^126 and takes +-2^64 by its sign. Equal to
 // clamp_inv(1.0f / s) for every s with |s| < 2^126, NaN included (rrt_testing_recip_check).
 __device__ __forceinline__ float clamped_slope(float s) {
-    if (!RRT_RCP) return clamp_inv(1.0f / s);
     return __builtin_fabsf(s) < 0x1.0p-126f ? __builtin_copysignf(0x1.0p64f, s) : clamp_inv(recip_rn(s));
 }
 
 // kLdsNodes: ox, oy, oz are the byte offsets of the (entry, exit) plane pairs in an LDS GNode; for
-// the 32-B f16 nodes read from global memory (RRT_F16_ORDERED) ox packs the rotations that put each
+// the 32-B f16 nodes read from global memory (kOrd16) ox packs the rotations that put each
 // axis's lo | hi << 16 word in (entry, exit) order — 16 when 1/d_a < 0, else 0 — at bits 0, 5 and 10
 // (v_alignbit reads the low 5 bits of its shift), so the traversal holds one register, not three.
-#ifndef RRT_F16_ORDERED
-#define RRT_F16_ORDERED 1
-#endif
 // the ordered f16 slab for kernel classes up to this one (book 1 <= 0, book 2 1-3; all by default):
 // C5 +7.9 %, bouncing spheres +4.7 %, final_scene +3.0 % same-box (profiles/r6_f16_ordered_ab.log).
 // The media class (3: final_scene) forms ra per leaf batch to hold the rotation register within its
@@ -387,12 +363,7 @@ __device__ __forceinline__ RayK ray_consts(V3 o, V3 d) {
 // 3.4e38). The remainders are exact from |q0| >= 2^-38 on (a * q0 is a multiple of 2^-148 there);
 // the bound leaves eight binades above that. With it the result is the IEEE quotient (the oracle's)
 // for every f32 n, bit for bit: exhaustive over n on the device for 48 divisors, rrt_testing_div_check,
-// tests/test_gpu_device_ops.py. Since the guard, kFast no longer changes anything: div_by_a<true> and
-// div_by_a<false> are the same function (before it, <false> tested ra == 0 and <true> took no
-// branch). The parameter stays because exact_root / test_range pass their kFastDiv through and the
-// lazy roots (RRT_LAZY_ROOT) still tell the two apart; the device checks run both instantiations,
-// which now can only agree.
-template <bool kFast = false>
+// tests/test_gpu_device_ops.py.
 __device__ __forceinline__ float div_by_a(float n, const RayK &rk) {
     const float q0 = n * rk.ra;
     const float m = __builtin_fabsf(q0);
@@ -594,27 +565,9 @@ __device__ __forceinline__ void test_prims(const PR &prim_cr, int first, int cou
     }
 }
 
-// ---- lazy exact roots (book-1 scenes, the non-counting kernel) -------------------------------------
-// The closest hit is the lexicographic minimum of (exact root, test order) over the valid roots
-// (sphere.rs:24-51 against the running closest, strictly less: the first of equal roots wins), and
-// box tests only prune (conservative boxes, BoxSlack). So the leaf loop need not form every root
-// exactly: it brackets each root in an interval from the hardware square root and the per-ray
-// reciprocal and keeps the best candidate's interval [lo, closest]. A candidate whose interval lies
-// wholly below lo replaces the best, one wholly at or above `closest` is rejected (both decisions
-// are the exact ones), and only an overlap (nearly equal roots, or a root near tmin) is resolved on
-// the exact roots, as the exact loop forms them. The box tests prune with the upper bound `closest`,
-// so they visit a superset of the exact walk's nodes in the same order, whose extra primitives the
-// exact comparison would reject anyway. The exact root of the winner is formed once, when the query
-// ends (lazy_finish): every decision and every t equal the exact loop's, bit for bit (the GPU parity
-// suite with the whole C2 frame passed with it on). Measured and left off (round 6, same-box): C2
-// -0.1 %, C5 -0.8 %, C4 -4 % — VALU instructions per ray fell only 0.4 % (the winner's exact root at
-// the query's end and the interval bookkeeping cost about what the sparse root code did) and SALU
-// rose 4.5 % (profiles/r6_lazy_root_ab.log). RRT_LAZY_ROOT=1 turns it on.
-#ifndef RRT_LAZY_ROOT
-#define RRT_LAZY_ROOT 0
-#endif
-// The exact root the leaf loop forms (test_range's arithmetic): the near root if above tmin, else the far.
-template <bool kFastDiv, class PR>
+// The exact root the leaf loop forms (test_range's arithmetic): the near root if above tmin, else the
+// far. The test-only rrt_device_ops kernel compares it with the leaf loop's decision.
+template <class PR>
 __device__ __forceinline__ float exact_root(const PR &prim_cr, int i, V3 o, V3 d, const RayK &rk) {
     const float4 cr = prim_cr.at(i);
     const V3 oc = v3(cr.x - o.x, cr.y - o.y, cr.z - o.z);
@@ -622,49 +575,19 @@ __device__ __forceinline__ float exact_root(const PR &prim_cr, int i, V3 o, V3 d
     const float c = dot(oc, oc) - (PR::kR2 ? cr.w : cr.w * cr.w);
     const float disc = __builtin_fmaf(h, h, -(rk.a * c));
     const float sq = sqrt_rn(disc);
-    float root = div_by_a<kFastDiv>(h - sq, rk);
-    if (!(0.001f < root)) root = div_by_a<kFastDiv>(h + sq, rk);
+    float root = div_by_a(h - sq, rk);
+    if (!(0.001f < root)) root = div_by_a(h + sq, rk);
     return root;
 }
-// An ambiguous candidate i (its interval overlaps the best's, or its root may lie at tmin): the exact
-// loop's decision on the exact roots. hit_prim < 0 or lo == closest: the best is exact already.
-template <bool kFastDiv, class PR>
-__device__ __forceinline__ void lazy_resolve(const PR &prim_cr, int i, V3 o, V3 d, const RayK &rk, float &lo,
-                                             float &closest, int &hit_prim) {
-    const float rc = exact_root<kFastDiv>(prim_cr, i, o, d, rk);
-    if (0.001f < rc && rc < closest) {  // else rc >= closest >= the best's root: rejected
-        const float rb = (hit_prim >= 0 && lo != closest) ? exact_root<kFastDiv>(prim_cr, hit_prim, o, d, rk) : closest;
-        if (rc < rb) {
-            hit_prim = i;
-            lo = closest = rc;
-        } else {
-            lo = closest = rb;
-        }
-    }
-}
-// The query's exact t: the winner's exact root when its interval is still open.
-template <class PR>
-__device__ __forceinline__ void lazy_finish(const PR &prim_cr, V3 o, V3 d, const RayK &rk, float &lo, float &closest,
-                                            int hit_prim) {
-    if (hit_prim >= 0 && lo != closest) {
-        closest = rk.ra != 0.0f ? exact_root<true>(prim_cr, hit_prim, o, d, rk) : exact_root<false>(prim_cr, hit_prim, o, d, rk);
-        lo = closest;
-    }
-}
-
 // Leaf primitives [first, first + count): the hit leaf children of one node visit, which are
 // adjacent in primitive order (sibling leaves split one range, rrt_host.cpp flatten2).
 // `skip` is the primitive the ray is leaving (exit_skip): it can never be accepted, so it is left
 // out of the loop — a lane whose range holds it runs one iteration less — but the counting
 // variant still counts it as a test, like the oracle's hit_prim (tests count every primitive of
-// the range). kFastDiv: with the lazy roots, every active lane's |d|^2 is in the range of the per-ray
-// reciprocal (the caller checked it wave-wide); otherwise always set: div_by_a guards itself.
-template <bool kCount, bool kFastDiv, class PR>
+// the range).
+template <bool kCount, class PR>
 __device__ __forceinline__ void test_range(const PR &prim_cr, int first, int count, V3 o, V3 d, const RayK &rk,
-                                           int skip, float &closest, int &hit_prim, float &lo, Counters &cnt) {
-    // lazy roots: book-1 spheres in the non-counting kernel (the counting twin keeps the exact
-    // walk, so its test counts stay the oracle's), the per-ray reciprocal in range (kFastDiv)
-    constexpr bool kLazy = RRT_LAZY_ROOT && !kCount && kFastDiv && PR::kR2 && !PR::kHasQuads;
+                                           int skip, float &closest, int &hit_prim, Counters &cnt) {
     const float a = rk.a;
     const bool trim = (uint32_t)(skip - first) < (uint32_t)count;
     const int n = count - (trim ? 1 : 0);
@@ -709,45 +632,12 @@ __device__ __forceinline__ void test_range(const PR &prim_cr, int first, int cou
         // when no lane takes it.
         if (disc < 0.0f) continue;
         if constexpr (RRT_PHASE_TIMING == 3) cnt.d2 += 1;
-        if constexpr (kLazy) {
-            // Interval of the exact near root r0 = RN(RN(h - RN(sqrt disc)) / a): the hardware root s
-            // is within 2 ulp of sqrt(disc) (the exhaustive device check of sqrt_rn_big), so
-            // |RN(h - s) - RN(h - sq)| <= 2^-21 s + 2u |h - s| and, with ra within 2u of 1/a,
-            // |q - r0| <= 9u ra (|h - s| + s) <= 9u ra (|h| + 2s) (u = 2^-24); e = 2^-20 ra (|h| + 2s)
-            // bounds it with 1.7x to spare, which also covers the roundings of e and of q -+ e
-            // (e >= 16u |q|). Decided here: the near root surely above tmin, and surely below the
-            // best's interval (accept) or surely at or above it (reject). Anything else — a root near
-            // tmin, a ray inside the sphere (the far root), overlapping intervals, disc below 2^-96 (the
-            // square root's scaled range), an overflow or a NaN — is resolved on the exact roots.
-            const float sv = __builtin_amdgcn_sqrtf(disc);
-            const float q = (h - sv) * rk.ra;
-            const float e = __builtin_fmaf(sv, 2.0f, __builtin_fabsf(h)) * (rk.ra * 0x1.0p-20f);
-            const float l = q - e, u = q + e;
-            const bool valid = (disc >= 0x1.0p-96f) & (l > 0.001f);
-            const bool acc = valid & (u < lo);
-            const bool rej = valid & (l >= closest);
-            lo = acc ? l : lo;
-            closest = acc ? u : closest;
-            hit_prim = acc ? i : hit_prim;
-            if (!(acc | rej)) lazy_resolve<kFastDiv>(prim_cr, i, o, d, rk, lo, closest, hit_prim);
-        } else {
-            const float sq = sqrt_rn(disc);
-            float root = div_by_a<kFastDiv>(h - sq, rk);
-            if (!(0.001f < root)) root = div_by_a<kFastDiv>(h + sq, rk);
-            if (RRT_LAZY_ROOT && !kCount && PR::kR2 && !PR::kHasQuads) {
-                // exact root against a best that may be an interval (an earlier lazy batch)
-                if (0.001f < root && root < closest) {
-                    if (root < lo) {
-                        lo = closest = root;
-                        hit_prim = i;
-                    } else {
-                        lazy_resolve<kFastDiv>(prim_cr, i, o, d, rk, lo, closest, hit_prim);
-                    }
-                }
-            } else if (0.001f < root && root < closest) {
-                closest = root;
-                hit_prim = i;
-            }
+        const float sq = sqrt_rn(disc);
+        float root = div_by_a(h - sq, rk);
+        if (!(0.001f < root)) root = div_by_a(h + sq, rk);
+        if (0.001f < root && root < closest) {
+            closest = root;
+            hit_prim = i;
         }
     }
 }
@@ -756,16 +646,14 @@ __device__ __forceinline__ void test_range(const PR &prim_cr, int first, int cou
 // Resumable BVH traversal: one call = one node. The state lives in registers (+ the LDS stack)
 // so a wave can leave the traversal loop while some lanes are still mid-tree.
 struct Trav {
-    float closest;  // the best hit's root, or (lazy roots) an upper bound of it
+    float closest;  // the best hit's root
     int hit_prim;
     int node;
     int sp;
-    float lo;       // lazy roots: a lower bound of the best hit's root (== closest when exact)
 };
 
 __device__ __forceinline__ void trav_begin(Trav &t) {
     t.closest = __builtin_inff();  // camera.rs:187 Interval(0.001, INFINITY)
-    t.lo = __builtin_inff();
     t.hit_prim = -1;
     t.node = 0;
     t.sp = 0;
@@ -881,16 +769,7 @@ __device__ __forceinline__ void trav_leaves(const PR &prims, Leaves lv, V3 o, V3
     RayK rk = rk_;
     if (!kHoldRa) rk.ra = refine_ra(rk.a);
     const int first = (int)(lv & kLinkFirstMask), count = (int)(lv >> kLinkCountShift);
-    // div_by_a guards itself (an out-of-range a has ra = 0 and takes the IEEE division there), so only
-    // the lazy roots' interval arithmetic (RRT_LAZY_ROOT builds) still needs the wave-wide range test
-    // and the kFastDiv = false loop; the shipped build has the one loop
-    if constexpr (RRT_LAZY_ROOT) {
-        if (__ballot(rk.ra == 0.0f) != 0) {
-            test_range<kCount, false>(prims, first, count, o, d, rk, skip, t.closest, t.hit_prim, t.lo, cnt);
-            return;
-        }
-    }
-    test_range<kCount, true>(prims, first, count, o, d, rk, skip, t.closest, t.hit_prim, t.lo, cnt);
+    test_range<kCount>(prims, first, count, o, d, rk, skip, t.closest, t.hit_prim, cnt);
 }
 
 // BVH4 step: test the 4 child boxes, test leaf children's spheres in place, then descend
@@ -1089,12 +968,6 @@ __device__ __forceinline__ float rrt_cosf(float xx) {
     return sign < 0.0f ? -y : y;
 }
 
-#ifndef RRT_NOISE_UNROLL
-#define RRT_NOISE_UNROLL 1
-#endif
-#ifndef RRT_PERLIN_LDS_PTR
-#define RRT_PERLIN_LDS_PTR 1
-#endif
 #ifndef RRT_DEBUG_NOISE_FIXED  // debug builds only: a constant-time stand-in (prices the texture; wrong images)
 #define RRT_DEBUG_NOISE_FIXED 0
 #endif
@@ -1117,7 +990,7 @@ __device__ __forceinline__ V3 gradient(Q randvec, uint32_t idx) { return v3(rand
 
 // Perlin::noise (perlin.rs:25-48) + perlin_interp (perlin.rs:79-98), operation order kept:
 // the (i*uu + (1-i)*(1-uu)) factors are exactly uu or 1-uu for i in {0,1}.
-template <class PP, bool kUnroll = RRT_NOISE_UNROLL>
+template <class PP>
 __device__ __forceinline__ float perlin_noise(PP pt, V3 p) {
     const float fx = __builtin_floorf(p.x), fy = __builtin_floorf(p.y), fz = __builtin_floorf(p.z);
     const float u = p.x - fx, v = p.y - fy, w = p.z - fz;
@@ -1130,20 +1003,7 @@ __device__ __forceinline__ float perlin_noise(PP pt, V3 p) {
     const uint32_t py0 = (pt->perm[(uint32_t)j & 255u] >> 8) & 0xffu, py1 = (pt->perm[(uint32_t)(j + 1) & 255u] >> 8) & 0xffu;
     const uint32_t pz0 = (pt->perm[(uint32_t)k & 255u] >> 16) & 0xffu, pz1 = (pt->perm[(uint32_t)(k + 1) & 255u] >> 16) & 0xffu;
     float accum = 0.0f;
-    if constexpr (!kUnroll) {
-#pragma unroll 1
-        for (int corner = 0; corner < 8; ++corner) {  // (di, dj, dk) in perlin_interp's nested order
-            const int di = corner >> 2, dj = (corner >> 1) & 1, dk = corner & 1;
-            const V3 c = gradient(pt->randvec, (di ? px1 : px0) ^ (dj ? py1 : py0) ^ (dk ? pz1 : pz0));
-            const float wx = u - (float)di, wy = v - (float)dj, wz = w - (float)dk;
-            const float fi = di ? uu : 1.0f - uu;
-            const float fj = dj ? vv : 1.0f - vv;
-            const float fk = dk ? ww : 1.0f - ww;
-            accum = accum + fi * fj * fk * dot(c, v3(wx, wy, wz));
-        }
-        return accum;
-    }
-    // RRT_NOISE_UNROLL: the corner loop unrolled. The corner offsets are constants (u - 0 = u and
+    // The corner loop, unrolled by face. The corner offsets are constants (u - 0 = u and
     // 0 * uu + 1 * (1 - uu) = 1 - uu exactly, as above), each (fi * fj) is formed once per pair
     // (perlin_interp multiplies left to right: (fi * fj) * fk * dot is the loop's product), and a
     // face's four gradient reads are independent loads in flight together instead of one round
@@ -1170,22 +1030,15 @@ __device__ __forceinline__ float perlin_noise(PP pt, V3 p) {
 // NoiseTexture::value (texture.rs:122-126): 0.5 * (1 + sin(scale * p.z + 10 * turb(p, 7))),
 // turb (perlin.rs:50-62): |sum of weight * noise(p * 2^i)|, weight halving. The octave loop stays
 // rolled: unrolled (56 corner evaluations) it swamps the megakernel's register allocation.
-#ifndef RRT_NOISE_CALL
-#define RRT_NOISE_CALL 1
-#endif
-#if RRT_NOISE_CALL
-#define RRT_NOISE_FN __attribute__((noinline))
-#else
-#define RRT_NOISE_FN __forceinline__
-#endif
-template <class PP, bool kUnroll = RRT_NOISE_UNROLL>
-__device__ RRT_NOISE_FN float noise_value(PP pt, float scale, V3 p) {
+// A real call (noinline): the megakernel's register allocation does not carry the noise code.
+template <class PP>
+__device__ __attribute__((noinline)) float noise_value(PP pt, float scale, V3 p) {
     if (RRT_DEBUG_NOISE_FIXED) return 0.5f + p.z * 0x1.0p-30f;
     float accum = 0.0f, weight = 1.0f;
     V3 tp = p;
 #pragma unroll 1
     for (int o = 0; o < 7; ++o) {
-        accum = accum + weight * perlin_noise<PP, kUnroll>(pt, tp);
+        accum = accum + weight * perlin_noise(pt, tp);
         weight = weight * 0.5f;
         tp = muls(tp, 2.0f);
     }
@@ -1195,87 +1048,8 @@ __device__ RRT_NOISE_FN float noise_value(PP pt, float scale, V3 p) {
 // Noise texture `table` at p: a wave-uniform branch on where the block keeps the tables.
 template <class KP>
 __device__ __forceinline__ float noise_at(const KP &P, const GPerlin *perlin, int table, float scale, V3 p) {
-    if (RRT_PERLIN_LDS_PTR && P.perlin_in_lds) return noise_value((LdsPerlin)(perlin + table), scale, p);
+    if (P.perlin_in_lds) return noise_value((LdsPerlin)(perlin + table), scale, p);
     return noise_value(perlin + table, scale, p);
-}
-
-#ifndef RRT_NOISE_WAVE
-#define RRT_NOISE_WAVE 0
-#endif
-// x from lane (this lane + n) of the same 16-lane row (DPP row_shl:n; 0 past the row's end)
-template <int n>
-__device__ __forceinline__ float row_shl(float x) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x100 | n, 0xf, 0xf, true));
-}
-
-// NoiseTexture::value for the lanes in `want` (a ballot), evaluated by the whole wave together (every lane
-// of the wave must be active). In final_scene a shading pass that meets the noise texture has 3.3
-// such lanes on average, and the per-lane evaluation costs the wave all 7 x 8 corners for them.
-// Here a pass takes up to 8 noise lanes: lane 8k + o (o < 7) evaluates octave o of the k-th one,
-// perlin_noise at p * 2^o (turb's doublings are exact, so that is the value its loop reaches) times
-// weight 2^-o (its halvings, exact too); lane 8k folds the seven terms in octave order by DPP row
-// shifts, ((0 + t0) + t1) + ... + t6, turb's own left fold; the noise lane pulls the sum back and
-// finishes value(). The same operations on the same values: bit-identical to noise_value.
-#ifndef RRT_NOISE_WAVE_MAX  // noise lanes per shading pass the wave evaluates together (above: per lane)
-#define RRT_NOISE_WAVE_MAX 64
-#endif
-#ifndef RRT_NOISE_WAVE_CALL
-#define RRT_NOISE_WAVE_CALL 0
-#endif
-#ifndef RRT_WAVE_NOISE_UNROLL  // the corner loop inside the wave pass (rolled: fewer live registers)
-#define RRT_WAVE_NOISE_UNROLL 0
-#endif
-#if RRT_NOISE_WAVE_CALL
-#define RRT_WAVE_NOISE_FN __attribute__((noinline))
-#else
-#define RRT_WAVE_NOISE_FN __forceinline__
-#endif
-template <class KP>
-__device__ RRT_WAVE_NOISE_FN float wave_noise(const KP &P, const GPerlin *perlin, uint64_t want, V3 p, int table,
-                                              float scale) {
-    const uint32_t lane = __lane_id();
-    const uint32_t slot = lane >> 3, oct = lane & 7u;
-    const uint64_t below = (1ull << lane) - 1ull;
-    float g = 0.0f;
-    for (uint64_t need = want; need != 0;) {
-        // this pass's source lanes: the first (up to) 8 noise lanes, slot k = the k-th
-        uint64_t rest = need;
-        int src = 0;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const int b = rest ? __builtin_ctzll(rest) : 0;
-            src = slot == (uint32_t)k ? b : src;
-            rest &= rest - 1ull;
-        }
-        const uint64_t pass = need ^ rest;
-        const uint32_t n_slots = (uint32_t)__popcll(pass);
-        const float qx = __int_as_float(__builtin_amdgcn_ds_bpermute(src << 2, __float_as_int(p.x)));
-        const float qy = __int_as_float(__builtin_amdgcn_ds_bpermute(src << 2, __float_as_int(p.y)));
-        const float qz = __int_as_float(__builtin_amdgcn_ds_bpermute(src << 2, __float_as_int(p.z)));
-        const int tbl = __builtin_amdgcn_ds_bpermute(src << 2, table);
-        float term = 0.0f;
-        if (oct < 7u && slot < n_slots) {
-            const float up = __int_as_float((int)(127u + oct) << 23);    // 2^oct
-            const float down = __int_as_float((int)(127u - oct) << 23);  // 2^-oct
-            const V3 tp = v3(qx * up, qy * up, qz * up);
-            const float nz = (RRT_PERLIN_LDS_PTR && P.perlin_in_lds)
-                                 ? perlin_noise<LdsPerlin, RRT_WAVE_NOISE_UNROLL>((LdsPerlin)(perlin + tbl), tp)
-                                 : perlin_noise<const GPerlin *, RRT_WAVE_NOISE_UNROLL>(perlin + tbl, tp);
-            term = down * nz;
-        }
-        float acc = 0.0f + term;
-        acc = acc + row_shl<1>(term);
-        acc = acc + row_shl<2>(term);
-        acc = acc + row_shl<3>(term);
-        acc = acc + row_shl<4>(term);
-        acc = acc + row_shl<5>(term);
-        acc = acc + row_shl<6>(term);
-        const uint32_t rank = (uint32_t)__popcll(pass & below);
-        const float turb_acc = __int_as_float(__builtin_amdgcn_ds_bpermute((int)(rank << 5), __float_as_int(acc)));
-        if ((pass >> lane) & 1ull) g = 0.5f * (1.0f + rrt_sinf(scale * p.z + 10.0f * __builtin_fabsf(turb_acc)));
-        need = rest;
-    }
-    return g;
 }
 
 // CheckerTexture::value (texture.rs:66-77) with solid even/odd colours.
@@ -1304,7 +1078,7 @@ __device__ __forceinline__ V3 texel(const KParams &P, int tex, float u, float v)
 // path ending at the sky or an emitter adds T*Le to `sum`.
 template <int kBook2, bool kNoise, typename C, class PR>
 __device__ __forceinline__ bool shade(const KParams &P, const PR &prims, const GMaterial *mtl, PathState &ps,
-                                      float t, int prim, V3 &sum, C &cnt, float gnoise, bool gnoise_ok) {
+                                      float t, int prim, V3 &sum, C &cnt) {
     if constexpr (RRT_PHASE_TIMING == 4) {
         cnt.d0 += wave_slot();
         cnt.d1 += 1;
@@ -1342,14 +1116,9 @@ __device__ __forceinline__ bool shade(const KParams &P, const PR &prims, const G
             outward = v3(qn.x, qn.y, qn.z);
         }
     } else {
-#ifndef RRT_INVR_HOST
-#define RRT_INVR_HOST 1
-#endif
         // 1 / r from the host: book 1 in the material record's b.w, books 2 / 3 in the motion
         // record's w (a sphere's motion is xyz only)
-        const float inv_r = !RRT_INVR_HOST ? 1.0f / (PR::kR2 ? __int_as_float(mtl[prim].b.w) : cr.w)
-                            : PR::kR2      ? __int_as_float(mtl[prim].b.w)
-                                           : qn.w;
+        const float inv_r = PR::kR2 ? __int_as_float(mtl[prim].b.w) : qn.w;
         outward = v3((p.x - cr.x) * inv_r, (p.y - cr.y) * inv_r, (p.z - cr.z) * inv_r);
     }
     const bool front = dot(ps.d, outward) < 0.0f;
@@ -1387,8 +1156,7 @@ __device__ __forceinline__ bool shade(const KParams &P, const PR &prims, const G
                 cnt.d0 += wave_slot();
                 cnt.d1 += 1;
             }
-            // evaluated by the wave before shading (RRT_NOISE_WAVE: gnoise_ok, wave-uniform), or here
-            const float g = gnoise_ok ? gnoise : noise_at(P, prims.perlin, m.b.z, m.a.w, p);
+            const float g = noise_at(P, prims.perlin, m.b.z, m.a.w, p);
             att = v3(g, g, g);
         } else {
             att = v3(m.a.x, m.a.y, m.a.z);
@@ -1427,11 +1195,8 @@ __device__ __forceinline__ bool shade(const KParams &P, const PR &prims, const G
         // 1 / pr is a material constant the host formed in the same operations (rrt_host.cpp
         // rr_inv_pr, in the record's unused b.y); a dielectric's att is (1, 1, 1): pr = 0.95. (The
         // textured classes divide: the select costs C4's 80-VGPR class a spill.)
-#ifndef RRT_PR_HOST
-#define RRT_PR_HOST 1
-#endif
         float inv_pr;
-        if (RRT_PR_HOST && kBook2 == kBook1Untextured) inv_pr = kind == 2 ? 1.0f / 0.95f : __int_as_float(m.b.y);
+        if (kBook2 == kBook1Untextured) inv_pr = kind == 2 ? 1.0f / 0.95f : __int_as_float(m.b.y);
         else inv_pr = recip_rn(pr);
         ps.T = muls(mul(ps.T, att), inv_pr);
     } else {
@@ -1526,7 +1291,7 @@ __device__ __forceinline__ V3 lights_random(const KParams &P, V3 o, RngState &rn
 // mixture 0.5 * lights + 0.5 * material and weight by scattering_pdf / (pdf * rr).
 template <bool kNoise, typename C, class PR>
 __device__ __forceinline__ bool shade_b3(const KParams &P, const PR &prims, const GMaterial *mtl, PathState &ps,
-                                         float t, int prim, V3 &sum, C &cnt, float gnoise, bool gnoise_ok) {
+                                         float t, int prim, V3 &sum, C &cnt) {
     if (prim < 0) {
         sum = add(sum, mul(ps.T, v3(P.background[0], P.background[1], P.background[2])));
         return true;
@@ -1546,7 +1311,7 @@ __device__ __forceinline__ bool shade_b3(const KParams &P, const PR &prims, cons
             outward = v3(qn.x, qn.y, qn.z);
         }
     } else {
-        const float inv_r = RRT_INVR_HOST ? qn.w : 1.0f / cr.w;  // 1 / r from the host (shade)
+        const float inv_r = qn.w;  // 1 / r from the host (shade)
         outward = v3((p.x - cr.x) * inv_r, (p.y - cr.y) * inv_r, (p.z - cr.z) * inv_r);
     }
     const bool front = (cr.w < 0.0f && (int)(-cr.w) - 1 >= (int)prims.n_quads) ? true : dot(ps.d, outward) < 0.0f;
@@ -1603,7 +1368,7 @@ __device__ __forceinline__ bool shade_b3(const KParams &P, const PR &prims, cons
         att = checker_even(m.a.w, p) ? v3(m.a.x, m.a.y, m.a.z)
                                      : v3(__int_as_float(m.b.y), __int_as_float(m.b.z), __int_as_float(m.b.w));
     } else if (kNoise && kind == 6) {
-        const float g = gnoise_ok ? gnoise : noise_at(P, prims.perlin, m.b.z, m.a.w, p);
+        const float g = noise_at(P, prims.perlin, m.b.z, m.a.w, p);
         att = v3(g, g, g);
     } else {
         att = v3(m.a.x, m.a.y, m.a.z);
@@ -1653,29 +1418,12 @@ __device__ __forceinline__ bool shade_b3(const KParams &P, const PR &prims, cons
     return false;
 }
 
-
-#ifndef RRT_LEAN_8W
-#define RRT_LEAN_8W 0
-#endif
-#ifndef RRT_PKEY_HOLD  // with RRT_LEAN_8W: 0 = the 8-wave class forms the pixel key per path
-#define RRT_PKEY_HOLD 0
-#endif
-#ifndef RRT_SUM_LDS  // with RRT_LEAN_8W: 1 = the 8-wave class keeps its radiance sum in LDS
-#define RRT_SUM_LDS 1
-#endif
-// This lane's radiance-sum slot in LDS (12-B stride: lanes fall on distinct banks).
-template <int kBlk>
-__device__ __forceinline__ V3 *sum_slot() {
-    __shared__ V3 slots[kBlk];
-    return &slots[threadIdx.x];
-}
-
 // The shading step of the scene class: book 3's MIS integrator or the book-1/2 one.
 template <int kBook2, bool kNoise, typename C, class PR>
 __device__ __forceinline__ bool shade_any(const KParams &P, const PR &prims, const GMaterial *mtl, PathState &ps,
-                                          float t, int prim, V3 &sum, C &cnt, float gnoise, bool gnoise_ok) {
-    if constexpr (kBook2 == 4) return shade_b3<kNoise>(P, prims, mtl, ps, t, prim, sum, cnt, gnoise, gnoise_ok);
-    else return shade<kBook2, kNoise>(P, prims, mtl, ps, t, prim, sum, cnt, gnoise, gnoise_ok);
+                                          float t, int prim, V3 &sum, C &cnt) {
+    if constexpr (kBook2 == 4) return shade_b3<kNoise>(P, prims, mtl, ps, t, prim, sum, cnt);
+    else return shade<kBook2, kNoise>(P, prims, mtl, ps, t, prim, sum, cnt);
 }
 
 // Debug builds only (-DRRT_TRACE_X/Y/S): one path's segments, printed at shading.
@@ -1753,16 +1501,8 @@ __device__ __forceinline__ void render_body(const KParams &P) {
     bool q_open = true;   // wave-uniform: the queue may still hold units
     // lane's unit: global pixel (x | y << 16), next sample s, end of its sample chunk s_hi
     uint32_t xy = 0, s = 0, s_hi = 0;
-    // The 8-wave class (C2's, 1024-thread blocks, 64 VGPRs) frees registers: its pixel key is formed
-    // again at each path start instead of held, and its radiance sum lives in LDS (RRT_LEAN_8W).
-    constexpr bool kLean = RRT_LEAN_8W && kLds && kBook2 == kBook1Untextured && kBlk >= 1024;
     uint64_t pkey = 0;  // the unit's pixel key (one splitmix64 per unit instead of per path)
-    V3 sum_reg = v3(0.0f, 0.0f, 0.0f);
-    V3 *sum_ptr;
-    if constexpr (kLean && RRT_SUM_LDS) sum_ptr = sum_slot<kBlk>();
-    else sum_ptr = &sum_reg;
-    V3 &sum = *sum_ptr;
-    sum = v3(0.0f, 0.0f, 0.0f);
+    V3 sum = v3(0.0f, 0.0f, 0.0f);
     PathState ps;
     Trav tr;
     // A lane is in the tree while tr.node >= 0 (or, inside the BVH2 loop, while it holds postponed
@@ -1841,9 +1581,8 @@ __device__ __forceinline__ void render_body(const KParams &P) {
                         s = Q.sample_begin + chunk_first(Q, chunk);
                         s_hi = min(s + (chunk < Q.n_big ? Q.chunk : Q.chunk_small), Q.sample_end);
                         sum = v3(0.0f, 0.0f, 0.0f);
-                        const uint64_t key = pixel_key(Q, x, y);
-                        if constexpr (!(kLean && !RRT_PKEY_HOLD)) pkey = key;
-                        ps.rng = path_rng_k(key, s);
+                        pkey = pixel_key(Q, x, y);
+                        ps.rng = path_rng_k(pkey, s);
                         camera_ray<kBook2 == 4>(P, x, y, s, ps, cnt);
                         need_ray = 1;
                         has = 1;
@@ -1879,7 +1618,7 @@ __device__ __forceinline__ void render_body(const KParams &P) {
         RayK rk;
         // the ordered f16 slab for scenes read from global memory (C5, bouncing spheres); the media
         // class keeps the min/max slab (RRT_F16_ORDERED_MAX_CLASS)
-        constexpr bool kOrd16 = RRT_F16_ORDERED && !kLds && !kWide && kBook2 <= RRT_F16_ORDERED_MAX_CLASS;
+        constexpr bool kOrd16 = !kLds && !kWide && kBook2 <= RRT_F16_ORDERED_MAX_CLASS;
         constexpr bool kHoldRa = !(kOrd16 && kBook2 == 3);
         if (tr.node >= 0) rk = ray_consts<!kOrd16, kHoldRa>(ps.o, ps.d);
         const Prims<kBook2> pr{prims, motion, ps.time, P.quads, P.media, P.n_quads, rng_key(ps.rng) ^ ((uint64_t)ps.k << 32), perlin};
@@ -1944,16 +1683,10 @@ __device__ __forceinline__ void render_body(const KParams &P) {
             ph1 += t - tp;
             tp = t;
         }
-        // Noise kernels evaluate the shading lanes' noise textures with the whole wave between the
-        // closest-hit query and shade (RRT_NOISE_WAVE): the shading block splits around it. Every
-        // lane is active there (the loop leaves on a wave-uniform ballot).
-        constexpr bool kWaveNoise = kNoise && RRT_NOISE_WAVE;
         const bool shading = has && !need_ray && tr.node < 0;
         if (shading) {
             need_ray = 1;
             const Prims<kBook2> spr{prims, motion, ps.time, P.quads, P.media, P.n_quads, rng_key(ps.rng) ^ ((uint64_t)ps.k << 32), perlin};
-            if constexpr (RRT_LAZY_ROOT && !kCount && Prims<kBook2>::kR2 && !kWide)
-                lazy_finish(spr, ps.o, ps.d, rk, tr.lo, tr.closest, tr.hit_prim);  // rk: the lane was in the tree this iteration
             if constexpr (Prims<kBook2>::kHasMedia) {
                 // The unbounded media (a fog around the whole scene; rrt_host.cpp unbounded_media):
                 // not in the tree, tested here against the closest hit of the walk, every lane whose
@@ -1971,42 +1704,15 @@ __device__ __forceinline__ void render_body(const KParams &P) {
                     }
                 }
             }
-            if constexpr (!kWaveNoise) {
-                trace_segment(xy, s, ps, tr.closest, tr.hit_prim);
-                seg_done = shade_any<kBook2, kNoise>(P, spr, mtl, ps, tr.closest, tr.hit_prim, sum, cnt, 0.0f, false) ? 1u : 0u;
-            }
-        }
-        if constexpr (kWaveNoise) {
-            bool want = false;
-            int tbl = 0;
-            float scale = 0.0f;
-            if (shading && tr.hit_prim >= 0) {
-                const GMaterial &hm = mtl[tr.hit_prim];
-                want = hm.b.x == 6;
-                tbl = hm.b.z;
-                scale = hm.a.w;
-            }
-            const V3 ph = v3(__builtin_fmaf(ps.d.x, tr.closest, ps.o.x), __builtin_fmaf(ps.d.y, tr.closest, ps.o.y),
-                             __builtin_fmaf(ps.d.z, tr.closest, ps.o.z));  // shade's Ray::at
-            // one wave pass for up to RRT_NOISE_WAVE_MAX noise lanes; more are evaluated per lane
-            // in shade (perlin_spheres: ~35 per shading pass; final_scene: 3.3)
-            const uint64_t nm = __ballot(want);
-            const bool gnoise_ok = nm != 0 && (uint32_t)__popcll(nm) <= RRT_NOISE_WAVE_MAX;
-            float gnoise = 0.0f;
-            if (gnoise_ok) gnoise = wave_noise(P, perlin, nm, ph, tbl, scale);
-            if (shading) {
-                const Prims<kBook2> spr{prims, motion, ps.time, P.quads, P.media, P.n_quads, rng_key(ps.rng) ^ ((uint64_t)ps.k << 32), perlin};
-                trace_segment(xy, s, ps, tr.closest, tr.hit_prim);
-                seg_done = shade_any<kBook2, kNoise>(P, spr, mtl, ps, tr.closest, tr.hit_prim, sum, cnt, gnoise, gnoise_ok) ? 1u : 0u;
-            }
+            trace_segment(xy, s, ps, tr.closest, tr.hit_prim);
+            seg_done = shade_any<kBook2, kNoise>(P, spr, mtl, ps, tr.closest, tr.hit_prim, sum, cnt) ? 1u : 0u;
         }
         w_paths += (uint32_t)__popcll(__ballot(seg_done));
         if (seg_done) {  // pixel_color += ray_color(..) (camera.rs:73-76): already in `sum`
             ++s;
             const uint32_t x = xy & 0xffffu, y = xy >> 16;
             if (s < s_hi) {
-                if constexpr (kLean && !RRT_PKEY_HOLD) ps.rng = path_rng_k(pixel_key(*kernarg_params(), x, y), s);
-                else ps.rng = path_rng_k(pkey, s);
+                ps.rng = path_rng_k(pkey, s);
                 if constexpr (RRT_PHASE_TIMING == 7) {
                     cnt.d0 += wave_slot();
                     cnt.d1 += 1;
@@ -2432,8 +2138,9 @@ __device__ __forceinline__ void st3(uint32_t *p, V3 v) {
     p[1] = __float_as_uint(v.y);
     p[2] = __float_as_uint(v.z);
 }
-// one sphere as a one-record Prims: exact_root in both divisions, and the leaf loop's decision
-// against `closest` (test_range, both divisions)
+// one sphere as a one-record Prims: exact_root, and the leaf loop's decision against `closest`
+// (test_range). Each result fills two columns: the kernel once had two division variants, which the
+// guard in div_by_a made one function; the columns stay so that the op's layout does.
 template <int kBook2>
 __device__ __forceinline__ void sphere_ops(float4 rec, V3 o, V3 d, const RayK &rk, float closest, uint32_t *r) {
     const float4 still = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
@@ -2441,23 +2148,13 @@ __device__ __forceinline__ void sphere_ops(float4 rec, V3 o, V3 d, const RayK &r
     pr.cr = &rec;
     pr.mo = &still;
     pr.time = 0.0f;
-    const bool fast = rk.ra != 0.0f;
-    const float slow_root = exact_root<false>(pr, 0, o, d, rk);
-    r[0] = __float_as_uint(slow_root);
-    r[1] = __float_as_uint(fast ? exact_root<true>(pr, 0, o, d, rk) : slow_root);
+    r[0] = r[1] = __float_as_uint(exact_root(pr, 0, o, d, rk));
     Counters cnt{};
-    float t = closest, lo = closest;
+    float t = closest;
     int prim = -1;
-    test_range<false, false>(pr, 0, 1, o, d, rk, -1, t, prim, lo, cnt);
-    r[2] = prim == 0 ? 1u : 0u;
-    r[3] = __float_as_uint(t);
-    if (fast) {
-        t = lo = closest;
-        prim = -1;
-        test_range<false, true>(pr, 0, 1, o, d, rk, -1, t, prim, lo, cnt);
-    }
-    r[4] = prim == 0 ? 1u : 0u;
-    r[5] = __float_as_uint(t);
+    test_range<false>(pr, 0, 1, o, d, rk, -1, t, prim, cnt);
+    r[2] = r[4] = prim == 0 ? 1u : 0u;
+    r[3] = r[5] = __float_as_uint(t);
 }
 __global__ __launch_bounds__(256) void rrt_device_ops(uint32_t op, uint32_t n, uint32_t cin, uint32_t cout,
                                                       const float *__restrict__ in, uint32_t *__restrict__ out,
@@ -2482,9 +2179,7 @@ __global__ __launch_bounds__(256) void rrt_device_ops(uint32_t op, uint32_t n, u
             RayK rk{};
             rk.a = x[1];
             rk.ra = refine_ra(rk.a);
-            const float slow = div_by_a<false>(x[0], rk);
-            r[0] = __float_as_uint(slow);
-            r[1] = __float_as_uint(rk.ra != 0.0f ? div_by_a<true>(x[0], rk) : slow);
+            r[0] = r[1] = __float_as_uint(div_by_a(x[0], rk));  // two columns: once two variants
             r[2] = __float_as_uint(x[0] / x[1]);
             r[3] = __float_as_uint(rk.ra);
             break;
@@ -2502,14 +2197,11 @@ __global__ __launch_bounds__(256) void rrt_device_ops(uint32_t op, uint32_t n, u
             const GPerlin *g = reinterpret_cast<const GPerlin *>(aux);
             const GPerlin *staged = &lds_table;
             const LdsPerlin l = (LdsPerlin)staged;
-            r[0] = __float_as_uint(perlin_noise<const GPerlin *, true>(g, p));
-            r[1] = __float_as_uint(noise_value<const GPerlin *, true>(g, scale, p));
-            r[2] = __float_as_uint(perlin_noise<const GPerlin *, false>(g, p));
-            r[3] = __float_as_uint(noise_value<const GPerlin *, false>(g, scale, p));
-            r[4] = __float_as_uint(perlin_noise<LdsPerlin, true>(l, p));
-            r[5] = __float_as_uint(noise_value<LdsPerlin, true>(l, scale, p));
-            r[6] = __float_as_uint(perlin_noise<LdsPerlin, false>(l, p));
-            r[7] = __float_as_uint(noise_value<LdsPerlin, false>(l, scale, p));
+            // columns 2-3 and 6-7 held the rolled corner loop's results: now the one loop's
+            r[0] = r[2] = __float_as_uint(perlin_noise(g, p));
+            r[1] = r[3] = __float_as_uint(noise_value(g, scale, p));
+            r[4] = r[6] = __float_as_uint(perlin_noise(l, p));
+            r[5] = r[7] = __float_as_uint(noise_value(l, scale, p));
             break;
         }
         case RRT_OP_VEC: {
@@ -2558,18 +2250,17 @@ __global__ __launch_bounds__(256) void rrt_div_check(const float *__restrict__ a
         for (uint64_t k = first; k < (1ull << 32); k += stride) {
             const float n = __uint_as_float((uint32_t)k);
             const float q = n / rk.a;
-            const float r = div_by_a<false>(n, rk);
+            const float r = div_by_a(n, rk);
             ++pairs;
             if (rk.ra == 0.0f) {
                 if (!same(r, q)) ++c2;
                 continue;
             }
-            const float rf = div_by_a<true>(n, rk);
             const float an = __builtin_fabsf(n), aq = __builtin_fabsf(q);
-            const bool differ = !same(r, q) || !same(rf, q);
+            const bool differ = !same(r, q);
             if (an >= 0x1.0p-103f && an < __builtin_inff() && aq >= 0x1.0p-126f && aq < __builtin_inff() && differ) ++c0;
-            if (accepted(r) != accepted(q) || accepted(rf) != accepted(q) || (accepted(q) && differ)) ++c1;
-            if (aq < 0x1.0p-126f && (__float_as_uint(r) != __float_as_uint(q) || __float_as_uint(rf) != __float_as_uint(q))) ++c3;
+            if (accepted(r) != accepted(q) || (accepted(q) && differ)) ++c1;
+            if (aq < 0x1.0p-126f && __float_as_uint(r) != __float_as_uint(q)) ++c3;
         }
     }
     // x = 0 (k = 0) and every f32 x in [2^-100, 8]

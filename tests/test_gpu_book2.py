@@ -86,9 +86,9 @@ def test_cornell_smoke_and_final_scene_larger_frames_kbvh():
 
 
 def test_noise_texture_scenes_larger_frames_kbvh():
-    # Perlin noise (perlin_spheres: ~35 noise lanes per shading pass, evaluated per lane; simple_light
-    # with its quad light) and final_scene's marble sphere (3.3 noise lanes per pass, evaluated by
-    # the whole wave: rrt_kernel.hip wave_noise): both paths occur in each frame, bit-exact
+    # Perlin noise, evaluated per lane in shade (rrt_kernel.hip noise_at): perlin_spheres (~35 noise
+    # lanes per shading pass), simple_light with its quad light, and final_scene's marble sphere
+    # (3.3 noise lanes per pass), bit-exact
     for scene, kw in ((4, dict(image_width=192, samples_per_pixel=8, max_depth=20)),
                       (6, dict(image_width=192, samples_per_pixel=8, max_depth=20)),
                       (9, dict(image_width=96, samples_per_pixel=8, max_depth=20))):
