@@ -218,6 +218,19 @@ typedef struct RrtOverrides {
  * RrtSceneExt data, not RRT_FLAG_BOOK3 (RRT_E_INVALID otherwise). Float entries return the f64 sums
  * rounded to f32; rrt_hip_render_f64 / rrt_render_tile_f64_async return them unrounded. */
 #define RRT_FLAG_F64 0x8u
+/* Scene creation builds the BVH on the device instead of the host (additive; RRT_ABI_VERSION is
+ * unchanged): a binned SAH builder (16 bins per axis, all three axes; rrt_bvh_binned.h) that emits
+ * the node formats the render kernels already read, so the kernels are the same. Accepted by
+ * rrt_scene_create / _ex and every one-shot entry (rrt_hip_render, _ex, _f64, _rgb8, _rgb8_ex,
+ * _f64_rgb8). The composition is scene creation's own: the LDS shape (leaves of up to 3, node price 2,
+ * or 1.5 with RRT_FLAG_F64) kept if it fits, else the global shape (single-primitive leaves, 32-B
+ * nodes), else the fallbacks of the host path; RRT_MAX_LEAF, RRT_MAX_LEAF_GLOBAL, RRT_SAH_CT and
+ * RRT_F64_SAH_CT_LDS apply, RRT_BVH_SPLIT is ignored, RRT_BVH_WIDTH=4 is refused (RRT_E_INVALID).
+ * The tree differs from the host builder's (other splits), never a primitive's result; its bytes
+ * are those of rrt_build_bvh_binned for the kept shape. A tree of at most one primitive is the
+ * root-leaf form and is written by the host builder. RrtBvhInfo.max_leaf_param then reports the kept
+ * shape's leaf size. Without the flag nothing changes. */
+#define RRT_FLAG_DEVICE_BVH 0x10u
 
 /* ---- error codes ------------------------------------------------------------------ */
 #define RRT_OK 0
@@ -374,6 +387,23 @@ int32_t rrt_build_bvh(const RrtSphere *spheres, uint32_t n_spheres, uint32_t wid
 int32_t rrt_build_bvh_ex(const RrtSphere *spheres, uint32_t n_spheres, const RrtSceneExt *ext, uint32_t width,
                          uint32_t max_leaf, void *nodes_out, size_t nodes_cap, uint32_t *prim_order_out,
                          RrtBvhInfo *info);
+
+/* Host-only: the tree RRT_FLAG_DEVICE_BVH builds for one shape and node format, by the sequential
+ * host twin of the device builder (same header, same bytes): leaves of up to max_leaf (1..7)
+ * primitives, the SAH node price node_cost, node_stride 80 (GNode) or 32 (GNodeH). Same primitive
+ * order, unbounded media and sizing protocol (nodes_cap 0 sizes) as rrt_build_bvh_ex. It is the
+ * specification the device builder is held to, and the tree a checker passes to a BVH-walking
+ * reference. */
+int32_t rrt_build_bvh_binned(const RrtSphere *spheres, uint32_t n_spheres, const RrtSceneExt *ext, uint32_t max_leaf,
+                             double node_cost, uint32_t node_stride, void *nodes_out, size_t nodes_cap,
+                             uint32_t *prim_order_out, RrtBvhInfo *info);
+
+/* The node array and leaf order the created scene holds, whichever builder made them: nodes_out of
+ * at least rrt_scene_bvh_info's node_bytes, prim_order_out of n_spheres + n_quads + n_media entries
+ * (the last n_unbounded outside the tree). Copies from the scene's device. Also the only view of the
+ * tree of an RRT_FLAG_F64 scene, or of a scene whose book-2 materials tip the LDS fit, which
+ * rrt_build_bvh_ex cannot reproduce. */
+int32_t rrt_scene_read_bvh(RrtScene *scene, void *nodes_out, size_t nodes_cap, uint32_t *prim_order_out);
 
 /* ---- host-side callers of the boundary ------------------------------------------------ */
 

@@ -50,6 +50,9 @@ mod imp {
     pub const RRT_FLAG_QUIET: u32 = 0x2;
     /// The books path's f64 arithmetic (RRT_FLAG_F64): checked against `--backend cpu` output.
     pub const RRT_FLAG_F64: u32 = 0x8;
+    /// Scene creation builds the BVH on the device (RRT_FLAG_DEVICE_BVH); same kernels, same output
+    /// contract, another tree.
+    pub const RRT_FLAG_DEVICE_BVH: u32 = 0x10;
     /// ABI this shim was written against (RRT_ABI_VERSION).
     pub const RRT_ABI_VERSION: u32 = 11;
 
@@ -118,6 +121,7 @@ mod imp {
     /// (rrt_hip_render_rgb8 + the library's P3 writer: identical bytes, 3 B/pixel over PCIe).
     /// RRT_BOOKS_F64=1 renders with the books path's f64 arithmetic (rrt_hip_render_f64) and
     /// prints the bytes color.rs's write_color gives for the f64 sums.
+    /// RRT_DEVICE_BVH=1 adds RRT_FLAG_DEVICE_BVH to whichever entry runs.
     fn render(camera: CameraUniform, spheres: &[SphereGpu], materials: &[MaterialGpu]) -> Result<(), String> {
         let abi = unsafe { rrt_hip_abi_version() };
         if abi != RRT_ABI_VERSION {
@@ -128,12 +132,13 @@ mod imp {
         let total_spp = camera.params_f[3].max(1.0) as u32; // cuda/mod.rs:384
         let n_gpus = gpus()?;
         let pixels = width as usize * height as usize;
+        let bvh_flag = if std::env::var("RRT_DEVICE_BVH").map(|v| v == "1").unwrap_or(false) { RRT_FLAG_DEVICE_BVH } else { 0 };
         if std::env::var("RRT_BOOKS_F64").map(|v| v == "1").unwrap_or(false) {
             let mut accum = vec![0.0f64; pixels * 4];
             check(unsafe {
                 rrt_hip_render_f64(&camera, spheres.as_ptr(), spheres.len() as u32,
                                    materials.as_ptr(), materials.len() as u32,
-                                   std::ptr::null(), 0, total_spp, n_gpus, RRT_FLAG_F64, accum.as_mut_ptr())
+                                   std::ptr::null(), 0, total_spp, n_gpus, RRT_FLAG_F64 | bvh_flag, accum.as_mut_ptr())
             })?;
             let mut rgb8 = vec![0u8; pixels * 3];
             check(unsafe { rrt_quantize_accum_books_f64(width, height, accum.as_ptr(), total_spp, rgb8.as_mut_ptr()) })?;
@@ -147,7 +152,7 @@ mod imp {
             check(unsafe {
                 rrt_hip_render_rgb8(&camera, spheres.as_ptr(), spheres.len() as u32,
                                     materials.as_ptr(), materials.len() as u32,
-                                    std::ptr::null(), 0, total_spp, n_gpus, 0, rgb8.as_mut_ptr())
+                                    std::ptr::null(), 0, total_spp, n_gpus, bvh_flag, rgb8.as_mut_ptr())
             })?;
             let stdout = b"-\0";
             return check(unsafe {
@@ -159,7 +164,7 @@ mod imp {
             rrt_hip_render_ex(&camera, spheres.as_ptr(), spheres.len() as u32,
                               materials.as_ptr(), materials.len() as u32,
                               std::ptr::null(), 0, std::ptr::null(),
-                              total_spp, n_gpus, 0, accum.as_mut_ptr())
+                              total_spp, n_gpus, bvh_flag, accum.as_mut_ptr())
         })?;
         write_ppm_from_accum(width as usize, height as usize, &accum, total_spp)
     }

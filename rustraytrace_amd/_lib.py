@@ -39,6 +39,7 @@ FLAG_RAY_TIME = 0x1
 FLAG_QUIET = 0x2
 FLAG_BOOK3 = 0x4
 FLAG_F64 = 0x8  # the books path's f64 arithmetic (include/rrt_hip.h RRT_FLAG_F64)
+FLAG_DEVICE_BVH = 0x10  # scene creation builds the BVH on the device (RRT_FLAG_DEVICE_BVH)
 
 # Every symbol include/rrt_hip.h declares (checked by tests/test_abi.py).
 EXPORTED_SYMBOLS = (
@@ -71,6 +72,8 @@ EXPORTED_SYMBOLS = (
     "rrt_hip_render_ex",
     "rrt_scene_create_ex",
     "rrt_build_bvh_ex",
+    "rrt_build_bvh_binned",
+    "rrt_scene_read_bvh",
     "rrt_build_next_week_scene",
     "rrt_build_rest_of_your_life_scene",
     "rrt_flatten_scene",
@@ -338,6 +341,8 @@ def load() -> ctypes.CDLL:
         "rrt_hip_render_ex": (c_int32, [P, P, c_uint32, P, c_uint32, P, c_uint32, P, c_uint32, c_uint32, c_uint32, P]),
         "rrt_scene_create_ex": (c_int32, [P, P, c_uint32, P, c_uint32, P, c_uint32, P, c_uint32, c_int32, P]),
         "rrt_build_bvh_ex": (c_int32, [P, c_uint32, P, c_uint32, c_uint32, P, c_size_t, P, P]),
+        "rrt_build_bvh_binned": (c_int32, [P, c_uint32, P, c_uint32, c_double, c_uint32, P, c_size_t, P, P]),
+        "rrt_scene_read_bvh": (c_int32, [P, P, c_size_t, P]),
         "rrt_build_next_week_scene": (c_int32, [c_int32, P, c_uint64, P]),
         "rrt_build_rest_of_your_life_scene": (c_int32, [P, c_uint64, P]),
         "rrt_flatten_scene": (c_int32, [P, c_uint32, P, c_uint32, c_uint32, P]),

@@ -1,0 +1,503 @@
+// rrt_bvh_build.hip — the scene's BVH built on the device (RRT_FLAG_DEVICE_BVH): the binned SAH
+// builder of rrt_bvh_binned.h, level-synchronous and top-down. Every floating-point decision is the
+// header's; this file only moves data: it fills the header's Bin records with integer atomics (adds
+// for counts, 64-bit min / max on the order-preserving keys of the f64 bits), runs the header's
+// decide() one lane per task, numbers nodes and next-level tasks by exclusive scans over the level's
+// tasks, and partitions stably by a prefix sum of the "goes left" flags. The kernel boundary is the
+// only synchronisation between workgroups: no spin waits, no look-back, no cooperative launch. The
+// host reads one small LevelState per level (the next level's task count) with a blocking copy.
+//
+// Per level: bins_init, bin, decide, scan (one block), emit, flags (reduce), scan (one block),
+// scatter. After the last level pack writes GNode / GNodeH records from the raw f64 nodes.
+// Tasks of a level are ordered left to right by position, so the flags' prefix at a task's start
+// is the exclusive scan of the tasks' left counts, and node ids come out breadth-first.
+#include "rrt_bvh_binned.h"
+#include "rrt_internal.h"
+
+#include <algorithm>
+#include <vector>
+
+namespace rrt {
+
+using namespace bvhb;
+
+namespace {
+
+constexpr int kBlk = 256;
+constexpr int kScanBlk = 1024;
+constexpr uint32_t kBinWords = 13;                       // u64 words of a Bin: n, k[12]
+constexpr uint32_t kTaskWords = 3 * kBins * kBinWords;   // of a task's bins
+static_assert(sizeof(Bin) == kBinWords * 8, "Bin is 13 packed u64");
+static_assert(sizeof(Task) == 112 && sizeof(RawNode) == 112, "layouts");
+static_assert(kLeafShift == kLinkCountShift, "leaf link encoding");
+
+struct LevelState {
+    uint32_t n_next;     // tasks of the next level
+    uint32_t n_nodes;    // internal nodes so far
+    uint32_t node_base;  // n_nodes before this level
+    uint32_t n_split;    // tasks of this level that split
+    uint32_t n_leaves;
+    uint32_t max_leaf;
+    uint32_t error;      // a scatter destination left its task's range (never expected)
+    uint32_t _pad;
+};
+
+typedef unsigned long long u64;
+
+__device__ __forceinline__ u64 word_identity(uint32_t w) {  // w = word of a Bin
+    return w == 0 ? 0ull : (key_is_min((int)w - 1) ? kKeyPosInf : kKeyNegInf);
+}
+// Folds one primitive into a task's bins (words: LDS or global, kTaskWords of them).
+__device__ __forceinline__ void bin_prim(u64 *words, const Task &t, uint32_t i, const Box6 &box) {
+    const Bounds bo = bounds_of(box);
+    for (int axis = 0; axis < 3; ++axis) {
+        const int b = task_bin(t, axis, i, box);
+        if (b < 0) continue;
+        u64 *w = words + (uint32_t)(axis * kBins + b) * kBinWords;
+        atomicAdd(w, 1ull);
+        for (int j = 0; j < 12; ++j) {
+            if (key_is_min(j)) atomicMin(w + 1 + j, (u64)bo.k[j]);
+            else atomicMax(w + 1 + j, (u64)bo.k[j]);
+        }
+    }
+}
+
+// The root task's bounds: LDS reduction per block, then 12 atomics per block.
+__global__ __launch_bounds__(kBlk) void k_root_bounds(uint32_t n, const uint32_t *order, const Box6 *boxes, Task *root) {
+    __shared__ u64 s[12];
+    if (threadIdx.x < 12) s[threadIdx.x] = key_is_min((int)threadIdx.x) ? kKeyPosInf : kKeyNegInf;
+    __syncthreads();
+    const uint32_t i = blockIdx.x * kBlk + threadIdx.x;
+    if (i < n) {
+        const Bounds bo = bounds_of(boxes[order[i]]);
+        for (int j = 0; j < 12; ++j) {
+            if (key_is_min(j)) atomicMin(&s[j], (u64)bo.k[j]);
+            else atomicMax(&s[j], (u64)bo.k[j]);
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < 12) {
+        u64 *dst = (u64 *)&root->b.k[threadIdx.x];
+        if (key_is_min((int)threadIdx.x)) atomicMin(dst, s[threadIdx.x]);
+        else atomicMax(dst, s[threadIdx.x]);
+    }
+}
+__global__ void k_root_finish(Task *root) { task_finish(*root); }
+
+__global__ __launch_bounds__(kBlk) void k_bins_init(uint64_t n_words, u64 *words) {
+    const uint64_t i = (uint64_t)blockIdx.x * kBlk + threadIdx.x;
+    if (i < n_words) words[i] = word_identity((uint32_t)(i % kBinWords));
+}
+
+// Each primitive of a live task bins into its task. A block whose 256 positions lie in one task
+// (every block of the top levels) reduces in LDS first and issues one atomic per touched bin word.
+__global__ __launch_bounds__(kBlk) void k_bin(uint32_t n, const uint32_t *order, const int32_t *ptask, const Task *tasks,
+                                              const Box6 *boxes, Bin *bins) {
+    __shared__ u64 s[kTaskWords];
+    const uint32_t i0 = blockIdx.x * kBlk;
+    if (i0 >= n) return;
+    const uint32_t i = i0 + threadIdx.x;
+    const uint32_t last = min(i0 + (uint32_t)kBlk - 1u, n - 1u);
+    const int32_t tf = ptask[i0];
+    const bool uniform = tf >= 0 && tf == ptask[last];  // tasks are contiguous ranges
+    if (uniform) {
+        for (uint32_t w = threadIdx.x; w < kTaskWords; w += kBlk) s[w] = word_identity(w % kBinWords);
+        __syncthreads();
+        if (i <= last) bin_prim(s, tasks[tf], i, boxes[order[i]]);
+        __syncthreads();
+        u64 *g = (u64 *)(bins + (size_t)tf * (3 * kBins));
+        for (uint32_t w = threadIdx.x; w < kTaskWords; w += kBlk) {
+            const uint32_t k = w % kBinWords;
+            const u64 v = s[w];
+            if (v == word_identity(k)) continue;
+            if (k == 0) atomicAdd(g + w, v);
+            else if (key_is_min((int)k - 1)) atomicMin(g + w, v);
+            else atomicMax(g + w, v);
+        }
+        return;
+    }
+    if (i > last) return;
+    const int32_t t = ptask[i];
+    if (t < 0) return;
+    bin_prim((u64 *)(bins + (size_t)t * (3 * kBins)), tasks[t], i, boxes[order[i]]);
+}
+
+// One lane per task: the header's decide(), and the three scan inputs.
+__global__ __launch_bounds__(64) void k_decide(uint32_t n_tasks, const Task *tasks, const Bin *bins, uint32_t max_leaf,
+                                               double node_cost, Decision *dec, uint32_t *s_node, uint32_t *s_child,
+                                               uint32_t *s_left) {
+    const uint32_t t = blockIdx.x * 64u + threadIdx.x;
+    if (t >= n_tasks) return;
+    const Task tk = tasks[t];
+    const Decision d = decide(tk, bins + (size_t)t * (3 * kBins), max_leaf, node_cost);
+    dec[t] = d;
+    const uint32_t span = tk.hi - tk.lo;
+    s_node[t] = d.split;
+    s_child[t] = d.split ? (d.n_left > 1u ? 1u : 0u) + (span - d.n_left > 1u ? 1u : 0u) : 0u;
+    s_left[t] = d.split ? d.n_left : 0u;
+}
+
+// Exclusive scan, in place, of up to three arrays of n entries by one block; totals[c] = the sum
+// of array c.
+__global__ __launch_bounds__(kScanBlk) void k_excl_scan(uint32_t n, uint32_t *a0, uint32_t *a1, uint32_t *a2,
+                                                        uint32_t *totals) {
+    __shared__ uint32_t s[3][kScanBlk];
+    uint32_t *a[3] = {a0, a1, a2};
+    uint32_t carry[3] = {0u, 0u, 0u};
+    const uint32_t tid = threadIdx.x;
+    for (uint32_t base = 0; base < n; base += kScanBlk) {
+        const uint32_t i = base + tid;
+        uint32_t own[3];
+        for (int c = 0; c < 3; ++c) {
+            own[c] = (a[c] && i < n) ? a[c][i] : 0u;
+            s[c][tid] = own[c];
+        }
+        __syncthreads();
+        for (uint32_t off = 1; off < (uint32_t)kScanBlk; off <<= 1) {
+            uint32_t v[3];
+            for (int c = 0; c < 3; ++c) v[c] = tid >= off ? s[c][tid - off] : 0u;
+            __syncthreads();
+            for (int c = 0; c < 3; ++c) s[c][tid] += v[c];
+            __syncthreads();
+        }
+        for (int c = 0; c < 3; ++c) {
+            if (a[c] && i < n) a[c][i] = carry[c] + s[c][tid] - own[c];
+            carry[c] += s[c][kScanBlk - 1];
+        }
+        __syncthreads();
+    }
+    if (tid == 0)
+        for (int c = 0; c < 3; ++c) totals[c] = carry[c];
+}
+
+// After the task scan: the level's totals into the state (one thread).
+__global__ void k_level_totals(const uint32_t *totals, LevelState *st) {
+    st->node_base = st->n_nodes;
+    st->n_split = totals[0];
+    st->n_nodes += totals[0];
+    st->n_next = totals[1];
+}
+
+// One lane per task: the task's link in its parent, its raw node, its leaf children and the next
+// level's tasks.
+__global__ __launch_bounds__(64) void k_emit(uint32_t n_tasks, const Task *tasks, const Decision *dec, const uint32_t *s_node,
+                                             const uint32_t *s_child, LevelState *st, RawNode *raw, uint32_t raw_cap,
+                                             Task *next, uint32_t next_cap) {
+    const uint32_t t = blockIdx.x * 64u + threadIdx.x;
+    if (t >= n_tasks) return;
+    const Task tk = tasks[t];
+    const uint32_t span = tk.hi - tk.lo;
+    const bool split = dec[t].split != 0;
+    if (!split) {
+        const uint32_t link = tk.lo | (span << kLeafShift);
+        if (tk.slot == kNoSlot) {  // the root is a leaf: child 0 = the leaf, child 1 never hit
+            RawNode r;
+            for (int a = 0; a < 3; ++a) {
+                r.box[0][a] = key_f64(tk.b.k[a]);
+                r.box[0][3 + a] = key_f64(tk.b.k[3 + a]);
+            }
+            never_hit(r.box[1]);
+            r.link[0] = link;
+            r.link[1] = 0u;
+            r._pad[0] = r._pad[1] = 0u;
+            raw[0] = r;
+            st->n_nodes = 1u;
+        } else if ((tk.slot >> 1) < raw_cap) {
+            raw[tk.slot >> 1].link[tk.slot & 1u] = link;
+        }
+        atomicAdd(&st->n_leaves, 1u);
+        atomicMax(&st->max_leaf, span);
+        return;
+    }
+    const uint32_t id = st->node_base + s_node[t];
+    if (id >= raw_cap) {
+        atomicOr(&st->error, 2u);
+        return;
+    }
+    const Decision &d = dec[t];
+    for (int c = 0; c < 2; ++c)
+        for (int a = 0; a < 3; ++a) {
+            raw[id].box[c][a] = key_f64(d.child[c].k[a]);
+            raw[id].box[c][3 + a] = key_f64(d.child[c].k[3 + a]);
+        }
+    raw[id]._pad[0] = raw[id]._pad[1] = 0u;
+    if (tk.slot != kNoSlot && (tk.slot >> 1) < raw_cap) raw[tk.slot >> 1].link[tk.slot & 1u] = id;
+    uint32_t ci = s_child[t];
+    const uint32_t first[2] = {tk.lo, tk.lo + d.n_left}, count[2] = {d.n_left, span - d.n_left};
+    for (int c = 0; c < 2; ++c) {
+        if (count[c] <= 1u) {
+            raw[id].link[c] = first[c] | (count[c] << kLeafShift);
+            atomicAdd(&st->n_leaves, 1u);
+            atomicMax(&st->max_leaf, count[c]);
+            continue;
+        }
+        raw[id].link[c] = 0u;  // set by the child's own level
+        if (ci >= next_cap) {
+            atomicOr(&st->error, 4u);
+            continue;
+        }
+        Task nt;
+        nt.lo = first[c];
+        nt.hi = first[c] + count[c];
+        nt.slot = 2u * id + (uint32_t)c;
+        nt.b = d.child[c];
+        task_finish(nt);
+        next[ci++] = nt;
+    }
+}
+
+__device__ __forceinline__ bool left_flag(uint32_t i, const uint32_t *order, const int32_t *ptask, const Task *tasks,
+                                          const Decision *dec, const Box6 *boxes) {
+    const int32_t t = ptask[i];
+    if (t < 0 || !dec[t].split) return false;
+    return goes_left(tasks[t], dec[t], i, boxes[order[i]]);
+}
+
+// Partition pass 1: the flags and their count per block of 256 positions.
+__global__ __launch_bounds__(kBlk) void k_flags(uint32_t n, const uint32_t *order, const int32_t *ptask, const Task *tasks,
+                                                const Decision *dec, const Box6 *boxes, uint8_t *flag, uint32_t *block_sum) {
+    const uint32_t i = blockIdx.x * kBlk + threadIdx.x;
+    const bool f = i < n && left_flag(i, order, ptask, tasks, dec, boxes);
+    if (i < n) flag[i] = f ? 1u : 0u;
+    const int c = __syncthreads_count(f ? 1 : 0);
+    if (threadIdx.x == 0) block_sum[blockIdx.x] = (uint32_t)c;
+}
+
+// Partition pass 3 (pass 2 is k_excl_scan over block_sum): each position's stable destination.
+// F = flags before position i; inside a split task [lo, hi) with n_left lefts, rel = F - F(lo):
+// a left goes to lo + rel, a right to lo + n_left + (i - lo - rel).
+__global__ __launch_bounds__(kBlk) void k_scatter(uint32_t n, const uint32_t *order, const int32_t *ptask, const Task *tasks,
+                                                  const Decision *dec, const uint32_t *s_child, const uint32_t *s_left,
+                                                  const uint8_t *flag, const uint32_t *block_off, uint32_t *order_out,
+                                                  int32_t *ptask_out, LevelState *st) {
+    __shared__ uint32_t s[kBlk];
+    const uint32_t tid = threadIdx.x, i = blockIdx.x * kBlk + tid;
+    const uint32_t f = i < n ? flag[i] : 0u;
+    s[tid] = f;
+    __syncthreads();
+    for (uint32_t off = 1; off < (uint32_t)kBlk; off <<= 1) {
+        const uint32_t v = tid >= off ? s[tid - off] : 0u;
+        __syncthreads();
+        s[tid] += v;
+        __syncthreads();
+    }
+    if (i >= n) return;
+    const uint32_t F = block_off[blockIdx.x] + s[tid] - f;
+    const int32_t t = ptask[i];
+    if (t < 0 || !dec[t].split) {  // outside the level's tasks, or in a task that became a leaf
+        order_out[i] = order[i];
+        ptask_out[i] = -1;
+        return;
+    }
+    const uint32_t lo = tasks[t].lo, hi = tasks[t].hi, n_left = dec[t].n_left;
+    const uint32_t rel = F - s_left[t];
+    const uint32_t dest = f ? lo + rel : lo + n_left + (i - lo - rel);
+    if (dest < lo || dest >= hi || dest >= n) {
+        atomicOr(&st->error, 1u);
+        return;
+    }
+    const uint32_t ci = s_child[t];
+    const bool task0 = n_left > 1u, task1 = hi - lo - n_left > 1u;
+    order_out[dest] = order[i];
+    ptask_out[dest] = f ? (task0 ? (int32_t)ci : -1) : (task1 ? (int32_t)(ci + (task0 ? 1u : 0u)) : -1);
+}
+
+__global__ __launch_bounds__(kBlk) void k_pack(uint32_t n_nodes, const RawNode *raw, Slack slack, uint32_t stride,
+                                               uint32_t *out) {
+    const uint32_t k = blockIdx.x * kBlk + threadIdx.x;
+    if (k >= n_nodes) return;
+    uint32_t w[20];
+    pack_node(raw[k], slack, stride, w);
+    const uint32_t words = stride / 4u;
+    for (uint32_t j = 0; j < words; ++j) out[(size_t)k * words + j] = w[j];
+}
+
+uint32_t blocks_of(uint32_t n, uint32_t b) { return (n + b - 1u) / b; }
+
+template <class T>
+hipError_t grow(T *&p, size_t &cap, size_t need) {
+    if (need <= cap) return hipSuccess;
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    cap = 0;
+    const size_t want = std::max(need, (size_t)64);
+    const hipError_t e = hipMalloc((void **)&p, want * sizeof(T));
+    if (e == hipSuccess) cap = want;
+    return e;
+}
+
+}  // namespace
+
+struct DeviceBvhBuilder::Impl {
+    uint32_t n_tree = 0;
+    Box6 *d_boxes = nullptr;
+    uint32_t *d_order[2] = {nullptr, nullptr};
+    int32_t *d_ptask[2] = {nullptr, nullptr};
+    uint32_t *d_order0 = nullptr;  // the initial order, kept for the second shape
+    Task *d_tasks[2] = {nullptr, nullptr};
+    size_t tasks_cap[2] = {0, 0};
+    Decision *d_dec = nullptr;
+    size_t dec_cap = 0;
+    Bin *d_bins = nullptr;
+    size_t bins_cap = 0;
+    uint32_t *d_scan = nullptr;  // 3 x scan_cap
+    size_t scan_cap = 0;
+    RawNode *d_raw = nullptr;
+    uint8_t *d_flag = nullptr;
+    uint32_t *d_block = nullptr;
+    uint32_t *d_totals = nullptr;  // 3 task totals, 3 block totals
+    LevelState *d_state = nullptr;
+    int cur = 0;
+    Slack slack{};
+    Summary sum{};
+    uint32_t levels = 0;
+
+    ~Impl() {
+        (void)hipFree(d_boxes);
+        for (int k = 0; k < 2; ++k) {
+            (void)hipFree(d_order[k]);
+            (void)hipFree(d_ptask[k]);
+            (void)hipFree(d_tasks[k]);
+        }
+        (void)hipFree(d_order0);
+        (void)hipFree(d_dec);
+        (void)hipFree(d_bins);
+        (void)hipFree(d_scan);
+        (void)hipFree(d_raw);
+        (void)hipFree(d_flag);
+        (void)hipFree(d_block);
+        (void)hipFree(d_totals);
+        (void)hipFree(d_state);
+    }
+};
+
+DeviceBvhBuilder::DeviceBvhBuilder() : impl_(new Impl) {}
+DeviceBvhBuilder::~DeviceBvhBuilder() { delete impl_; }
+
+#define BB_TRY(expr)                       \
+    do {                                   \
+        const hipError_t e_ = (expr);      \
+        if (e_ != hipSuccess) return e_;   \
+    } while (0)
+
+hipError_t DeviceBvhBuilder::upload(const Box6 *boxes, uint32_t n_boxes, const uint32_t *objs, uint32_t n_tree) {
+    Impl &m = *impl_;
+    if (n_tree < 2u) return hipErrorInvalidValue;
+    for (uint32_t i = 0; i < n_tree; ++i)
+        if (objs[i] >= n_boxes) return hipErrorInvalidValue;
+    m.n_tree = n_tree;
+    const uint32_t nb = blocks_of(n_tree, kBlk);
+    BB_TRY(hipMalloc((void **)&m.d_boxes, (size_t)n_boxes * sizeof(Box6)));
+    BB_TRY(hipMemcpy(m.d_boxes, boxes, (size_t)n_boxes * sizeof(Box6), hipMemcpyHostToDevice));
+    BB_TRY(hipMalloc((void **)&m.d_order0, (size_t)n_tree * 4));
+    BB_TRY(hipMemcpy(m.d_order0, objs, (size_t)n_tree * 4, hipMemcpyHostToDevice));
+    for (int k = 0; k < 2; ++k) {
+        BB_TRY(hipMalloc((void **)&m.d_order[k], (size_t)n_tree * 4));
+        BB_TRY(hipMalloc((void **)&m.d_ptask[k], (size_t)n_tree * 4));
+    }
+    BB_TRY(hipMalloc((void **)&m.d_raw, (size_t)n_tree * sizeof(RawNode)));  // internal nodes <= n_tree - 1
+    BB_TRY(hipMalloc((void **)&m.d_flag, (size_t)n_tree));
+    BB_TRY(hipMalloc((void **)&m.d_block, (size_t)nb * 4));
+    BB_TRY(hipMalloc((void **)&m.d_totals, 6 * 4));
+    BB_TRY(hipMalloc((void **)&m.d_state, sizeof(LevelState)));
+    return hipSuccess;
+}
+
+hipError_t DeviceBvhBuilder::build(uint32_t max_leaf, double node_cost, Summary *out) {
+    Impl &m = *impl_;
+    const uint32_t n = m.n_tree;
+    if (n < 2u) return hipErrorInvalidValue;
+    const uint32_t nb = blocks_of(n, kBlk);
+    m.cur = 0;
+    BB_TRY(hipMemcpy(m.d_order[0], m.d_order0, (size_t)n * 4, hipMemcpyDeviceToDevice));
+    BB_TRY(hipMemset(m.d_ptask[0], 0, (size_t)n * 4));  // every primitive in task 0, the root
+    BB_TRY(hipMemset(m.d_state, 0, sizeof(LevelState)));
+    BB_TRY(grow(m.d_tasks[0], m.tasks_cap[0], 1));
+    Task root;
+    root.lo = 0;
+    root.hi = n;
+    root.slot = kNoSlot;
+    root.usable = 0;
+    root.b = bounds_empty();
+    BB_TRY(hipMemcpy(m.d_tasks[0], &root, sizeof(Task), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_root_bounds, dim3(nb), dim3(kBlk), 0, 0, n, m.d_order[0], m.d_boxes, m.d_tasks[0]);
+    hipLaunchKernelGGL(k_root_finish, dim3(1), dim3(1), 0, 0, m.d_tasks[0]);
+    BB_TRY(hipGetLastError());
+    BB_TRY(hipMemcpy(&root, m.d_tasks[0], sizeof(Task), hipMemcpyDeviceToHost));
+    double root_box[6];
+    for (int j = 0; j < 6; ++j) root_box[j] = key_f64(root.b.k[j]);
+    m.slack = slack_of(root_box);
+
+    uint32_t n_tasks = 1, level = 0, max_depth = 0;
+    LevelState st{};
+    while (n_tasks > 0) {
+        if (level > n) return hipErrorUnknown;  // every split leaves two non-empty sides: depth < n
+        const int c = m.cur, o = 1 - m.cur;
+        const uint32_t next_cap = std::min<uint64_t>(2ull * n_tasks, n / 2u);
+        BB_TRY(grow(m.d_tasks[o], m.tasks_cap[o], std::max<size_t>(next_cap, 1)));
+        BB_TRY(grow(m.d_dec, m.dec_cap, n_tasks));
+        BB_TRY(grow(m.d_bins, m.bins_cap, (size_t)n_tasks * (3 * kBins)));
+        if (n_tasks > m.scan_cap) {
+            (void)hipFree(m.d_scan);
+            m.d_scan = nullptr;
+            m.scan_cap = 0;
+            BB_TRY(hipMalloc((void **)&m.d_scan, (size_t)n_tasks * 3 * 4));
+            m.scan_cap = n_tasks;
+        }
+        uint32_t *s_node = m.d_scan, *s_child = m.d_scan + m.scan_cap, *s_left = m.d_scan + 2 * m.scan_cap;
+        const uint64_t bin_words = (uint64_t)n_tasks * kTaskWords;
+        const uint32_t tb = blocks_of(n_tasks, 64u);
+        hipLaunchKernelGGL(k_bins_init, dim3((uint32_t)((bin_words + kBlk - 1) / kBlk)), dim3(kBlk), 0, 0, bin_words,
+                           (u64 *)m.d_bins);
+        hipLaunchKernelGGL(k_bin, dim3(nb), dim3(kBlk), 0, 0, n, m.d_order[c], m.d_ptask[c], m.d_tasks[c], m.d_boxes,
+                           m.d_bins);
+        hipLaunchKernelGGL(k_decide, dim3(tb), dim3(64), 0, 0, n_tasks, m.d_tasks[c], m.d_bins, max_leaf, node_cost,
+                           m.d_dec, s_node, s_child, s_left);
+        hipLaunchKernelGGL(k_excl_scan, dim3(1), dim3(kScanBlk), 0, 0, n_tasks, s_node, s_child, s_left, m.d_totals);
+        hipLaunchKernelGGL(k_level_totals, dim3(1), dim3(1), 0, 0, m.d_totals, m.d_state);
+        hipLaunchKernelGGL(k_emit, dim3(tb), dim3(64), 0, 0, n_tasks, m.d_tasks[c], m.d_dec, s_node, s_child, m.d_state,
+                           m.d_raw, n, m.d_tasks[o], next_cap);
+        hipLaunchKernelGGL(k_flags, dim3(nb), dim3(kBlk), 0, 0, n, m.d_order[c], m.d_ptask[c], m.d_tasks[c], m.d_dec,
+                           m.d_boxes, m.d_flag, m.d_block);
+        hipLaunchKernelGGL(k_excl_scan, dim3(1), dim3(kScanBlk), 0, 0, nb, m.d_block, (uint32_t *)nullptr,
+                           (uint32_t *)nullptr, m.d_totals + 3);
+        hipLaunchKernelGGL(k_scatter, dim3(nb), dim3(kBlk), 0, 0, n, m.d_order[c], m.d_ptask[c], m.d_tasks[c], m.d_dec,
+                           s_child, s_left, m.d_flag, m.d_block, m.d_order[o], m.d_ptask[o], m.d_state);
+        BB_TRY(hipGetLastError());
+        BB_TRY(hipMemcpy(&st, m.d_state, sizeof(LevelState), hipMemcpyDeviceToHost));  // the per-level blocking read
+        if (st.error || st.n_next > next_cap) return hipErrorUnknown;
+        if (st.n_split) max_depth = level + 1;
+        m.cur = o;
+        n_tasks = st.n_next;
+        ++level;
+    }
+    m.levels = level;
+    m.sum.n_nodes = st.n_nodes;
+    m.sum.n_leaves = st.n_leaves;
+    m.sum.max_depth = std::max(max_depth, 1u);  // a root leaf: depth 1
+    m.sum.max_leaf = st.max_leaf;
+    if (m.sum.n_nodes == 0 || m.sum.n_nodes > n) return hipErrorUnknown;
+    if (out) *out = m.sum;
+    return hipSuccess;
+}
+
+hipError_t DeviceBvhBuilder::emit(uint32_t stride, uint8_t **d_nodes_out, uint32_t *order_out) {
+    Impl &m = *impl_;
+    if ((stride != 80u && stride != 32u) || m.sum.n_nodes == 0) return hipErrorInvalidValue;
+    uint8_t *d = nullptr;
+    BB_TRY(hipMalloc((void **)&d, (size_t)m.sum.n_nodes * stride));
+    hipLaunchKernelGGL(k_pack, dim3(blocks_of(m.sum.n_nodes, kBlk)), dim3(kBlk), 0, 0, m.sum.n_nodes, m.d_raw, m.slack,
+                       stride, (uint32_t *)d);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpy(order_out, m.d_order[m.cur], (size_t)m.n_tree * 4, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) {
+        (void)hipFree(d);
+        return e;
+    }
+    *d_nodes_out = d;
+    return hipSuccess;
+}
+
+uint32_t DeviceBvhBuilder::levels() const { return impl_->levels; }
+
+}  // namespace rrt

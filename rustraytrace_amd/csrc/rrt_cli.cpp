@@ -100,12 +100,14 @@ static void usage() {
                  "Usage: rrt [--backend hip|cuda|gpu] <book> [scene] [--image_width N] [--samples_per_pixel N]\n"
                  "           [--max_depth N] [--aspect_ratio X] [--vfov X] [--lookfrom x,y,z] [--lookat x,y,z]\n"
                  "           [--vup x,y,z] [--defocus_angle X] [--focus_dist X] [--background r,g,b]\n"
-                 "           [--gpus N] [--seed S] [--grid_half G] [--p6] [--host-quantise] [--books-f64] [-o out.ppm]\n"
+                 "           [--gpus N] [--seed S] [--grid_half G] [--p6] [--host-quantise] [--books-f64] [--device-bvh]\n"
+                 "           [-o out.ppm]\n"
                  "  --p6             binary P6 instead of render_io.rs's P3 text\n"
                  "  --host-quantise  copy the float accum and quantise on the host (same bytes)\n"
                  "  --books-f64      the f64 books kernel (RRT_FLAG_F64, in_one_weekend) and the books path's own\n"
                  "                   quantiser (color.rs) on the device: the P3 camera.rs prints; with\n"
                  "                   --host-quantise the f64 sums are copied and quantised on the host (same bytes)\n"
+                 "  --device-bvh     build the scene's BVH on the device (RRT_FLAG_DEVICE_BVH) instead of the host\n"
                  "books: in_one_weekend, the_next_week [1-9, other = final_scene(400, 250, 4)], "
                  "the_rest_of_your_life\n");
 }
@@ -143,7 +145,7 @@ int main(int argc, char **argv) {
     uint64_t seed = 0x5EED1234ull;
     int grid_half = 11;
     std::string out = "-";
-    bool p6 = false, host_quantise = false, seed_set = false, books_f64 = false;
+    bool p6 = false, host_quantise = false, seed_set = false, books_f64 = false, device_bvh = false;
 
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
@@ -176,6 +178,7 @@ int main(int argc, char **argv) {
         else if (a == "--p6") p6 = true;
         else if (a == "--host-quantise") host_quantise = true;
         else if (a == "--books-f64") books_f64 = true;
+        else if (a == "--device-bvh") device_bvh = true;
         else if (a == "-h" || a == "--help") { usage(); return 0; }
         else positional.push_back(a);
     }
@@ -285,6 +288,7 @@ int main(int argc, char **argv) {
     ext.n_boundary_quads = (uint32_t)boundary_quads.size();
     ext.lights = lights.empty() ? nullptr : lights.data();
     ext.n_lights = (uint32_t)lights.size();
+    if (device_bvh) flags |= RRT_FLAG_DEVICE_BVH;
     const uint32_t w = (uint32_t)cam.params_f[1], h = (uint32_t)cam.params_f[2];
     const uint32_t spp = (uint32_t)(cam.params_f[3] < 1.0f ? 1.0f : cam.params_f[3]);
     const auto t0 = std::chrono::steady_clock::now();

@@ -9,6 +9,7 @@
 // returns (ownership contract of SURVEY §8b). No CPU rendering fallback exists here:
 // without a HIP device every render entry fails with RRT_E_NODEV.
 #include "rrt_internal.h"
+#include "rrt_bvh_binned.h"
 #include "../../include/rrt_hip.h"
 
 #include <algorithm>
@@ -767,12 +768,8 @@ std::vector<uint32_t> unbounded_media(const RrtSphere *spheres, uint32_t n_spher
     return out;
 }
 
-// BVH2 node layout: the sign-ordered 80-B nodes when `lds_fit(the tree in those nodes)` says the
-// scene will be staged in LDS, else the 32-B f16 global-memory nodes. node_cost: the SAH's node
-// visit price in sphere tests (Builder::node_cost).
-FlatBvh build_bvh(const RrtSphere *spheres, uint32_t n_spheres, const ExtView &ex, uint32_t width,
-                  uint32_t max_leaf, double node_cost, std::vector<uint32_t> &order,
-                  const std::function<bool(const FlatBvh &)> &lds_fit) {
+// The padded f64 box of every primitive, in primitive order (spheres, quads, media).
+std::vector<Aabb> prim_boxes(const RrtSphere *spheres, uint32_t n_spheres, const ExtView &ex) {
     const float *motion = ex.motion;
     const uint32_t n_quads = ex.n_quads;
     std::vector<Aabb> boxes(n_spheres + (size_t)n_quads + ex.n_media);
@@ -802,6 +799,17 @@ FlatBvh build_bvh(const RrtSphere *spheres, uint32_t n_spheres, const ExtView &e
         }
         boxes[n_spheres + n_quads + m] = b;
     }
+    return boxes;
+}
+
+// BVH2 node layout: the sign-ordered 80-B nodes when `lds_fit(the tree in those nodes)` says the
+// scene will be staged in LDS, else the 32-B f16 global-memory nodes. node_cost: the SAH's node
+// visit price in sphere tests (Builder::node_cost).
+FlatBvh build_bvh(const RrtSphere *spheres, uint32_t n_spheres, const ExtView &ex, uint32_t width,
+                  uint32_t max_leaf, double node_cost, std::vector<uint32_t> &order,
+                  const std::function<bool(const FlatBvh &)> &lds_fit) {
+    const uint32_t n_quads = ex.n_quads;
+    const std::vector<Aabb> boxes = prim_boxes(spheres, n_spheres, ex);
     const uint32_t n_prims = n_spheres + n_quads + ex.n_media;
     const std::vector<uint32_t> unb = unbounded_media(spheres, n_spheres, ex);
     Builder bld(boxes, max_leaf);
@@ -858,6 +866,195 @@ FlatBvh scene_bvh(const RrtSphere *spheres, uint32_t n_spheres, const ExtView &e
     return fb;
 }
 
+// ---- RRT_FLAG_DEVICE_BVH: the binned builder of rrt_bvh_binned.h ---------------------------------
+namespace bvhb = rrt::bvhb;
+// Its input, formed on the host in O(n): every primitive's padded box (prim_boxes), the tree's
+// primitives in their original order, and the unbounded media that stay outside the tree.
+struct BinnedInput {
+    std::vector<bvhb::Box6> boxes;
+    std::vector<uint32_t> objs;
+    std::vector<uint32_t> unbounded;  // primitive indices, appended to the leaf order
+};
+BinnedInput binned_input(const RrtSphere *spheres, uint32_t n_spheres, const ExtView &ex) {
+    BinnedInput in;
+    const std::vector<Aabb> boxes = prim_boxes(spheres, n_spheres, ex);
+    in.boxes.resize(boxes.size());
+    for (size_t i = 0; i < boxes.size(); ++i)
+        for (int a = 0; a < 3; ++a) in.boxes[i].mn[a] = boxes[i].ax[a].min, in.boxes[i].mx[a] = boxes[i].ax[a].max;
+    std::vector<bool> out(boxes.size(), false);
+    for (uint32_t m : unbounded_media(spheres, n_spheres, ex)) {
+        in.unbounded.push_back(n_spheres + ex.n_quads + m);
+        out[n_spheres + ex.n_quads + m] = true;
+    }
+    for (uint32_t i = 0; i < (uint32_t)boxes.size(); ++i)
+        if (!out[i]) in.objs.push_back(i);
+    return in;
+}
+
+// The host twin: the header's builder run sequentially, level by level. The device builder
+// (rrt_bvh_build.hip) must produce these bytes.
+struct BinnedTree {
+    std::vector<bvhb::RawNode> raw;
+    std::vector<uint32_t> objs;
+    bvhb::Summary sum{};
+    bvhb::Slack slack{};
+};
+BinnedTree build_binned_host(const BinnedInput &in, uint32_t max_leaf, double node_cost) {
+    using namespace bvhb;
+    BinnedTree bt;
+    bt.objs = in.objs;
+    std::vector<uint32_t> &objs = bt.objs;
+    const uint32_t n = (uint32_t)objs.size();
+    Task root;
+    root.lo = 0, root.hi = n, root.slot = kNoSlot, root.usable = 0;
+    root.b = bounds_empty();
+    for (uint32_t i = 0; i < n; ++i) bounds_merge(root.b, bounds_of(in.boxes[objs[i]]));
+    task_finish(root);
+    double root_box[6];
+    for (int j = 0; j < 6; ++j) root_box[j] = key_f64(root.b.k[j]);
+    if (n == 0) never_hit(root_box);
+    bt.slack = slack_of(root_box);
+    auto leaf_seen = [&](uint32_t count) {
+        bt.sum.n_leaves++;
+        bt.sum.max_leaf = std::max(bt.sum.max_leaf, count);
+    };
+    auto root_leaf = [&]() {  // flatten2's root-leaf form: child 0 = the leaf, child 1 never hit
+        RawNode r{};
+        for (int j = 0; j < 6; ++j) r.box[0][j] = root_box[j];
+        never_hit(r.box[1]);
+        r.link[0] = n << kLeafShift;
+        bt.raw.push_back(r);
+        leaf_seen(n);
+        bt.sum.max_depth = 1;
+    };
+    std::vector<Task> tasks, next;
+    if (n <= 1) root_leaf();
+    else tasks.push_back(root);
+    std::vector<Bin> bins(3 * kBins);
+    std::vector<uint32_t> tmp;
+    for (uint32_t level = 0; !tasks.empty(); ++level) {
+        next.clear();
+        for (const Task &t : tasks) {
+            for (Bin &b : bins) b.n = 0, b.b = bounds_empty();
+            for (uint32_t i = t.lo; i < t.hi; ++i)
+                for (int axis = 0; axis < 3; ++axis) {
+                    const int b = task_bin(t, axis, i, in.boxes[objs[i]]);
+                    if (b < 0) continue;
+                    bins[axis * kBins + b].n++;
+                    bounds_merge(bins[axis * kBins + b].b, bounds_of(in.boxes[objs[i]]));
+                }
+            const Decision d = decide(t, bins.data(), max_leaf, node_cost);
+            const uint32_t span = t.hi - t.lo;
+            if (!d.split) {
+                if (t.slot == kNoSlot) root_leaf();
+                else bt.raw[t.slot >> 1].link[t.slot & 1u] = t.lo | (span << kLeafShift), leaf_seen(span);
+                continue;
+            }
+            const uint32_t id = (uint32_t)bt.raw.size();
+            RawNode r{};
+            for (int c = 0; c < 2; ++c)
+                for (int j = 0; j < 6; ++j) r.box[c][j] = key_f64(d.child[c].k[j]);
+            bt.raw.push_back(r);
+            if (t.slot != kNoSlot) bt.raw[t.slot >> 1].link[t.slot & 1u] = id;
+            bt.sum.max_depth = level + 1;
+            tmp.assign(objs.begin() + t.lo, objs.begin() + t.hi);
+            uint32_t l = t.lo, rr = t.lo + d.n_left;
+            for (uint32_t i = t.lo; i < t.hi; ++i) {
+                const uint32_t o = tmp[i - t.lo];
+                if (goes_left(t, d, i, in.boxes[o])) objs[l++] = o;
+                else objs[rr++] = o;
+            }
+            const uint32_t first[2] = {t.lo, t.lo + d.n_left}, count[2] = {d.n_left, span - d.n_left};
+            for (int c = 0; c < 2; ++c) {
+                if (count[c] <= 1u) {
+                    bt.raw[id].link[c] = first[c] | (count[c] << kLeafShift);
+                    leaf_seen(count[c]);
+                    continue;
+                }
+                Task nt;
+                nt.lo = first[c], nt.hi = first[c] + count[c], nt.slot = 2u * id + (uint32_t)c;
+                nt.b = d.child[c];
+                task_finish(nt);
+                next.push_back(nt);
+            }
+        }
+        tasks.swap(next);
+    }
+    bt.sum.n_nodes = (uint32_t)bt.raw.size();
+    return bt;
+}
+
+// The twin's FlatBvh in the 80-B or 32-B node format (the header's roundings).
+FlatBvh flat_of_summary(const bvhb::Summary &sum, uint32_t stride, const BinnedInput &in) {
+    FlatBvh f;
+    f.n_nodes = sum.n_nodes;
+    f.n_leaves = sum.n_leaves;
+    f.max_depth = sum.max_depth;
+    f.max_leaf = sum.max_leaf;
+    f.stack_need = sum.max_depth + 1;
+    f.width = 2;
+    f.stride = stride;
+    f.n_unbounded = (uint32_t)in.unbounded.size();
+    return f;
+}
+FlatBvh flatten_binned(const BinnedTree &bt, uint32_t stride, const BinnedInput &in, std::vector<uint32_t> &order) {
+    FlatBvh f = flat_of_summary(bt.sum, stride, in);
+    f.bytes.resize((size_t)bt.raw.size() * stride);
+    for (size_t k = 0; k < bt.raw.size(); ++k)
+        bvhb::pack_node(bt.raw[k], bt.slack, stride, (uint32_t *)(f.bytes.data() + k * stride));
+    order = bt.objs;
+    order.insert(order.end(), in.unbounded.begin(), in.unbounded.end());
+    return f;
+}
+
+// scene_bvh's composition with the device builder: the LDS shape kept when it fits (and not built
+// when the primitive records alone exceed the budget: it would be discarded), else the global shape
+// in 32-B nodes, else the documented fallback to the caller's leaf size. The nodes stay on the
+// device (d_nodes, owned by the caller); the order and the summary come back. n_tree >= 2.
+// leaf_param: the leaf size of the shape that was kept.
+int scene_bvh_device(const BinnedInput &in, size_t n_prims_all, uint32_t max_leaf, bool book2, bool f64, FlatBvh &fb,
+                     uint8_t **d_nodes, std::vector<uint32_t> &order, uint32_t &leaf_param, uint32_t &levels) {
+    rrt::DeviceBvhBuilder bld;
+    if (bld.upload(in.boxes.data(), (uint32_t)in.boxes.size(), in.objs.data(), (uint32_t)in.objs.size()) != hipSuccess)
+        return fail(RRT_E_HIP, "device BVH: upload failed");
+    auto cost = [](double c) {
+        if (const char *e = std::getenv("RRT_SAH_CT")) return std::atof(e);
+        return c;
+    };
+    auto fits = [&](const bvhb::Summary &s) {
+        if (scene_lds_forced_off()) return false;
+        if (f64) return rrt::f64_lds_min_bytes(s.n_nodes, (uint32_t)n_prims_all, s.max_depth + 1) <= 64u * 1024u;
+        return scene_lds_fit((size_t)s.n_nodes * sizeof(rrt::GNode), n_prims_all, book2);
+    };
+    bvhb::Summary sum{};
+    levels = 0;
+    uint32_t stride = 0;
+    bvhb::Summary none{};
+    none.n_nodes = 1, none.max_depth = 1;
+    if (fits(none)) {  // the primitive records leave room for a node
+        if (bld.build(max_leaf, cost(f64 ? f64_node_cost_lds() : kNodeCost), &sum) != hipSuccess)
+            return fail(RRT_E_HIP, "device BVH: build failed");
+        levels += bld.levels();
+        if (fits(sum)) stride = (uint32_t)sizeof(rrt::GNode), leaf_param = max_leaf;
+    }
+    if (!stride) {
+        stride = (uint32_t)sizeof(rrt::GNodeH);
+        leaf_param = std::min(max_leaf, max_leaf_global());
+        if (bld.build(leaf_param, cost(kNodeCost), &sum) != hipSuccess) return fail(RRT_E_HIP, "device BVH: build failed");
+        levels += bld.levels();
+        if ((f64 && sum.n_nodes > 65535u) || sum.max_depth + 1 > (uint32_t)rrt::kMaxStackDepth) {
+            leaf_param = max_leaf;
+            if (bld.build(leaf_param, cost(kNodeCost), &sum) != hipSuccess) return fail(RRT_E_HIP, "device BVH: build failed");
+            levels += bld.levels();
+        }
+    }
+    fb = flat_of_summary(sum, stride, in);
+    order.assign(in.objs.size(), 0u);
+    if (bld.emit(stride, d_nodes, order.data()) != hipSuccess) return fail(RRT_E_HIP, "device BVH: emit failed");
+    order.insert(order.end(), in.unbounded.begin(), in.unbounded.end());
+    return RRT_OK;
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------
@@ -892,6 +1089,7 @@ struct RrtScene {
     uint32_t last_groups = 0, last_passes = 0;      // the last launch: 64-unit groups per pass, passes
     rrt::KParams base{};
     RrtBvhInfo info{};
+    std::vector<uint32_t> order;  // the leaf order (rrt_scene_read_bvh)
 };
 
 namespace {
@@ -1253,7 +1451,15 @@ static int32_t scene_create(const RrtCamera *cam, const RrtSphere *spheres, uint
         book2 = book2 || materials[i].kind == RRT_MAT_CHECKER_LAMBERTIAN || materials[i].kind == RRT_MAT_NOISE_LAMBERTIAN ||
                 materials[i].kind == RRT_MAT_ISOTROPIC;
     static_assert(RRT_FLAG_F64 == rrt::kFlagF64, "RRT_FLAG_F64");
+    static_assert(RRT_FLAG_DEVICE_BVH == rrt::kFlagDeviceBvh, "RRT_FLAG_DEVICE_BVH");
     const bool f64 = (flags & RRT_FLAG_F64) != 0;
+    const bool device_bvh = (flags & RRT_FLAG_DEVICE_BVH) != 0;
+    flags &= ~RRT_FLAG_DEVICE_BVH;  // a choice of scene creation: the kernels never see it
+    if (device_bvh) {
+        uint32_t w, l;
+        bvh_defaults(w, l);
+        if (w != 2) return fail(RRT_E_INVALID, "RRT_FLAG_DEVICE_BVH builds binary trees only (RRT_BVH_WIDTH=4 is set)");
+    }
     if (f64 && (book2 || n_perlin || ex.n_lights))
         return fail(RRT_E_INVALID, "RRT_FLAG_F64 renders book-1 scenes (material kinds 0-4, no RrtSceneExt data, "
                                    "not RRT_FLAG_BOOK3)");
@@ -1289,7 +1495,28 @@ static int32_t scene_create(const RrtCamera *cam, const RrtSphere *spheres, uint
         (uint64_t)n_quads + ex.n_bquads + ex.n_lights >= (1u << 24))
         return fail(RRT_E_INVALID, ">= 2^24 primitives or quads");
     if (!has_motion) ex.motion = nullptr;
-    const FlatBvh fb = scene_bvh(spheres, n_spheres, ex, width, max_leaf, book2, f64, order);
+    // RRT_FLAG_DEVICE_BVH: the binned builder on the device (rrt_bvh_build.hip); its nodes stay there.
+    // A tree of at most one primitive is the root-leaf form, which the host builder writes.
+    FlatBvh fb;
+    struct DeviceNodes {
+        uint8_t *p = nullptr;
+        ~DeviceNodes() { if (p) (void)hipFree(p); }
+    } dev_nodes;
+    uint32_t leaf_param = max_leaf;
+    bool built_on_device = false;
+    if (device_bvh) {
+        const BinnedInput in = binned_input(spheres, n_spheres, ex);
+        if (in.objs.size() > 1) {
+            if (hipSetDevice(device) != hipSuccess) return fail(RRT_E_HIP, "hipSetDevice failed");
+            uint32_t levels = 0;
+            if (int rc = scene_bvh_device(in, (size_t)n_spheres + n_quads + n_media, max_leaf, book2, f64, fb, &dev_nodes.p,
+                                          order, leaf_param, levels))
+                return rc;
+            built_on_device = true;
+        }
+    }
+    if (!built_on_device) fb = scene_bvh(spheres, n_spheres, ex, width, max_leaf, book2, f64, order);
+    const size_t node_bytes = built_on_device ? (size_t)fb.n_nodes * fb.stride : fb.bytes.size();
     if (fb.stack_need > (uint32_t)rrt::kMaxStackDepth)
         return fail(RRT_E_INVALID, "BVH depth " + std::to_string(fb.max_depth) + " exceeds the LDS stack");
     if (f64 && fb.n_nodes > 65535u) return fail(RRT_E_INVALID, "RRT_FLAG_F64: more than 65535 BVH nodes");
@@ -1423,7 +1650,10 @@ static int32_t scene_create(const RrtCamera *cam, const RrtSphere *spheres, uint
     int rc = RRT_OK;
     do {
         if (hipSetDevice(device) != hipSuccess) { rc = fail(RRT_E_HIP, "hipSetDevice failed"); break; }
-        if ((rc = upload(&s->d_nodes, fb.bytes.data(), fb.bytes.size(), "nodes"))) break;
+        if (built_on_device) {
+            s->d_nodes = dev_nodes.p;
+            dev_nodes.p = nullptr;
+        } else if ((rc = upload(&s->d_nodes, fb.bytes.data(), fb.bytes.size(), "nodes"))) break;
         if ((rc = upload(&s->d_prim_cr, prim_cr.data(), prim_cr.size(), "spheres"))) break;
         if ((rc = upload(&s->d_prim_mtl, prim_mtl.data(), prim_mtl.size(), "sphere materials"))) break;
         if (book2 && (rc = upload(&s->d_prim_motion, prim_motion.data(), prim_motion.size(), "sphere motion"))) break;
@@ -1531,7 +1761,7 @@ static int32_t scene_create(const RrtCamera *cam, const RrtSphere *spheres, uint
     p.bvh_width = fb.width;
     // BVH2: the node layout already encodes the choice (80-B sign-ordered nodes are the LDS ones)
     p.scene_in_lds = fb.width == 2 ? fb.stride == (uint32_t)sizeof(rrt::GNode)
-                                   : scene_lds_fit(fb.bytes.size(), n_prims, book2);
+                                   : scene_lds_fit(node_bytes, n_prims, book2);
     // traversal exit / leaf batch thresholds (x/256 of the live lanes), same-box sweeps against 32/32:
     // book-1 LDS scenes 56/56 (C2 +0.6 %, C4 +0.25 %); L2 scenes 64/48 (C5 +2.0 %, final_scene and
     // bouncing spheres +4 %). Book-2/3 LDS scenes by kernel class (round 6, after the class launch
@@ -1572,10 +1802,11 @@ static int32_t scene_create(const RrtCamera *cam, const RrtSphere *spheres, uint
     bi.n_leaves = fb.n_leaves;
     bi.max_depth = fb.max_depth;
     bi.max_leaf_size = fb.max_leaf;
-    bi.node_bytes = fb.bytes.size();
+    bi.node_bytes = node_bytes;
     bi.node_stride = fb.stride;
     bi.width = fb.width;
-    bi.max_leaf_param = max_leaf;
+    bi.max_leaf_param = built_on_device ? leaf_param : max_leaf;  // the device builder reports the kept shape's
+    s->order = order;
     bi.n_unbounded = fb.n_unbounded;
     bi.prim_bytes = (uint64_t)n_prims * (rrt::kPrimBytes + (book2 ? rrt::kMotionBytes : 0)) +
                     (uint64_t)gquads.size() * sizeof(rrt::GQuad) + (uint64_t)n_media * sizeof(rrt::GMedium);
@@ -1657,6 +1888,56 @@ int32_t rrt_scene_destroy(RrtScene *scene) {
 int32_t rrt_scene_bvh_info(const RrtScene *scene, RrtBvhInfo *out) {
     if (!scene || !out) return fail(RRT_E_INVALID, "null scene or out");
     *out = scene->info;
+    return RRT_OK;
+}
+
+int32_t rrt_scene_read_bvh(RrtScene *scene, void *nodes_out, size_t nodes_cap, uint32_t *prim_order_out) {
+    if (!scene) return fail(RRT_E_INVALID, "null scene");
+    const size_t bytes = (size_t)scene->info.node_bytes;
+    if (!nodes_out || nodes_cap < bytes || (scene->order.size() && !prim_order_out))
+        return fail(RRT_E_INVALID, "nodes buffer too small (need " + std::to_string(bytes) + " bytes)");
+    HIP_TRY(hipSetDevice(scene->device), "hipSetDevice");
+    HIP_TRY(hipMemcpy(nodes_out, scene->d_nodes, bytes, hipMemcpyDeviceToHost), "copy nodes");
+    if (scene->order.size()) std::memcpy(prim_order_out, scene->order.data(), scene->order.size() * sizeof(uint32_t));
+    return RRT_OK;
+}
+
+int32_t rrt_build_bvh_binned(const RrtSphere *spheres, uint32_t n_spheres, const RrtSceneExt *ext, uint32_t max_leaf,
+                             double node_cost, uint32_t node_stride, void *nodes_out, size_t nodes_cap,
+                             uint32_t *prim_order_out, RrtBvhInfo *info) {
+    if (n_spheres && !spheres) return fail(RRT_E_INVALID, "null spheres");
+    const ExtView ex(ext);
+    for (uint32_t m = 0; m < ex.n_media; ++m)
+        if (ex.media[m].boundary_kind == RRT_BOUNDARY_QUADS &&
+            (ex.media[m].count == 0 || (uint64_t)ex.media[m].first + ex.media[m].count > ex.n_bquads))
+            return fail(RRT_E_INVALID, "medium " + std::to_string(m) + ": boundary quad range out of bounds");
+    if (max_leaf == 0 || max_leaf > rrt::kMaxLeafPrims || (node_stride != 80u && node_stride != 32u) || !(node_cost == node_cost))
+        return fail(RRT_E_INVALID, "max_leaf must be 1..7, node_stride 80 or 32");
+    if ((uint64_t)n_spheres + ex.n_quads + ex.n_media >= (1u << 24)) return fail(RRT_E_INVALID, ">= 2^24 primitives");
+    const BinnedInput in = binned_input(spheres, n_spheres, ex);
+    std::vector<uint32_t> order;
+    const FlatBvh fb = flatten_binned(build_binned_host(in, max_leaf, node_cost), node_stride, in, order);
+    if (info) {
+        const bool book2 = ex.motion || ex.n_quads || ex.n_media;
+        *info = RrtBvhInfo{};
+        info->n_nodes = fb.n_nodes;
+        info->n_leaves = fb.n_leaves;
+        info->max_depth = fb.max_depth;
+        info->max_leaf_size = fb.max_leaf;
+        info->node_bytes = fb.bytes.size();
+        info->node_stride = fb.stride;
+        info->prim_bytes = (uint64_t)order.size() * (rrt::kPrimBytes + (book2 ? rrt::kMotionBytes : 0)) +
+                           ((uint64_t)ex.n_quads + ex.n_bquads) * sizeof(rrt::GQuad) +
+                           (uint64_t)ex.n_media * sizeof(rrt::GMedium);
+        info->width = 2;
+        info->max_leaf_param = max_leaf;
+        info->n_unbounded = fb.n_unbounded;
+    }
+    if (nodes_cap == 0) return RRT_OK;
+    if (!nodes_out || nodes_cap < fb.bytes.size() || (order.size() && !prim_order_out))
+        return fail(RRT_E_INVALID, "nodes buffer too small (need " + std::to_string(fb.bytes.size()) + " bytes)");
+    std::memcpy(nodes_out, fb.bytes.data(), fb.bytes.size());
+    if (order.size()) std::memcpy(prim_order_out, order.data(), order.size() * sizeof(uint32_t));
     return RRT_OK;
 }
 

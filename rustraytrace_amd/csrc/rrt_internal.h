@@ -395,4 +395,32 @@ hipError_t launch_accum64_to_f32(const D4 *d_accum64, float4 *d_accum, uint32_t 
 // Test support (rrt_testing_f64_layout): force the f64 kernel's LDS layout of a staged scene (-1: auto)
 void set_f64_layout(int layout);
 
+// RRT_FLAG_DEVICE_BVH (include/rrt_hip.h): scene creation builds the tree on the device
+constexpr uint32_t kFlagDeviceBvh = 0x10u;
+// The binned SAH builder of rrt_bvh_binned.h on the current device (rrt_bvh_build.hip). upload:
+// one padded box per primitive and the n_tree >= 2 primitives of the tree in their original order
+// (host pointers). build: the tree of one shape, kept on the device in raw f64 form; may be called
+// again for another shape. emit: the last build's nodes in the 80-B or 32-B format as a fresh
+// hipMalloc'd array the caller owns, and the leaf order (n_tree entries) to the host. Synchronous,
+// on the default stream.
+namespace bvhb {
+struct Box6;
+struct Summary;
+}  // namespace bvhb
+class DeviceBvhBuilder {
+public:
+    DeviceBvhBuilder();
+    ~DeviceBvhBuilder();
+    DeviceBvhBuilder(const DeviceBvhBuilder &) = delete;
+    DeviceBvhBuilder &operator=(const DeviceBvhBuilder &) = delete;
+    hipError_t upload(const bvhb::Box6 *boxes, uint32_t n_boxes, const uint32_t *objs, uint32_t n_tree);
+    hipError_t build(uint32_t max_leaf, double node_cost, bvhb::Summary *out);
+    hipError_t emit(uint32_t stride, uint8_t **d_nodes_out, uint32_t *order_out);
+    uint32_t levels() const;  // of the last build: one blocking read each
+
+private:
+    struct Impl;
+    Impl *impl_;
+};
+
 }  // namespace rrt

@@ -72,13 +72,14 @@ def scene_ext(scene: SceneData):
     return ext, keep
 
 
-def render(scene: SceneData, spp: Optional[int] = None, n_gpus: int = 1, quiet: bool = True) -> np.ndarray:
+def render(scene: SceneData, spp: Optional[int] = None, n_gpus: int = 1, quiet: bool = True,
+           device_bvh: bool = False) -> np.ndarray:
     """Render `scene` on `n_gpus` GPUs; returns the RGBA float32 accum (H, W, 4), w = sample count."""
     lib = _lib.load()
     accum = np.zeros((scene.height, scene.width, 4), dtype=np.float32)
     tex, ntex, keep = _textures(scene)
     ext, keep_ext = scene_ext(scene)
-    flags = scene.flags | (_lib.FLAG_QUIET if quiet else 0)
+    flags = scene.flags | (_lib.FLAG_QUIET if quiet else 0) | (_lib.FLAG_DEVICE_BVH if device_bvh else 0)
     _lib.check(lib.rrt_hip_render_ex(_lib.ptr(scene.camera), _lib.ptr(scene.spheres), len(scene.spheres),
                                      _lib.ptr(scene.materials), len(scene.materials),
                                      ctypes.cast(tex, ctypes.c_void_p) if tex is not None else None, ntex,
@@ -88,7 +89,8 @@ def render(scene: SceneData, spp: Optional[int] = None, n_gpus: int = 1, quiet: 
     return accum
 
 
-def render_f64(scene: SceneData, spp: Optional[int] = None, n_gpus: int = 1, quiet: bool = True) -> np.ndarray:
+def render_f64(scene: SceneData, spp: Optional[int] = None, n_gpus: int = 1, quiet: bool = True,
+               device_bvh: bool = False) -> np.ndarray:
     """rrt_hip_render_f64: the books path's own f64 arithmetic (RRT_FLAG_F64, book-1 scenes);
     returns the RGBA float64 accum (H, W, 4) of f64 sums, w = sample count."""
     lib = _lib.load()
@@ -96,7 +98,7 @@ def render_f64(scene: SceneData, spp: Optional[int] = None, n_gpus: int = 1, qui
         raise ValueError("render_f64: book-1 scenes only (RRT_FLAG_F64)")
     accum = np.zeros((scene.height, scene.width, 4), dtype=np.float64)
     tex, ntex, keep = _textures(scene)
-    flags = scene.flags | _lib.FLAG_F64 | (_lib.FLAG_QUIET if quiet else 0)
+    flags = scene.flags | _lib.FLAG_F64 | (_lib.FLAG_QUIET if quiet else 0) | (_lib.FLAG_DEVICE_BVH if device_bvh else 0)
     _lib.check(lib.rrt_hip_render_f64(_lib.ptr(scene.camera), _lib.ptr(scene.spheres), len(scene.spheres),
                                       _lib.ptr(scene.materials), len(scene.materials),
                                       ctypes.cast(tex, ctypes.c_void_p) if tex is not None else None, ntex,
@@ -105,7 +107,8 @@ def render_f64(scene: SceneData, spp: Optional[int] = None, n_gpus: int = 1, qui
     return accum
 
 
-def render_rgb8(scene: SceneData, spp: Optional[int] = None, n_gpus: int = 1, quiet: bool = True) -> np.ndarray:
+def render_rgb8(scene: SceneData, spp: Optional[int] = None, n_gpus: int = 1, quiet: bool = True,
+                device_bvh: bool = False) -> np.ndarray:
     """rrt_hip_render_rgb8_ex: render and quantise on the device (render_io.rs quantiser);
     returns (H, W, 3) uint8, identical to quantize_accum(render(scene)) at the same spp, for
     every book (the scene's RrtSceneExt — motion, Perlin tables, quads, media, lights — is passed)."""
@@ -113,7 +116,7 @@ def render_rgb8(scene: SceneData, spp: Optional[int] = None, n_gpus: int = 1, qu
     out = np.zeros((scene.height, scene.width, 3), dtype=np.uint8)
     tex, ntex, keep = _textures(scene)
     ext, keep_ext = scene_ext(scene)
-    flags = scene.flags | (_lib.FLAG_QUIET if quiet else 0)
+    flags = scene.flags | (_lib.FLAG_QUIET if quiet else 0) | (_lib.FLAG_DEVICE_BVH if device_bvh else 0)
     _lib.check(lib.rrt_hip_render_rgb8_ex(_lib.ptr(scene.camera), _lib.ptr(scene.spheres), len(scene.spheres),
                                           _lib.ptr(scene.materials), len(scene.materials),
                                           ctypes.cast(tex, ctypes.c_void_p) if tex is not None else None, ntex,
@@ -130,7 +133,8 @@ def quantize_accum_async(n_pixels: int, d_accum_ptr: int, samples_per_pixel: int
                                                     ctypes.c_void_p(d_rgb8_ptr), ctypes.c_void_p(stream_ptr)))
 
 
-def render_f64_rgb8(scene: SceneData, spp: Optional[int] = None, n_gpus: int = 1, quiet: bool = True) -> np.ndarray:
+def render_f64_rgb8(scene: SceneData, spp: Optional[int] = None, n_gpus: int = 1, quiet: bool = True,
+                    device_bvh: bool = False) -> np.ndarray:
     """rrt_hip_render_f64_rgb8: the f64 books kernel (RRT_FLAG_F64, book-1 scenes), then the books
     path's quantiser (color.rs) on the device; returns (H, W, 3) uint8, identical to
     quantize_accum_books_f64(render_f64(scene)) at the same spp."""
@@ -139,7 +143,7 @@ def render_f64_rgb8(scene: SceneData, spp: Optional[int] = None, n_gpus: int = 1
         raise ValueError("render_f64_rgb8: book-1 scenes only (RRT_FLAG_F64)")
     out = np.zeros((scene.height, scene.width, 3), dtype=np.uint8)
     tex, ntex, keep = _textures(scene)
-    flags = scene.flags | _lib.FLAG_F64 | (_lib.FLAG_QUIET if quiet else 0)
+    flags = scene.flags | _lib.FLAG_F64 | (_lib.FLAG_QUIET if quiet else 0) | (_lib.FLAG_DEVICE_BVH if device_bvh else 0)
     _lib.check(lib.rrt_hip_render_f64_rgb8(_lib.ptr(scene.camera), _lib.ptr(scene.spheres), len(scene.spheres),
                                            _lib.ptr(scene.materials), len(scene.materials),
                                            ctypes.cast(tex, ctypes.c_void_p) if tex is not None else None, ntex,
@@ -277,6 +281,29 @@ def build_bvh(scene: SceneData, width: int = 0, max_leaf: int = 0):
     return nodes, order[:n_prims], info.as_dict()
 
 
+def build_bvh_binned(scene: SceneData, max_leaf: int, node_cost: float, node_stride: int):
+    """rrt_build_bvh_binned (host only): the tree RRT_FLAG_DEVICE_BVH builds for one shape (max_leaf,
+    node_cost) and node format (node_stride 80 or 32), by the device builder's sequential host twin.
+    Returns (node bytes uint8, leaf-order permutation uint32, info dict) like build_bvh."""
+    lib = _lib.load()
+    info = _lib.RrtBvhInfo()
+    n = len(scene.spheres)
+    ext, keep = scene_ext(scene)
+    n_prims = n + (0 if ext is None else ext.n_quads + ext.n_media)
+    extp = ctypes.byref(ext) if ext is not None else None
+
+    def build(nodes_p, cap, order_p):
+        return lib.rrt_build_bvh_binned(_lib.ptr(scene.spheres), n, extp, int(max_leaf), float(node_cost),
+                                        int(node_stride), nodes_p, cap, order_p, ctypes.byref(info))
+
+    _lib.check(build(None, 0, None))
+    nodes = np.zeros(info.node_bytes, dtype=np.uint8)
+    order = np.zeros(max(n_prims, 1), dtype=np.uint32)
+    _lib.check(build(_lib.ptr(nodes), nodes.size, _lib.ptr(order)))
+    del keep
+    return nodes, order[:n_prims], info.as_dict()
+
+
 def decode_bvh2(nodes: np.ndarray, stride: int):
     """Decode build_bvh's width-2 node bytes (rrt_internal.h; stride = info["node_stride"]: 80 =
     GNode, sign-ordered lo/hi/lo planes, 32 = GNodeH, f16 planes): per node and child, box lo/hi (n, 2, 3),
@@ -305,11 +332,12 @@ def make_tile(band_rows=16, rank=0, n_ranks=1, sample_begin=0, sample_end=0) -> 
 class DeviceScene:
     """RrtScene*: scene + BVH resident on one device; renders tiles asynchronously on a stream."""
 
-    def __init__(self, scene: SceneData, device: int = 0, f64: bool = False):
-        """f64=True: the books path's f64 kernel (RRT_FLAG_F64, book-1 scenes)."""
+    def __init__(self, scene: SceneData, device: int = 0, f64: bool = False, device_bvh: bool = False):
+        """f64=True: the books path's f64 kernel (RRT_FLAG_F64, book-1 scenes). device_bvh=True: the
+        BVH is built on the device (RRT_FLAG_DEVICE_BVH) instead of the host."""
         lib = _lib.load()
         self.scene = scene
-        flags = scene.flags | (_lib.FLAG_F64 if f64 else 0)
+        flags = scene.flags | (_lib.FLAG_F64 if f64 else 0) | (_lib.FLAG_DEVICE_BVH if device_bvh else 0)
         self._lib = lib
         self._h = ctypes.c_void_p()
         tex, ntex, keep = _textures(scene)
@@ -376,3 +404,15 @@ class DeviceScene:
         b = _lib.RrtBvhInfo()
         _lib.check(self._lib.rrt_scene_bvh_info(self._h, ctypes.byref(b)))
         return b.as_dict()
+
+    def read_bvh(self):
+        """rrt_scene_read_bvh: the node bytes (uint8) and leaf order (uint32) this scene holds on its
+        device, with either builder, and the info dict (as build_bvh returns them)."""
+        info = self.bvh_info()
+        ext, keep = scene_ext(self.scene)
+        n_prims = len(self.scene.spheres) + (0 if ext is None else ext.n_quads + ext.n_media)
+        del keep
+        nodes = np.zeros(info["node_bytes"], dtype=np.uint8)
+        order = np.zeros(max(n_prims, 1), dtype=np.uint32)
+        _lib.check(self._lib.rrt_scene_read_bvh(self._h, _lib.ptr(nodes), nodes.size, _lib.ptr(order)))
+        return nodes, order[:n_prims], info
