@@ -623,6 +623,13 @@ void rrt_testing_device_wrap(int32_t on);
  * Process-wide. */
 void rrt_testing_f64_layout(int32_t layout);
 
+/* Test support, not part of the drop-in (RRT_ABI_VERSION is unchanged and the Rust shim does not bind
+ * it): a BVH2 node link as the f32 kernel stages it in LDS — the child's byte offset in the staged
+ * node array (index x 80) for an inner link, the word itself for a leaf link (first primitive |
+ * count << 28, count > 0). The function the kernel's staging loop applies; no device is needed
+ * (tests/test_lds_links.py). */
+uint32_t rrt_testing_lds_node_link(uint32_t link);
+
 /* Test support, not part of the drop-in (no reference counterpart; RRT_ABI_VERSION is unchanged and
  * the Rust shim does not bind it): the launch shape the library picks for a scene, computed on the
  * host from the scene's counts alone by the code the render launches and rrt_scene_create use. No

@@ -86,6 +86,7 @@ EXPORTED_SYMBOLS = (
     "rrt_hip_render_f64_rgb8",
     "rrt_testing_device_wrap",
     "rrt_testing_f64_layout",
+    "rrt_testing_lds_node_link",
     "rrt_testing_launch_plan",
     "rrt_testing_recip_check",
     "rrt_testing_trig32_check",
@@ -356,6 +357,7 @@ def load() -> ctypes.CDLL:
                                               P]),
         "rrt_testing_device_wrap": (None, [c_int32]),
         "rrt_testing_f64_layout": (None, [c_int32]),
+        "rrt_testing_lds_node_link": (c_uint32, [c_uint32]),
         "rrt_testing_launch_plan": (c_int32, [P, P]),
         "rrt_testing_recip_check": (c_int32, [P]),
         "rrt_testing_trig32_check": (c_int32, [P]),

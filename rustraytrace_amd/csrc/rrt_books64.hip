@@ -587,7 +587,7 @@ struct Trav64 {
 // and the farther one pushed. The visiting order only prunes: the closest hit is the smallest
 // accepted root whatever the order (exact ties aside), as with BvhNode::hit's left-first walk.
 template <bool kCount, typename Node, typename Stack>
-__device__ __forceinline__ bool trav_node64(const Node *__restrict__ nodes, Stack &stack, const RayK64 &rk,
+__device__ __forceinline__ void trav_node64(const Node *__restrict__ nodes, Stack &stack, const RayK64 &rk,
                                             Trav64 &t, Leaves &lv, Counters &cnt) {
     if (kCount) { cnt.nodes++; cnt.boxes += 2; }
     bool h0, h1;
@@ -613,11 +613,12 @@ __device__ __forceinline__ bool trav_node64(const Node *__restrict__ nodes, Stac
         l0 = b.z;
         l1 = b.w;
     }
-    const uint32_t c0 = h0 ? (l0 >> kLinkCountShift) : 0u;
-    const uint32_t c1 = h1 ? (l1 >> kLinkCountShift) : 0u;
-    lv = c0 ? l0 + (c1 << kLinkCountShift) : l1;
-    if (c0) h0 = false;
-    if (c1) h1 = false;
+    // f_c: child c is a leaf that was hit (rrt_kernel.hip trav_node); lv = 0 when neither is
+    const bool f0 = h0 && l0 > kLinkFirstMask, f1 = h1 && l1 > kLinkFirstMask;
+    const uint32_t m1 = f1 ? l1 : 0u;
+    lv = f0 ? l0 + (m1 & ~kLinkFirstMask) : m1;
+    if (f0) h0 = false;
+    if (f1) h1 = false;
     if (h0 && h1) {
         const bool first1 = tn1 < tn0;
         stack.store(t.sp, first1 ? (int)l0 : (int)l1);
@@ -633,7 +634,6 @@ __device__ __forceinline__ bool trav_node64(const Node *__restrict__ nodes, Stac
         --t.sp;
         t.node = stack.load(t.sp);
     }
-    return (c0 | c1) != 0;
 }
 
 // Sphere::hit (sphere.rs:24-51) over the leaf range: oc = center - o, a = |d|^2, h = d.oc,
@@ -1078,10 +1078,7 @@ __device__ __forceinline__ void render64_body(const KParams &P) {
                     ph1 += (uint64_t)__popcll(sm);
                 }
             }
-            if (tr.node >= 0 && lv == 0) {
-                Leaves l;
-                if (trav_node64<kCount>(nodes, stack, rk, tr, l, cnt)) lv = l;
-            }
+            if (tr.node >= 0 && lv == 0) trav_node64<kCount>(nodes, stack, rk, tr, lv, cnt);
             const uint64_t pm = __ballot(lv != 0);
             const uint64_t tm = __ballot(tr.node >= 0) | pm;
             const bool leave = (uint32_t)__popcll(tm) <= min_active;

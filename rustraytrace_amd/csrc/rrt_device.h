@@ -93,9 +93,16 @@ struct Counters {
 
 // Traversal stack in LDS. 16-bit entries: the dword at (depth, wave, k) holds lanes k and
 // k+32, which the LDS serves in different cycles (2 x 32-lane groups), so no bank conflicts.
+// The f32 BVH2 node step holds its stack pointer as the LDS byte address of the lane's next free
+// entry (push / pop; empty = bottom): no depth * stride + base per access.
+template <class T>
+using LdsPtr = __attribute__((address_space(3))) T *;
+__device__ __forceinline__ uint32_t lds_addr(const void *p) { return (uint32_t)(uintptr_t)(LdsPtr<const char>)p; }
 template <typename StackT, int kBlk>
 struct LdsStack {
+    static constexpr uint32_t kStride = (uint32_t)kBlk * (uint32_t)sizeof(StackT);  // bytes between depths
     StackT *base;
+    uint32_t bottom;  // LDS address of base
     __device__ __forceinline__ void init(StackT *lds, uint32_t tid) {
         if constexpr (sizeof(StackT) == 2) {
             const uint32_t lane = tid & 63u;
@@ -103,9 +110,16 @@ struct LdsStack {
         } else {
             base = lds + tid;
         }
+        bottom = lds_addr(base);
     }
     __device__ __forceinline__ void store(int sp, int v) { base[sp * kBlk] = (StackT)v; }
     __device__ __forceinline__ int load(int sp) const { return (int)base[sp * kBlk]; }
+    static __device__ __forceinline__ void push(uint32_t &sp, int v) {
+        *(LdsPtr<StackT>)(uintptr_t)sp = (StackT)v;
+        sp += kStride;
+    }
+    // pop: sp -= kStride, then the entry there
+    static __device__ __forceinline__ int top(uint32_t sp) { return (int)*(LdsPtr<const StackT>)(uintptr_t)sp; }
 };
 
 // A lane's postponed leaf tests: primitives [first, first + count), packed first | count << 28

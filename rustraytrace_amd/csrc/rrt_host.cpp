@@ -2084,6 +2084,9 @@ extern "C" void rrt_testing_device_wrap(int32_t on) { g_device_wrap.store(on != 
 // bits; tests/test_gpu_books64.py reaches each fallback with it). -1 restores the automatic choice.
 extern "C" void rrt_testing_f64_layout(int32_t layout) { rrt::set_f64_layout(layout); }
 
+// Test support (rrt_testing_lds_node_link): the link rule of the f32 kernel's LDS staging loop.
+extern "C" uint32_t rrt_testing_lds_node_link(uint32_t link) { return rrt::lds_node_link(link); }
+
 // Test support (rrt_testing_launch_plan): the launch plan of a scene given by its counts, through the
 // same rrt::plan_launch / perlin_fits_lds the launches and scene creation use; no device needed.
 extern "C" int32_t rrt_testing_launch_plan(const RrtLaunchPlanQuery *q, RrtLaunchPlan *out) {

@@ -36,6 +36,14 @@ static_assert(sizeof(GNodeH) == 32, "GNodeH must be 32 B");
 constexpr uint32_t kLinkCountShift = 28;
 constexpr uint32_t kLinkFirstMask = (1u << kLinkCountShift) - 1u;
 constexpr uint32_t kMaxLeafPrims = 7;  // two leaf children's counts share one 4-bit field
+// A GNode link as the f32 kernel stages it in LDS: the node array sits at LDS offset 0, so an inner
+// link (count 0) becomes the child's byte offset there — the address the node step reads, with no
+// index * 80 per visit — and a leaf link (first primitive | count << 28) stays what it is. A staged
+// scene is at most kLdsSceneBudget (40 KB), so every offset fits a 16-bit stack entry; the root is
+// still 0. Nodes read from global memory (GNodeH) keep indices.
+__host__ __device__ constexpr uint32_t lds_node_link(uint32_t link) {
+    return link > kLinkFirstMask ? link : link * (uint32_t)sizeof(GNode);
+}
 constexpr uint32_t kMaxUnbounded = 4;  // media tested outside the BVH (rrt_host.cpp unbounded_media)
 
 // BVH4 node, 128 B: the boxes of 4 children as SoA float4s (child c in component c), the

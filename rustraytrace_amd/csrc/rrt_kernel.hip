@@ -26,6 +26,7 @@
 #include "../../include/rrt_hip.h"  // RrtDeviceOp (the test-only rrt_device_ops kernel)
 
 #include <algorithm>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <type_traits>
@@ -252,13 +253,22 @@ __device__ __forceinline__ bool box_hit(float lx, float hx, float ly, float hy, 
 // the ray's sign offsets): fma is monotonic in P for a fixed multiplier, so the entry plane's
 // distance is exactly min(t_lo, t_hi) and the exit plane's exactly the max — the same values
 // and decisions as box_hit, without its six min/max.
+// tmax (the closest hit, carried round the traversal loop) joins the exit through v_min_f32 itself:
+// __builtin_fminf on a value the compiler cannot prove canonical first quiets it with a
+// v_max_f32 x, x, x per node step. The exit only feeds the comparison, and min over the same four
+// values in another order is the same number (NaN operands are dropped either way).
+__device__ __forceinline__ float min_f32_raw(float a, float b) {
+    float r;
+    asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
 __device__ __forceinline__ bool box_hit_ordered(float nx, float fx, float ny, float fy, float nz, float fz, V3 inv,
                                                 V3 oi, float tmin, float tmax, float &tnear) {
     const float x0 = __builtin_fmaf(nx, inv.x, -oi.x), x1 = __builtin_fmaf(fx, inv.x, -oi.x);
     const float y0 = __builtin_fmaf(ny, inv.y, -oi.y), y1 = __builtin_fmaf(fy, inv.y, -oi.y);
     const float z0 = __builtin_fmaf(nz, inv.z, -oi.z), z1 = __builtin_fmaf(fz, inv.z, -oi.z);
     const float nr = __builtin_fmaxf(__builtin_fmaxf(x0, y0), __builtin_fmaxf(z0, tmin));
-    const float fr = __builtin_fminf(__builtin_fminf(x1, y1), __builtin_fminf(z1, tmax));
+    const float fr = min_f32_raw(__builtin_fminf(__builtin_fminf(x1, y1), z1), tmax);
     tnear = nr;
     return nr < fr;
 }
@@ -648,15 +658,16 @@ __device__ __forceinline__ void test_range(const PR &prim_cr, int first, int cou
 struct Trav {
     float closest;  // the best hit's root
     int hit_prim;
-    int node;
-    int sp;
+    int node;     // node index; BVH2 staged in LDS: the node's LDS address (lds_node_link); -1 = done
+    uint32_t sp;  // stack depth; BVH2: LDS address of the lane's next free stack entry (LdsStack::push)
 };
 
-__device__ __forceinline__ void trav_begin(Trav &t) {
+// root: 0, or the staged BVH2 node array's LDS address; sp0: 0, or the BVH2 stack's bottom
+__device__ __forceinline__ void trav_begin(Trav &t, int root, uint32_t sp0) {
     t.closest = __builtin_inff();  // camera.rs:187 Interval(0.001, INFINITY)
     t.hit_prim = -1;
-    t.node = 0;
-    t.sp = 0;
+    t.node = root;
+    t.sp = sp0;
 }
 
 
@@ -664,28 +675,30 @@ __device__ __forceinline__ void trav_begin(Trav &t) {
 // closest hit, records leaf children in `lv` (tested later, before this lane's next node
 // visit), descends into the nearer internal child and pushes the farther one; t.node = -1
 // when nothing is left to visit. The next node depends only on these box results, so
-// testing the leaves later keeps every ray's sequence of operations unchanged. Returns
-// true when leaf tests are pending.
+// testing the leaves later keeps every ray's sequence of operations unchanged. lv = 0
+// when no leaf tests are pending. A staged GNode's inner links, t.node and the stack entries
+// are byte offsets (lds_node_link); GNodeH links are indices.
 template <bool kCount, bool kOrd16, typename Node, typename Stack>
-__device__ __forceinline__ bool trav_node(const Node *__restrict__ nodes, Stack &stack, const RayK &rk, Trav &t,
+__device__ __forceinline__ void trav_node(const Node *__restrict__ nodes, Stack &stack, const RayK &rk, Trav &t,
                                           Leaves &lv, Counters &cnt) {
     if (kCount) { cnt.nodes++; cnt.boxes += 2; }
     float tn0 = 0.0f, tn1 = 0.0f;
     bool h0, h1;
     uint32_t l0, l1;
     if constexpr (std::is_same<Node, GNode>::value) {
-        // node * 80 as a 24-bit multiply (full rate; node indices < 2^24)
-        const GNode &n = *reinterpret_cast<const GNode *>(reinterpret_cast<const char *>(nodes) +
-                                                           __umul24((uint32_t)t.node, (uint32_t)sizeof(GNode)));
+        // t.node is the node's LDS address (its byte offset in the staged array, lds_node_link, which
+        // starts the block's LDS): the fields at immediate offsets, no index * 80 per visit
+        static_assert(offsetof(GNode, box) == 0, "GNode planes start the record");
+        const uint32_t bx = (uint32_t)t.node;
         // LDS: each plane pair read at the ray's sign offset (ds_read2_b32), no min/max
-        const char *bx = reinterpret_cast<const char *>(&n.box[0][0]);
-        auto plane = [&](uint32_t byte_off) { return *reinterpret_cast<const float *>(bx + byte_off); };
+        auto plane = [&](uint32_t byte_off) { return *(LdsPtr<const float>)(uintptr_t)(bx + byte_off); };
         h0 = box_hit_ordered(plane(rk.ox), plane(rk.ox + 4), plane(rk.oy), plane(rk.oy + 4), plane(rk.oz),
                              plane(rk.oz + 4), rk.inv, rk.oi, 0.001f, t.closest, tn0);
         h1 = box_hit_ordered(plane(rk.ox + 36), plane(rk.ox + 40), plane(rk.oy + 36), plane(rk.oy + 40),
                              plane(rk.oz + 36), plane(rk.oz + 40), rk.inv, rk.oi, 0.001f, t.closest, tn1);
-        l0 = n.link[0];
-        l1 = n.link[1];
+        const LdsPtr<const uint32_t> lk = (LdsPtr<const uint32_t>)(uintptr_t)(bx + (uint32_t)offsetof(GNode, link));
+        l0 = lk[0];
+        l1 = lk[1];
     } else {
         // global memory (scenes beyond the LDS budget): the 32-B f16 node in two 16-B loads and
         // the min/max slab (per-lane dword gathers cost more there than the min/max)
@@ -739,27 +752,29 @@ __device__ __forceinline__ bool trav_node(const Node *__restrict__ nodes, Stack 
     // Leaf children (count in the link's top bits, 0 = internal) are postponed; the hit ones
     // form one range: sibling leaves are adjacent in primitive order, so l0's first primitive
     // continues into l1's.
-    const uint32_t c0 = h0 ? (l0 >> kLinkCountShift) : 0u;
-    const uint32_t c1 = h1 ? (l1 >> kLinkCountShift) : 0u;
-    lv = c0 ? l0 + (c1 << kLinkCountShift) : l1;
-    if (c0) h0 = false;
-    if (c1) h1 = false;
+    // f_c: child c is a leaf that was hit. lv = l0 with l1's count added when both are, else the
+    // one that is, else 0 (the lane held 0: the caller's lv is assigned unconditionally).
+    const bool f0 = h0 && l0 > kLinkFirstMask, f1 = h1 && l1 > kLinkFirstMask;
+    const uint32_t m1 = f1 ? l1 : 0u;
+    lv = f0 ? l0 + (m1 & ~kLinkFirstMask) : m1;
+    if (f0) h0 = false;
+    if (f1) h1 = false;
     if (h0 && h1) {
         const bool first1 = tn1 < tn0;
-        stack.store(t.sp, first1 ? (int)l0 : (int)l1);
-        ++t.sp;
+        Stack::push(t.sp, first1 ? (int)l0 : (int)l1);
         t.node = first1 ? (int)l1 : (int)l0;
     } else if (h0) {
         t.node = (int)l0;
     } else if (h1) {
         t.node = (int)l1;
-    } else if (t.sp == 0) {
-        t.node = -1;
     } else {
-        --t.sp;
-        t.node = stack.load(t.sp);
+        // pop, or done on an empty stack: the step back is unconditional (a lane that is done takes
+        // its stack pointer from trav_begin again), the read is not
+        const bool more = t.sp != stack.bottom;
+        t.node = -1;
+        t.sp -= Stack::kStride;
+        if (more) t.node = Stack::top(t.sp);
     }
-    return (c0 | c1) != 0;
 }
 
 // The postponed leaf tests of one node visit (leaf 0's primitives, then leaf 1's).
@@ -1440,8 +1455,13 @@ __device__ __forceinline__ void trace_segment(uint32_t xy, uint32_t s, const Pat
 template <bool kLds, bool kCount, typename StackT, bool kWide, int kBook2, int kBlk, bool kNoise>
 __device__ __forceinline__ void render_body(const KParams &P) {
     extern __shared__ uint4 lds_dyn[];
-    // LDS layout: [traversal stack: stack_depth x kBlk x StackT, 16-B aligned][nodes][primitives]
-    StackT *lds_stack = reinterpret_cast<StackT *>(lds_dyn);
+    // LDS layout. Scene staged (kLds): [nodes][primitives][materials][motion][Perlin tables][traversal
+    // stack: stack_depth x kBlk x StackT] — the node array at offset 0, so a staged BVH2 link is the
+    // node's LDS address (lds_node_link). Scene in global memory: [stack, 16-B aligned][Perlin tables].
+    // Both add up to f32_lds_bytes.
+    uint32_t stack16 = 0;  // the stack's offset in 16-B units
+    // LDS address of the staged BVH2 node array, the root's t.node (dynamic LDS starts the block's LDS: 0)
+    [[maybe_unused]] const uint32_t node_base = kLds && !kWide ? lds_addr(lds_dyn) : 0u;
     // BVH2 nodes: sign-ordered 80-B GNode when staged in LDS, 32-B f16 GNodeH in global memory
     using Node = typename std::conditional<kWide, GNode4, typename std::conditional<kLds, GNode, GNodeH>::type>::type;
     const Node *nodes = reinterpret_cast<const Node *>(P.nodes);
@@ -1450,18 +1470,31 @@ __device__ __forceinline__ void render_body(const KParams &P) {
     const float4 *motion = P.prim_motion;
     if constexpr (kLds) {
         // Stage the whole BVH + spheres + their materials (KB-sized) in LDS once per block.
-        uint4 *dst = lds_dyn + (P.stack_depth * kBlk * sizeof(StackT) + 15u) / 16u;
+        uint4 *dst = lds_dyn;
         const uint4 *src_n = reinterpret_cast<const uint4 *>(P.nodes);
-        const uint32_t nn = P.n_nodes * (uint32_t)(sizeof(Node) / 16);
-        for (uint32_t i = threadIdx.x; i < nn; i += kBlk) dst[i] = src_n[i];
+        constexpr uint32_t kNode16 = (uint32_t)(sizeof(Node) / 16);
+        const uint32_t nn = P.n_nodes * kNode16;
+        for (uint32_t i = threadIdx.x; i < nn; i += kBlk) {
+            uint4 v = src_n[i];
+            if constexpr (!kWide) {  // the links are the last two words of a GNode
+                static_assert(offsetof(GNode, link) == sizeof(GNode) - 8, "GNode links end the record");
+                if (i % kNode16 == kNode16 - 1u) {
+                    v.z = lds_node_link(v.z) + (v.z > kLinkFirstMask ? 0u : node_base);
+                    v.w = lds_node_link(v.w) + (v.w > kLinkFirstMask ? 0u : node_base);
+                }
+            }
+            dst[i] = v;
+        }
         const uint4 *src_p = reinterpret_cast<const uint4 *>(P.prim_cr);
         for (uint32_t i = threadIdx.x; i < P.n_prims; i += kBlk) dst[nn + i] = src_p[i];
         const uint4 *src_m = reinterpret_cast<const uint4 *>(P.prim_mtl);
         const uint32_t nm = P.n_prims * (uint32_t)(sizeof(GMaterial) / 16);
         for (uint32_t i = threadIdx.x; i < nm; i += kBlk) dst[nn + P.n_prims + i] = src_m[i];
+        stack16 = nn + P.n_prims + nm;
         if constexpr (kBook2 > 0) {
             const uint4 *src_v = reinterpret_cast<const uint4 *>(P.prim_motion);
             for (uint32_t i = threadIdx.x; i < P.n_prims; i += kBlk) dst[nn + P.n_prims + nm + i] = src_v[i];
+            stack16 += P.n_prims;
         }
         __syncthreads();
         nodes = reinterpret_cast<const Node *>(dst);
@@ -1475,16 +1508,18 @@ __device__ __forceinline__ void render_body(const KParams &P) {
     const GPerlin *perlin = P.perlin;
     if constexpr (kBook2 > 0) {
         if (P.perlin_in_lds) {
-            size_t off16 = (P.stack_depth * kBlk * sizeof(StackT) + 15u) / 16u;
-            if constexpr (kLds) off16 += P.n_nodes * (uint32_t)(sizeof(Node) / 16) + 3u * P.n_prims + P.n_prims;
+            size_t off16 = stack16;
+            if constexpr (!kLds) off16 = (P.stack_depth * kBlk * sizeof(StackT) + 15u) / 16u;
             uint4 *dst = lds_dyn + off16;
             const uint4 *src = reinterpret_cast<const uint4 *>(P.perlin);
             const uint32_t n16 = P.n_perlin * (uint32_t)(sizeof(GPerlin) / 16);
             for (uint32_t i = threadIdx.x; i < n16; i += kBlk) dst[i] = src[i];
             __syncthreads();
             perlin = reinterpret_cast<const GPerlin *>(dst);
+            if constexpr (kLds) stack16 += n16;
         }
     }
+    StackT *lds_stack = reinterpret_cast<StackT *>(lds_dyn + stack16);
     LdsStack<StackT, kBlk> stack;
     stack.init(lds_stack, threadIdx.x);
 
@@ -1600,7 +1635,7 @@ __device__ __forceinline__ void render_body(const KParams &P) {
             if (ps.k >= P.max_depth) {  // ray_color: depth <= 0 -> 0 (no query)
                 seg_done = 1;
             } else {
-                trav_begin(tr);
+                trav_begin(tr, kWide ? 0 : (int)node_base, kWide ? 0u : stack.bottom);
                 need_ray = 0;
                 started = 1;
             }
@@ -1638,6 +1673,10 @@ __device__ __forceinline__ void render_body(const KParams &P) {
             const uint32_t leaf_min = (live * P.leaf_frac) >> 8;
             __builtin_amdgcn_s_setprio(RRT_PRIO_NODE);  // the node steps (phase priorities: see the loop head)
             Leaves lv = 0;  // the postponed leaf range (0 = none: a range has count >= 1)
+            // the lanes that take the next node step — in the tree, no leaf tests pending — as a lane
+            // mask: the loop's bottom ballots decide it, so the step's own test costs no compare
+            // (wave-uniform assignments only: a scalar register pair, not a divergent bool)
+            uint64_t step = __ballot(tr.node >= 0);
             for (;;) {
                 if constexpr (RRT_PHASE_TIMING == 2) {
                     ph0 += 64;
@@ -1656,22 +1695,22 @@ __device__ __forceinline__ void render_body(const KParams &P) {
                         }
                     }
                 }
-                if (tr.node >= 0 && lv == 0) {
-                    Leaves l;
-                    if (trav_node<kCount, kOrd16>(nodes, stack, rk, tr, l, cnt)) lv = l;
-                }
+                if (__builtin_amdgcn_inverse_ballot_w64(step)) trav_node<kCount, kOrd16>(nodes, stack, rk, tr, lv, cnt);
                 // wave-uniform decisions in scalar registers, without short-circuit branches:
                 // pm = lanes waiting on leaf tests, tm = lanes still in the tree (pm is a subset)
                 const uint64_t pm = __ballot(lv != 0);
-                const uint64_t tm = __ballot(tr.node >= 0) | pm;
+                const uint64_t nm = __ballot(tr.node >= 0);
+                const uint64_t tm = nm | pm;
                 const bool leave = (uint32_t)__popcll(tm) <= min_active;
                 const bool batch = ((uint32_t)__popcll(pm) > leaf_min) | leave | (tm == pm);
+                step = nm & ~pm;
                 if ((pm != 0) & batch) {
                     __builtin_amdgcn_s_setprio(RRT_PRIO_LEAF);
-                    if (lv != 0) {
+                    if (__builtin_amdgcn_inverse_ballot_w64(pm)) {
                         trav_leaves<kCount, kHoldRa>(pr, lv, ps.o, ps.d, rk, ps.skip, tr, cnt);
                         lv = 0;
                     }
+                    step = nm;  // the batch tests every pending range and leaves tr.node alone
                     __builtin_amdgcn_s_setprio(RRT_PRIO_NODE);
                 }
                 if (leave) break;
@@ -1894,8 +1933,8 @@ int f32_class(const KParams &p) {
     return p.image_tex ? 0 : kBook1Untextured;
 }
 
-// Dynamic LDS of a block: the one formula (the kernel's carve-up: stack, nodes, primitives, motion,
-// Perlin tables, rrt_device.h / render_body).
+// Dynamic LDS of a block: the one formula (the kernel's carve-up, render_body: nodes, primitives,
+// motion, Perlin tables, then the stack for a staged scene; the stack, then the Perlin tables otherwise).
 size_t f32_lds_bytes(const KParams &p, int cls, const ArmShape &s, bool lds) {
     size_t n = ((size_t)p.stack_depth * (size_t)s.threads * (size_t)s.stack_bytes + 15u) / 16u * 16u;
     if (lds)
@@ -1980,6 +2019,8 @@ hipError_t launch_variant(const KParams &p, const LaunchPlan &pl, bool count, hi
     if (pl.arm != kArm || pl.kclass != kBook2 || pl.threads != (uint32_t)kBlk || pl.scene_in_lds != (kLds ? 1u : 0u) ||
         (p.bvh_width == 4) != kWide)
         return hipErrorInvalidValue;  // the plan names another instantiation
+    // staged BVH2 links are byte offsets held in 16-bit stack entries (lds_node_link)
+    if (kLds && !kWide && sizeof(StackT) == 2 && (size_t)p.n_nodes * sizeof(GNode) > 65536u) return hipErrorInvalidValue;
     const size_t lds = (size_t)pl.lds_bytes;
     auto kernel = count                       ? rrt_render<kLds, true, StackT, kWide, kWaves, kBook2, kBlk, (kBook2 > 0)>
                   : !kNoiseFree || p.n_perlin ? rrt_render<kLds, false, StackT, kWide, kWaves, kBook2, kBlk, (kBook2 > 0)>
