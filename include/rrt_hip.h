@@ -231,6 +231,18 @@ typedef struct RrtOverrides {
  * root-leaf form and is written by the host builder. RrtBvhInfo.max_leaf_param then reports the kept
  * shape's leaf size. Without the flag nothing changes. */
 #define RRT_FLAG_DEVICE_BVH 0x10u
+/* The f64 books path for the slice of book 2 its kernel covers (additive; RRT_ABI_VERSION is
+ * unchanged). Implies RRT_FLAG_F64. rrt_scene_create_ex then also accepts sphere_motion (needs
+ * RRT_FLAG_RAY_TIME, as for f32: the path keeps the camera's time draw and every sphere is tested at
+ * center1 + time * motion, the_next_week/sphere.rs:44), quads (quad.rs:61-87 on the unrounded f64
+ * plane; Lambertian, checker, metal, dielectric or diffuse-light materials) and material kinds 0-5 on
+ * spheres (checker textures, texture.rs:66-77; kind 3 image textures as for RRT_FLAG_F64). Bit-identical
+ * to the reference's CPU books path on the_next_week scenes 1, 2, 5 and 7 (exact t-ties between two
+ * primitives aside, which go by tree order on either side). Still RRT_E_INVALID, before any device
+ * call: Perlin tables or kind 6, media, boundary quads or kind 7, lights or RRT_FLAG_BOOK3, more than
+ * 65535 BVH nodes; the message names this flag and the item. A book-1 scene created with the flag
+ * renders the bits RRT_FLAG_F64 alone renders. RRT_FLAG_F64 alone keeps refusing book-2 data. */
+#define RRT_FLAG_F64_BOOK2 0x20u
 
 /* ---- error codes ------------------------------------------------------------------ */
 #define RRT_OK 0
@@ -271,6 +283,16 @@ int32_t rrt_hip_render_f64(const RrtCamera *cam,
                            const RrtTexture *textures, uint32_t n_textures,
                            uint32_t total_spp, uint32_t n_gpus, uint32_t flags,
                            double *accum_out);
+
+/* rrt_hip_render_f64 with book-2 scene data: RRT_FLAG_F64 and RRT_FLAG_F64_BOOK2 are implied; ext
+ * may be NULL (then it is rrt_hip_render_f64). Same multi-device path. */
+int32_t rrt_hip_render_f64_ex(const RrtCamera *cam,
+                              const RrtSphere *spheres, uint32_t n_spheres,
+                              const RrtMaterial *materials, uint32_t n_materials,
+                              const RrtTexture *textures, uint32_t n_textures,
+                              const RrtSceneExt *ext,
+                              uint32_t total_spp, uint32_t n_gpus, uint32_t flags,
+                              double *accum_out);
 
 /* Thread-local message for the last failing call on this thread ("" if none). */
 const char *rrt_hip_last_error(void);
@@ -589,14 +611,23 @@ int32_t rrt_quantize_accum_books_f64_async(uint32_t n_pixels, const double *d_ac
 /* rrt_hip_render_f64 (RRT_FLAG_F64 is implied; book-1 scenes), then the books path's quantiser on
  * each device: rgb8_out[3*W*H] holds the bytes camera.rs:87-94 prints through color.rs — identical
  * to rrt_quantize_accum_books_f64 of rrt_hip_render_f64's accum_out with samples_per_pixel =
- * total_spp. Format them with rrt_format_pnm_from_rgb8. There is no _ex form: the f64 kernel takes
- * no RrtSceneExt. */
+ * total_spp. Format them with rrt_format_pnm_from_rgb8. The _ex form below takes an
+ * RrtSceneExt. */
 int32_t rrt_hip_render_f64_rgb8(const RrtCamera *cam,
                                 const RrtSphere *spheres, uint32_t n_spheres,
                                 const RrtMaterial *materials, uint32_t n_materials,
                                 const RrtTexture *textures, uint32_t n_textures,
                                 uint32_t total_spp, uint32_t n_gpus, uint32_t flags,
                                 uint8_t *rgb8_out);
+/* The same with book-2 scene data (RRT_FLAG_F64 and RRT_FLAG_F64_BOOK2 implied; ext may be NULL):
+ * rrt_hip_render_f64_ex, then the books quantiser on each device. */
+int32_t rrt_hip_render_f64_rgb8_ex(const RrtCamera *cam,
+                                   const RrtSphere *spheres, uint32_t n_spheres,
+                                   const RrtMaterial *materials, uint32_t n_materials,
+                                   const RrtTexture *textures, uint32_t n_textures,
+                                   const RrtSceneExt *ext,
+                                   uint32_t total_spp, uint32_t n_gpus, uint32_t flags,
+                                   uint8_t *rgb8_out);
 
 /* PNM from quantised pixels: binary = 0 -> P3 text byte-identical to
  * rrt_format_ppm_from_accum of the same image; binary = 1 -> P6 ("P6\nW H\n255\n" + rgb8).
@@ -638,18 +669,20 @@ uint32_t rrt_testing_lds_node_link(uint32_t link);
  * 80 (BVH2 staged in LDS), 32 (BVH2 read from global memory) or 128 (the width-4 tree, staged when
  * bvh4_in_lds); book 0 (book 1), 2 (the scene has book-2 data: motion, quads, media, checker / noise
  * materials) or 3 (RRT_FLAG_BOOK3); specular / image_tex: some material is metal or dielectric /
- * image-textured; n_perlin, n_media, n_quads as in RrtSceneExt; f64: RRT_FLAG_F64; min_waves /
+ * image-textured; n_perlin, n_media, n_quads as in RrtSceneExt; f64: RRT_FLAG_F64; f64_book2:
+ * RRT_FLAG_F64_BOOK2 (with f64 = 1 and book = 2: the f64 kernel's book-2 class, ok = 0 with n_perlin or
+ * n_media; 0 leaves every other answer as it was); min_waves /
  * global_waves: 0 for the defaults (the RRT_MIN_WAVES / RRT_GLOBAL_WAVES overrides otherwise).
  * Result: ok = 0 when rrt_scene_create refuses such a scene (no launch shape), else the kernel class
  * (f32: -2 diffuse, -1 untextured, 0 full book 1, 1-3 book 2 spheres / quads / media, 4 book 3; f64:
- * 0 full, 1 untextured, 2 diffuse), its block (threads, launch-bounds waves per SIMD, 1 = none),
+ * 0 full, 1 untextured, 2 diffuse, 3 book 2), its block (threads, launch-bounds waves per SIMD, 1 = none),
  * bytes per stack entry, what is staged in LDS, the block's dynamic LDS bytes, and raise_limit = 1
  * when those exceed 64 KiB and the launch raises the kernel's dynamic-LDS limit (at most 160 KiB). */
 typedef struct RrtLaunchPlanQuery {
     uint32_t n_nodes, n_prims, stack_depth, node_stride;
     uint32_t book, specular, image_tex, n_perlin;
     uint32_t n_media, n_quads, f64, bvh4_in_lds;
-    uint32_t min_waves, global_waves, _pad[2];
+    uint32_t min_waves, global_waves, f64_book2, _pad;
 } RrtLaunchPlanQuery;
 typedef struct RrtLaunchPlan {
     uint32_t ok, f64;
@@ -748,7 +781,7 @@ int32_t rrt_testing_div_check(const float *a_values, uint32_t n_a, uint64_t *out
  * applied elementwise on the device (tests/test_gpu_device_ops64.py compares every result bit for
  * bit with the oracle's f64 path or with the IEEE operation). `in` holds n rows of f64 columns, `out`
  * receives n rows of 64-bit words (f64 bits unless noted; i32 and flags zero-extended from 32 bits);
- * host pointers, copied inside. Row i runs on lane i % 64 of wave i / 64. aux: none (pass NULL).
+ * host pointers, copied inside. Row i runs on lane i % 64 of wave i / 64. aux: QUAD64's records, else NULL.
  *   op           in columns                        out columns
  *   ACOS64       x                                 rrt_acos64(x)
  *   ATAN2_64     y, x                              rrt_atan2_64(y, x)
@@ -770,6 +803,10 @@ int32_t rrt_testing_div_check(const float *a_values, uint32_t n_a, uint64_t *out
  *                                                  (float4) and then the record widened as the LDS staging widens it
  *                                                  (Sphere64): exact_root64, leaves64's decision over a one-sphere
  *                                                  leaf against `closest` (hit u32, t: `closest` on a miss). 6 words.
+ *   QUAD64       o.xyz, d.xyz, tmin, closest, j    quad_hit64 of quad j over the closed [tmin, closest]: hit (u32), t (0 on
+ *                                                  a miss). aux: u32 count, 12 bytes of padding, then count RrtQuad
+ *                                                  records (f64 planes formed by scene creation's code); j < count
+ *   CHECKER64    inv_scale, p.xyz                  checker_even64 (u32 0 / 1)
  * Every input, NaN and infinities included, is ordinary arithmetic. */
 enum RrtDeviceOp64 {
     RRT_OP_ACOS64 = 0,
@@ -781,7 +818,9 @@ enum RrtDeviceOp64 {
     RRT_OP_ATT64 = 6,
     RRT_OP_VEC64 = 7,
     RRT_OP_TEXEL64 = 8,
-    RRT_OP_SPHERE64 = 9
+    RRT_OP_SPHERE64 = 9,
+    RRT_OP_QUAD64 = 10,
+    RRT_OP_CHECKER64 = 11
 };
 int32_t rrt_testing_device_ops64(uint32_t op, uint32_t n, const void *in, void *out, const void *aux);
 

@@ -40,6 +40,7 @@ FLAG_QUIET = 0x2
 FLAG_BOOK3 = 0x4
 FLAG_F64 = 0x8  # the books path's f64 arithmetic (include/rrt_hip.h RRT_FLAG_F64)
 FLAG_DEVICE_BVH = 0x10  # scene creation builds the BVH on the device (RRT_FLAG_DEVICE_BVH)
+FLAG_F64_BOOK2 = 0x20  # the f64 books path for moving spheres, quads, checker textures (RRT_FLAG_F64_BOOK2)
 
 # Every symbol include/rrt_hip.h declares (checked by tests/test_abi.py).
 EXPORTED_SYMBOLS = (
@@ -84,6 +85,8 @@ EXPORTED_SYMBOLS = (
     "rrt_quantize_accum_books_async",
     "rrt_quantize_accum_books_f64_async",
     "rrt_hip_render_f64_rgb8",
+    "rrt_hip_render_f64_ex",
+    "rrt_hip_render_f64_rgb8_ex",
     "rrt_testing_device_wrap",
     "rrt_testing_f64_layout",
     "rrt_testing_lds_node_link",
@@ -107,6 +110,7 @@ DEVICE_OPS = {
 DEVICE_OPS64 = {
     "ACOS64": (0, 1, 1), "ATAN2_64": (1, 2, 1), "DIV_A64": (2, 2, 3), "DIV_CONST64": (3, 1, 4), "SQRT64": (4, 1, 1),
     "AS_I32": (5, 1, 1), "ATT64": (6, 2, 4), "VEC64": (7, 9, 11), "TEXEL64": (8, 5, 6), "SPHERE64": (9, 11, 6),
+    "QUAD64": (10, 9, 2), "CHECKER64": (11, 4, 1),
 }
 
 
@@ -213,7 +217,7 @@ class RrtBvhInfo(ctypes.Structure):
 class RrtLaunchPlanQuery(ctypes.Structure):  # include/rrt_hip.h, test support
     _fields_ = [(f, c_uint32) for f in ("n_nodes", "n_prims", "stack_depth", "node_stride", "book", "specular",
                                         "image_tex", "n_perlin", "n_media", "n_quads", "f64", "bvh4_in_lds",
-                                        "min_waves", "global_waves")] + [("_pad", c_uint32 * 2)]
+                                        "min_waves", "global_waves", "f64_book2", "_pad")]
 
 
 class RrtLaunchPlan(ctypes.Structure):  # include/rrt_hip.h, test support
@@ -258,15 +262,21 @@ def device_ops(op: str, rows, quads=None, perlin=None, scale=0.0) -> np.ndarray:
     return out
 
 
-def device_ops64(op: str, rows) -> np.ndarray:
+def device_ops64(op: str, rows, quads=None) -> np.ndarray:
     """rrt_testing_device_ops64 (test support): the f64 books kernel's building block `op` (a
     DEVICE_OPS64 name) on each row of `rows` (float64, n x columns in); returns the n x words-out
     results as uint64 (view as float64 where the op returns doubles). Row i runs on lane i % 64 of
-    wave i / 64."""
+    wave i / 64. quads: QUAD_DTYPE records for QUAD64."""
     code, cin, cout = DEVICE_OPS64[op]
     x = np.ascontiguousarray(rows, dtype=np.float64).reshape(-1, cin)
     out = np.zeros((len(x), cout), dtype=np.uint64)
-    check(load().rrt_testing_device_ops64(code, len(x), ptr(x), ptr(out), None))
+    aux = None
+    if op == "QUAD64":  # the aux layout of device_ops' QUAD
+        q = np.ascontiguousarray(quads, dtype=QUAD_DTYPE)
+        aux = np.zeros(16 + q.nbytes, dtype=np.uint8)
+        aux[:4] = np.frombuffer(np.uint32(len(q)).tobytes(), dtype=np.uint8)
+        aux[16:] = np.frombuffer(q.tobytes(), dtype=np.uint8)
+    check(load().rrt_testing_device_ops64(code, len(x), ptr(x), ptr(out), ptr(aux)))
     return out
 
 
@@ -353,6 +363,9 @@ def load() -> ctypes.CDLL:
         "rrt_quantize_accum_books_f64": (c_int32, [c_uint32, c_uint32, P, c_uint32, P]),
         "rrt_quantize_accum_books_async": (c_int32, [c_uint32, P, c_uint32, P, P]),
         "rrt_quantize_accum_books_f64_async": (c_int32, [c_uint32, P, c_uint32, P, P]),
+        "rrt_hip_render_f64_ex": (c_int32, [P, P, c_uint32, P, c_uint32, P, c_uint32, P, c_uint32, c_uint32, c_uint32, P]),
+        "rrt_hip_render_f64_rgb8_ex": (c_int32, [P, P, c_uint32, P, c_uint32, P, c_uint32, P, c_uint32, c_uint32, c_uint32,
+                                                 P]),
         "rrt_hip_render_f64_rgb8": (c_int32, [P, P, c_uint32, P, c_uint32, P, c_uint32, c_uint32, c_uint32, c_uint32,
                                               P]),
         "rrt_testing_device_wrap": (None, [c_int32]),

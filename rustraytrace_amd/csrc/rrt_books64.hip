@@ -27,7 +27,11 @@
 //
 // Scope: book-1 scenes (the BASELINE configs C1, C2, C4, C5: Lambertian, metal, dielectric,
 // image-textured Lambertian, diffuse light; sky or constant background). The host rejects book-2/3
-// scene data with RRT_FLAG_F64. Same work queue, chunked accumulation order and BVH (f32 boxes,
+// scene data with RRT_FLAG_F64 alone. With RRT_FLAG_F64_BOOK2 also the slice of book 2 whose
+// attenuations the 12-byte history record holds unchanged (class kF64Book2): moving spheres
+// (the_next_week/sphere.rs:24-45 at the path's time draw), quads (quad.rs:61-87 on the unrounded f64
+// plane) and checker textures (texture.rs:66-77), i.e. the_next_week scenes 1, 2, 5, 7; noise textures,
+// media and book 3 stay refused. Same work queue, chunked accumulation order and BVH (f32 boxes,
 // rounded outward and grown by the f32 slab bound, tested in f64: conservative) as the f32 kernel.
 #include "rrt_internal.h"
 #include "../../include/rrt_hip.h"  // RrtDeviceOp64 (the test-only rrt_device_ops64 kernel)
@@ -774,15 +778,93 @@ __device__ __forceinline__ void leaves64(const Rec *__restrict__ prims, const fl
     }
 }
 
+// ---- book 2 (class kF64Book2, RRT_FLAG_F64_BOOK2): moving spheres, quads, checker textures ------
+// vec3.rs:160-166 cross
+__device__ __forceinline__ D3 cross(D3 u, D3 v) {
+    return d3(u.y * v.z - u.z * v.y, u.z * v.x - u.x * v.z, u.x * v.y - u.y * v.x);
+}
+__device__ __forceinline__ D3 ld3(const double *p) { return d3(p[0], p[1], p[2]); }
+// Quad::hit (the_next_week/quad.rs:61-87) on the unrounded record: denom = normal . d, a miss when
+// |denom| < 1e-8; t = (D - normal . o) / denom, the IEEE quotient, in the closed [tmin, closest];
+// planar = (o + t * d) - q, alpha = w . (planar x v), beta = w . (u x planar), both in the closed [0, 1].
+// A NaN fails every comparison but the first, as Interval::contains does.
+__device__ __forceinline__ bool quad_hit64(const GQuad64 *__restrict__ g, D3 o, D3 d, double tmin, double closest,
+                                           double &t_out) {
+    const D3 n = ld3(g->n);
+    const double denom = dot(n, d);
+    if (__builtin_fabs(denom) < 1e-8) return false;
+    const double t = (g->D - dot(n, o)) / denom;
+    if (!(tmin <= t && t <= closest)) return false;
+    const D3 planar = sub(add(o, muls(d, t)), ld3(g->q));
+    const D3 w = ld3(g->w);
+    const double alpha = dot(w, cross(planar, ld3(g->v)));
+    const double beta = dot(w, cross(ld3(g->u), planar));
+    if (!(0.0 <= alpha && alpha <= 1.0 && 0.0 <= beta && beta <= 1.0)) return false;  // is_interior
+    t_out = t;
+    return true;
+}
+// the quad a leaf-order record (q.xyz, -(1 + index)) names (KParams.quads)
+__device__ __forceinline__ int quad_index(const float4 &c) { return (int)(-c.w) - 1; }
+// Sphere::current_center (the_next_week/sphere.rs:44): center1 + time * (center2 - center1), Ray::at
+__device__ __forceinline__ D3 center_at(const float4 &c, const float4 &m, double time) {
+    return add(center_of(c), muls(f2d(m.x, m.y, m.z), time));
+}
+// CheckerTexture::value's parity (texture.rs:66-77): floor in f64, `as i32` (saturating, NaN -> 0),
+// the i32 sum (wrapping), even
+__device__ __forceinline__ bool checker_even64(double inv_scale, D3 p) {
+    const int xi = as_i32_rs(__builtin_floor(inv_scale * p.x)), yi = as_i32_rs(__builtin_floor(inv_scale * p.y)),
+              zi = as_i32_rs(__builtin_floor(inv_scale * p.z));
+    return (((uint32_t)xi + (uint32_t)yi + (uint32_t)zi) & 1u) == 0u;  // sum % 2 == 0
+}
+// The leaf range of a book-2 scene: spheres at the ray's time (every sphere of such a scene, zero
+// motion rows included, as World::book2 does: c + time * 0 = c) with leaves64's root selection over
+// the open (0.001, closest), quads over the closed [0.001, closest]. The motion rows and the quad
+// records are read from global memory.
+template <bool kCount>
+__device__ __forceinline__ void leaves64_b2(const float4 *__restrict__ prims, const float4 *__restrict__ motion,
+                                            const GQuad64 *__restrict__ quads, Leaves lv, D3 o, D3 d, double a,
+                                            double time, Trav64 &t, Counters &cnt) {
+    const double ra = recip_a64(a);
+    const int first = (int)(lv & kLinkFirstMask), count = (int)(lv >> kLinkCountShift);
+    if (kCount) cnt.spheres += (uint32_t)count;
+    for (int i = first; i < first + count; ++i) {
+        const float4 cr = prims[i];
+        if (cr.w < 0.0f) {
+            double tq;
+            if (quad_hit64(quads + quad_index(cr), o, d, 0.001, t.closest, tq)) {
+                t.closest = tq;
+                t.closest32 = (float)tq;
+                t.hit_prim = i;
+            }
+            continue;
+        }
+        const D3 oc = sub(center_at(cr, motion[i], time), o);
+        const double h = dot(d, oc);
+        const double c = dot(oc, oc) - radius_sq_of(cr);
+        const double disc = h * h - a * c;
+        if (disc < 0.0) continue;
+        const double root = root64(h, sqrt64(disc), a, ra);
+        if (0.001 < root && root < t.closest) {
+            t.closest = root;
+            t.closest32 = (float)root;
+            t.hit_prim = i;
+        }
+    }
+}
+
 struct Path64 {
     D3 o, d;
     RngState rng;
     uint32_t k;  // bounce index (camera ray = 0)
+    float time;  // kF64Book2: the camera ray's time draw, kept across bounces (24 bits: exact in f32)
 };
 
 // Camera::get_ray (camera.rs:152-180) in f64 from the camera block the host widened to f64
 // (KParams.cam64: the f32 ABI values cast as gpu/mod.rs:278-298 casts them; defocus_disk_u/v =
 // u/v * radius formed in f64, camera.rs:136-138).
+// kTime (kF64Book2): the time draw is kept in ps.time (0 without RRT_FLAG_RAY_TIME); else it is drawn
+// and dropped.
+template <bool kTime>
 __device__ __forceinline__ void camera_ray64(uint32_t x, uint32_t y, Path64 &ps) {
     const auto &C = *kernarg_params();
     const double ox = rnd64(ps.rng) - 0.5, oy = rnd64(ps.rng) - 0.5;  // sample_square
@@ -803,7 +885,12 @@ __device__ __forceinline__ void camera_ray64(uint32_t x, uint32_t y, Path64 &ps)
         const D3 dv = d3(C.cam64[5][0], C.cam64[5][1], C.cam64[5][2]);
         origin = add(add(origin, muls(du, px)), muls(dv, py));
     }
-    if (C.flags & 0x1u) (void)rnd64(ps.rng);  // RRT_FLAG_RAY_TIME: the time draw (the_next_week/camera.rs:160)
+    if constexpr (kTime) {
+        ps.time = 0.0f;
+        if (C.flags & 0x1u) ps.time = (float)(rng_next(ps.rng) >> 8) * 0x1.0p-24f;  // rnd64's value, exact in f32
+    } else {
+        if (C.flags & 0x1u) (void)rnd64(ps.rng);  // RRT_FLAG_RAY_TIME: the time draw (the_next_week/camera.rs:160)
+    }
     ps.o = origin;
     ps.d = sub(sample, origin);
     ps.k = 0;
@@ -816,8 +903,10 @@ __device__ __forceinline__ void camera_ray64(uint32_t x, uint32_t y, Path64 &ps)
 // bounce k of the lane's history.
 // kClass: kF64Full (every book-1 material kind), kF64Untextured (no image texture: the f64 acos /
 // atan2 / texel path compiled out), kF64Diffuse (Lambertian and emissive only: metal and dielectric
-// compiled out), chosen per scene by launch_render_pass_f64 like the f32 kernel's classes.
-constexpr int kF64Full = 0, kF64Untextured = 1, kF64Diffuse = 2;
+// compiled out), kF64Book2 (RRT_FLAG_F64_BOOK2 scenes: every kind 0-5, spheres at the path's time,
+// quads, checker textures; the leaf-order records of KParams.quads' comment), chosen per scene by
+// launch_render_pass_f64 like the f32 kernel's classes.
+constexpr int kF64Full = 0, kF64Untextured = 1, kF64Diffuse = 2, kF64Book2 = 3;
 template <int kClass, typename Rec>
 __device__ __forceinline__ bool shade64(const KParams &P, const Rec *prims, const GMaterial *mtl, const double *inv_r,
                                         Path64 &ps, double t, int prim, D3 &Le, const Hist64 &hist) {
@@ -837,7 +926,15 @@ __device__ __forceinline__ bool shade64(const KParams &P, const Rec *prims, cons
     const Rec cr = prims[prim];
     const D3 p = add(ps.o, muls(ps.d, t));  // Ray::at = orig + t * dir
     // (p - center) / r = (1/r) * v (vec3.rs:142-148), 1 / r from the host's table
-    const D3 outward = muls(sub(p, center_of(cr)), inv_r[prim]);
+    D3 outward;
+    if constexpr (kClass == kF64Book2) {
+        if (cr.w < 0.0f)  // quad.rs:79: the stored normal
+            outward = ld3((reinterpret_cast<const GQuad64 *>(P.quads) + quad_index(cr))->n);
+        else  // the_next_week/sphere.rs:64: the center at the ray's time
+            outward = muls(sub(p, center_at(cr, P.prim_motion[prim], (double)ps.time)), inv_r[prim]);
+    } else {
+        outward = muls(sub(p, center_of(cr)), inv_r[prim]);
+    }
     const bool front = dot(ps.d, outward) < 0.0;
     const D3 nrm = front ? outward : d3(-outward.x, -outward.y, -outward.z);
     const GMaterial m = mtl[prim];
@@ -874,6 +971,14 @@ __device__ __forceinline__ bool shade64(const KParams &P, const Rec *prims, cons
             const uint32_t b = texel_bytes64(P, m.b.z, outward);
             att = texel_value64(b);
             rec = rec_texel(b);
+        }
+        if constexpr (kClass == kF64Book2) {
+            // CheckerTexture (texture.rs:66-77): inv_scale in the fuzz slot, the odd colour in b.yzw
+            // (f32 bits); the colour chosen is the attenuation and its history record
+            if (kind == 5 && !checker_even64((double)m.a.w, p)) {
+                rec = Att32{(uint32_t)m.b.y, (uint32_t)m.b.z, (uint32_t)m.b.w};
+                att = f2d(__int_as_float(m.b.y), __int_as_float(m.b.z), __int_as_float(m.b.w));
+            }
         }
         dir = add(nrm, random_unit_vector(ps.rng));
         if (__builtin_fabs(dir.x) < 1e-8 && __builtin_fabs(dir.y) < 1e-8 && __builtin_fabs(dir.z) < 1e-8) dir = nrm;
@@ -1029,7 +1134,7 @@ __device__ __forceinline__ void render64_body(const KParams &P) {
                     sum = d3(0.0, 0.0, 0.0);
                     pkey = pixel_key(Q, x, y);
                     ps.rng = path_rng_k(pkey, s);
-                    camera_ray64(x, y, ps);
+                    camera_ray64<kClass == kF64Book2>(x, y, ps);
                     need_ray = 1;
                     has = 1;
                 }
@@ -1087,7 +1192,11 @@ __device__ __forceinline__ void render64_body(const KParams &P) {
                 __builtin_amdgcn_s_setprio(kPrioLeaf);
                 [[maybe_unused]] const uint32_t n_l = lv >> kLinkCountShift, s_l = cnt.d1;
                 if (lv != 0) {
-                    leaves64<kCount>(prims, recs32, lv, ps.o, ps.d, a, P.sphere32 != 0u, tr, cnt);
+                    if constexpr (kClass == kF64Book2)
+                        leaves64_b2<kCount>(prims, P.prim_motion, reinterpret_cast<const GQuad64 *>(P.quads), lv, ps.o,
+                                            ps.d, a, (double)ps.time, tr, cnt);
+                    else
+                        leaves64<kCount>(prims, recs32, lv, ps.o, ps.d, a, P.sphere32 != 0u, tr, cnt);
                     lv = 0;
                 }
                 if constexpr (RRT_F64_STATS == 2) {
@@ -1139,7 +1248,7 @@ __device__ __forceinline__ void render64_body(const KParams &P) {
             const uint32_t x = xy & 0xffffu, y = xy >> 16;
             if (s < s_hi) {
                 ps.rng = path_rng_k(pkey, s);
-                camera_ray64(x, y, ps);
+                camera_ray64<kClass == kF64Book2>(x, y, ps);
             } else {  // unit complete: the chunk's f64 sum, in sample order
                 const uint32_t rel = s_hi - 1u - Q.sample_begin;
                 const uint32_t nbs = Q.n_big * Q.chunk;
@@ -1192,7 +1301,13 @@ __device__ __forceinline__ void render64_body(const KParams &P) {
 constexpr int kBlock64 = RRT_F64_BLOCK;  // threads per block of the f64 kernel
 // The full class (texture + specular) needs more than 128 VGPRs (3 waves/SIMD): 512-thread blocks,
 // since a block of 1024 needs 4 waves per SIMD.
-__host__ __device__ constexpr int blk64(int cls) { return cls == 0 ? 512 : kBlock64; }
+// The book-2 class needs 143-149 VGPRs (3 waves/SIMD, no scratch; bounded to 4 waves = 128 VGPRs it
+// spills 36 B per lane): 256-thread blocks bounded to 3 waves, so three blocks share a CU. In 512-thread
+// blocks without a bound (151-158 VGPRs) only one block fits, 2 waves/SIMD: bouncing spheres 9.4
+// against 12.2 Grays/s.
+__host__ __device__ constexpr int blk64(int cls) { return cls == kF64Book2 ? 256 : cls == kF64Full ? 512 : kBlock64; }
+// the launch-bounds waves per SIMD of a class (1: no bound)
+__host__ __device__ constexpr int waves64(int cls) { return cls == kF64Book2 ? 3 : cls == kF64Full ? 1 : RRT_F64_WAVES; }
 // LDS one block may declare: 160 KiB on gfx950 (MI355X_MICROARCH.md occupancy section) when the
 // block is the CU's only one (1024 threads at 4 waves/SIMD), else the 64 KiB that keeps two
 // 512-thread blocks per CU
@@ -1204,7 +1319,7 @@ __host__ __device__ constexpr size_t lds_budget64(int blk) {
 }
 
 template <int kMode, bool kCount, int kClass>
-__global__ __launch_bounds__(blk64(kClass), kClass == kF64Full ? 1 : RRT_F64_WAVES) void rrt_render64(KParams P) {
+__global__ __launch_bounds__(blk64(kClass), waves64(kClass)) void rrt_render64(KParams P) {
     render64_body<kMode, kCount, blk64(kClass), kClass>(P);
 }
 
@@ -1385,7 +1500,6 @@ __global__ __launch_bounds__(256) void rrt_sqrt64_check(unsigned long long *out)
 // include/rrt_hip.h RrtDeviceOp64, device_op64_columns). The functions themselves, in this translation
 // unit, with the f64 kernel's flags. Row i runs on thread i of the grid, so rows map to lanes in order
 // (SQRT64's wave-uniform choice sees 64 consecutive rows).
-__device__ __forceinline__ D3 ld3(const double *p) { return d3(p[0], p[1], p[2]); }
 __device__ __forceinline__ uint64_t bits64(double x) { return (uint64_t)__double_as_longlong(x); }
 __device__ __forceinline__ void st3(uint64_t *p, D3 v) {
     p[0] = bits64(v.x);
@@ -1409,7 +1523,8 @@ __device__ __forceinline__ void sphere_ops64(const Rec &rec, const float4 &rec32
     r[2] = bits64(t.closest);
 }
 __global__ __launch_bounds__(256) void rrt_device_ops64(uint32_t op, uint32_t n, uint32_t cin, uint32_t cout,
-                                                        const double *__restrict__ in, uint64_t *__restrict__ out) {
+                                                        const double *__restrict__ in, uint64_t *__restrict__ out,
+                                                        const GQuad64 *__restrict__ quads) {
     for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n; i += gridDim.x * 256u) {
         const double *x = in + (size_t)i * cin;
         uint64_t *r = out + (size_t)i * cout;
@@ -1467,6 +1582,14 @@ __global__ __launch_bounds__(256) void rrt_device_ops64(uint32_t op, uint32_t n,
             sphere_ops64(widen_sphere64(rec), rec, o, d, x[10], r + 3);
             break;
         }
+        case RRT_OP_QUAD64: {  // the host checked j against the record count
+            double t = 0.0;
+            const bool hit = quad_hit64(quads + (int)x[8], ld3(x), ld3(x + 3), x[6], x[7], t);
+            r[0] = hit ? 1u : 0u;
+            r[1] = bits64(hit ? t : 0.0);
+            break;
+        }
+        case RRT_OP_CHECKER64: r[0] = checker_even64(x[0], ld3(x + 1)) ? 1u : 0u; break;
         default: break;
         }
     }
@@ -1513,9 +1636,13 @@ std::atomic<int> g_f64_layout{-1};
 LaunchPlan plan_launch_f64(const KParams &p) {
     LaunchPlan pl{};
     pl.f64 = 1u;
-    if (p.bvh_width != 2 || p.prim_motion || p.stack_depth > (uint32_t)kMaxStackDepth || p.n_nodes > 65535u)
-        return pl;  // the host builds a 16-bit-stack BVH2 for book-1 scenes
-    const int cls = !p.specular ? kF64Diffuse : !p.image_tex ? kF64Untextured : kF64Full;
+    // a scene with book-2 data (motion rows present) runs only as the book-2 class (RRT_FLAG_F64_BOOK2),
+    // which takes no Perlin table and no medium
+    const bool b2 = (p.flags & kFlagF64Book2) != 0;
+    if (p.bvh_width != 2 || (p.prim_motion && !b2) || p.stack_depth > (uint32_t)kMaxStackDepth || p.n_nodes > 65535u)
+        return pl;  // the host builds a 16-bit-stack BVH2 for f64 scenes
+    if (b2 && (p.n_perlin || p.n_media)) return pl;
+    const int cls = b2 ? kF64Book2 : !p.specular ? kF64Diffuse : !p.image_tex ? kF64Untextured : kF64Full;
     const int B = blk64(cls);
     KParams q = p;
     q.rec32_in_lds = 0u;
@@ -1523,7 +1650,14 @@ LaunchPlan plan_launch_f64(const KParams &p) {
     int mode = kF64Global;
     if (p.scene_in_lds) {
         mode = -1;
-        if (const int lay = g_f64_layout.load(); lay >= 0) {  // a forced layout over the budget fails the render
+        if (b2) {
+            // the book-2 class stages the nodes and the f32 records (spheres as (center1, r), quads as
+            // (q, tag)), and the 1/r table when it fits; motion rows and quad records stay in global
+            // memory (no widened-record layout: a sphere's center moves with the ray's time)
+            mode = kF64Lds;
+            q.inv_r_in_lds = 1u;
+            if (lds64_bytes(q, kF64Lds, B) > lds_budget64(B)) q.inv_r_in_lds = 0u;
+        } else if (const int lay = g_f64_layout.load(); lay >= 0) {  // a forced layout over the budget fails the render
             const bool wide = (lay & 1) != 0;
             q.inv_r_in_lds = (lay & 2) ? 1u : 0u;
             q.rec32_in_lds = wide && (lay & 4) ? 1u : 0u;
@@ -1556,7 +1690,7 @@ LaunchPlan plan_launch_f64(const KParams &p) {
     pl.arm = mode;
     pl.stack_bytes = 2u;
     pl.threads = (uint32_t)B;
-    pl.waves = pl.waves_nf = cls == kF64Full ? 1u : (uint32_t)RRT_F64_WAVES;
+    pl.waves = pl.waves_nf = (uint32_t)waves64(cls);
     pl.scene_in_lds = mode != kF64Global ? 1u : 0u;
     pl.inv_r_in_lds = q.inv_r_in_lds;
     pl.rec32_in_lds = q.rec32_in_lds;
@@ -1601,7 +1735,8 @@ hipError_t launch64(const KParams &p, const LaunchPlan &pl, bool count, hipStrea
 template <int kClass>
 hipError_t launch64_placed(const KParams &p, const LaunchPlan &pl, bool count, hipStream_t stream) {
     if (pl.arm == kF64Global) return launch64<kF64Global, kClass>(p, pl, count, stream);
-    return pl.arm == kF64LdsWide ? launch64<kF64LdsWide, kClass>(p, pl, count, stream)
+    if constexpr (kClass == kF64Book2) return launch64<kF64Lds, kClass>(p, pl, count, stream);  // no widened layout
+    else return pl.arm == kF64LdsWide ? launch64<kF64LdsWide, kClass>(p, pl, count, stream)
                                  : launch64<kF64Lds, kClass>(p, pl, count, stream);
 }
 
@@ -1612,7 +1747,8 @@ hipError_t launch_render_pass_f64(const KParams &p, bool count, hipStream_t stre
     const LaunchPlan pl = plan_launch_f64(p);
     if (!pl.ok) return hipErrorInvalidValue;
     hipError_t e;
-    if (pl.kclass == kF64Diffuse) e = launch64_placed<kF64Diffuse>(p, pl, count, stream);
+    if (pl.kclass == kF64Book2) e = launch64_placed<kF64Book2>(p, pl, count, stream);
+    else if (pl.kclass == kF64Diffuse) e = launch64_placed<kF64Diffuse>(p, pl, count, stream);
     else if (pl.kclass == kF64Untextured) e = launch64_placed<kF64Untextured>(p, pl, count, stream);
     else e = launch64_placed<kF64Full>(p, pl, count, stream);
     if (e != hipSuccess || p.n_chunks <= 1 || p.seq) return e;
@@ -1647,16 +1783,21 @@ void device_op64_columns(uint32_t op, uint32_t &cols_in, uint32_t &cols_out) {
     case RRT_OP_VEC64: cols_in = 9, cols_out = 11; break;
     case RRT_OP_TEXEL64: cols_in = 5, cols_out = 6; break;
     case RRT_OP_SPHERE64: cols_in = 11, cols_out = 6; break;
+    case RRT_OP_QUAD64: cols_in = 9, cols_out = 2; break;
+    case RRT_OP_CHECKER64: cols_in = 4, cols_out = 1; break;
     default: cols_in = cols_out = 0; break;
     }
 }
 
-hipError_t launch_device_ops64(uint32_t op, uint32_t n, const double *d_in, uint64_t *d_out, hipStream_t stream) {
+hipError_t launch_device_ops64(uint32_t op, uint32_t n, const double *d_in, uint64_t *d_out, const void *d_aux,
+                               uint32_t n_aux, hipStream_t stream) {
     uint32_t cin = 0, cout = 0;
     device_op64_columns(op, cin, cout);
     if (cin == 0 || n == 0) return hipErrorInvalidValue;
+    if (op == RRT_OP_QUAD64 && (!d_aux || n_aux == 0)) return hipErrorInvalidValue;
     // one thread per row (a whole number of 256-thread blocks): row i is lane i % 64 of wave i / 64
-    hipLaunchKernelGGL(rrt_device_ops64, dim3((n + 255u) / 256u), dim3(256), 0, stream, op, n, cin, cout, d_in, d_out);
+    hipLaunchKernelGGL(rrt_device_ops64, dim3((n + 255u) / 256u), dim3(256), 0, stream, op, n, cin, cout, d_in, d_out,
+                       static_cast<const GQuad64 *>(d_aux));
     return hipGetLastError();
 }
 

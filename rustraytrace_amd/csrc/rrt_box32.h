@@ -23,6 +23,21 @@
 // is below t* already. Likewise fr >= t* - E(fr) (fl32(closest) >= closest (1 - u) > t* - E). So
 // nr - E(nr) < t* < fr + E(fr): the box is accepted. Other axes need no widening of their own:
 // only the attaining one enters the comparison.
+// The book-2 class (rrt_books64.hip kF64Book2) adds two cases, which the same argument covers:
+//   a quad hit at t* in the closed [0.001, closest]: the comparisons above are strict with room to
+//   spare at both ends (the tmin constant is the largest f32 below 0.001 <= t*, and fl32(closest) >=
+//   closest (1 - u) >= t* (1 - u) > t* - E), so t* = 0.001 and t* = closest are accepted like interior
+//   points. The hit point o + t* d has alpha, beta in [0, 1] up to f64 roundings, i.e. it lies within
+//   ~2^-50 of the scene's extent of the parallelogram, whose four corners span the leaf box (quad.rs:
+//   40-45, padded to 1e-4 where flat); every stored plane is moved outward by BoxSlack's
+//   4u (2 |P| + 3 M_a) >= 12u M_a (M_a: the scene's largest |coordinate| on the axis; u = 2^-24) and
+//   then rounded outward to f32, 2^26 times that f64 error.
+//   a sphere at center1 + time * motion, time in [0, 1): each coordinate lies between center1 and
+//   center1 + motion (up to an f64 rounding). The builders' leaf box is the union of the boxes at
+//   center1 and at fl32(center1 + motion) (the_next_week/sphere.rs:31-33; rrt_host.cpp prim_boxes), and
+//   fl32(center1 + motion) is within u |center1 + motion| <= u M_a of center1 + motion: inside the
+//   12u M_a of slack with 11u M_a left for the clamped-axis case below (which needs u |o_a|).
+// A wrong prune would show as a ray-count or bit mismatch against BOOKS (tests/test_gpu_books64_book2.py).
 // A clamped axis (|q| > 2^64: d_a = 0 or |d_a| < 2^-64) gives plane distances (P - o32) * 2^64 with
 // the sign of P - o (the host grows every stored plane by more than u |o_a| for origins within the
 // scene's extent, rrt_host.cpp BoxSlack): such a ray stays inside that slab, or outside it, for

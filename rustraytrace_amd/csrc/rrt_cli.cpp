@@ -100,13 +100,16 @@ static void usage() {
                  "Usage: rrt [--backend hip|cuda|gpu] <book> [scene] [--image_width N] [--samples_per_pixel N]\n"
                  "           [--max_depth N] [--aspect_ratio X] [--vfov X] [--lookfrom x,y,z] [--lookat x,y,z]\n"
                  "           [--vup x,y,z] [--defocus_angle X] [--focus_dist X] [--background r,g,b]\n"
-                 "           [--gpus N] [--seed S] [--grid_half G] [--p6] [--host-quantise] [--books-f64] [--device-bvh]\n"
+                 "           [--gpus N] [--seed S] [--grid_half G] [--p6] [--host-quantise] [--books-f64] [--books-f64-book2]\n"
+                 "           [--device-bvh]\n"
                  "           [-o out.ppm]\n"
                  "  --p6             binary P6 instead of render_io.rs's P3 text\n"
                  "  --host-quantise  copy the float accum and quantise on the host (same bytes)\n"
                  "  --books-f64      the f64 books kernel (RRT_FLAG_F64, in_one_weekend) and the books path's own\n"
                  "                   quantiser (color.rs) on the device: the P3 camera.rs prints; with\n"
                  "                   --host-quantise the f64 sums are copied and quantised on the host (same bytes)\n"
+                 "  --books-f64-book2  --books-f64 that also takes the_next_week 1, 2, 5 and 7 (RRT_FLAG_F64_BOOK2:\n"
+                 "                   moving spheres, quads, checker textures); other scenes are refused\n"
                  "  --device-bvh     build the scene's BVH on the device (RRT_FLAG_DEVICE_BVH) instead of the host\n"
                  "books: in_one_weekend, the_next_week [1-9, other = final_scene(400, 250, 4)], "
                  "the_rest_of_your_life\n");
@@ -145,7 +148,7 @@ int main(int argc, char **argv) {
     uint64_t seed = 0x5EED1234ull;
     int grid_half = 11;
     std::string out = "-";
-    bool p6 = false, host_quantise = false, seed_set = false, books_f64 = false, device_bvh = false;
+    bool p6 = false, host_quantise = false, seed_set = false, books_f64 = false, books_f64_book2 = false, device_bvh = false;
 
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
@@ -178,6 +181,7 @@ int main(int argc, char **argv) {
         else if (a == "--p6") p6 = true;
         else if (a == "--host-quantise") host_quantise = true;
         else if (a == "--books-f64") books_f64 = true;
+        else if (a == "--books-f64-book2") books_f64 = books_f64_book2 = true;
         else if (a == "--device-bvh") device_bvh = true;
         else if (a == "-h" || a == "--help") { usage(); return 0; }
         else positional.push_back(a);
@@ -298,22 +302,29 @@ int main(int argc, char **argv) {
     if (books_f64) {  // the f64 books kernel and color.rs's quantiser: the books path's own PPM
         const RrtTexture *tex = n_tex ? &earth : nullptr;
         rc = RRT_OK;
-        if (!book1) {  // book-2/3 data: the library's refusal (the f64 one-shot entries take no RrtSceneExt)
+        // --books-f64-book2: the _ex entries, which imply RRT_FLAG_F64_BOOK2 and take the RrtSceneExt
+        const uint32_t b2 = books_f64_book2 ? RRT_FLAG_F64_BOOK2 : 0u;
+        if (!book1) {  // book-2/3 data: scene creation's refusal, which comes before any device call (without
+                       // --books-f64-book2 every such scene is refused: those one-shot entries take no RrtSceneExt)
             RrtScene *refused = nullptr;
             rc = rrt_scene_create_ex(&cam, spheres.data(), n, materials.data(), n_mat, tex, n_tex, &ext,
-                                     flags | RRT_FLAG_F64, 0, &refused);
+                                     flags | RRT_FLAG_F64 | b2, 0, &refused);
             if (!rc) rrt_scene_destroy(refused);
         }
         rgb8.resize((size_t)w * h * 3);
         if (rc) {  // refused: reported below like every failed render
         } else if (host_quantise) {  // 32 B/pixel of f64 sums to the host, write_color there
             std::vector<double> accum64((size_t)w * h * 4);
-            rc = rrt_hip_render_f64(&cam, spheres.data(), n, materials.data(), n_mat, tex, n_tex, spp, gpus, flags,
-                                    accum64.data());
+            rc = b2 ? rrt_hip_render_f64_ex(&cam, spheres.data(), n, materials.data(), n_mat, tex, n_tex, &ext, spp, gpus,
+                                            flags, accum64.data())
+                    : rrt_hip_render_f64(&cam, spheres.data(), n, materials.data(), n_mat, tex, n_tex, spp, gpus, flags,
+                                         accum64.data());
             if (!rc) rc = rrt_quantize_accum_books_f64(w, h, accum64.data(), spp, rgb8.data());
         } else {  // quantised on the device, 3 B/pixel to the host
-            rc = rrt_hip_render_f64_rgb8(&cam, spheres.data(), n, materials.data(), n_mat, tex, n_tex, spp, gpus, flags,
-                                         rgb8.data());
+            rc = b2 ? rrt_hip_render_f64_rgb8_ex(&cam, spheres.data(), n, materials.data(), n_mat, tex, n_tex, &ext, spp,
+                                                 gpus, flags, rgb8.data())
+                    : rrt_hip_render_f64_rgb8(&cam, spheres.data(), n, materials.data(), n_mat, tex, n_tex, spp, gpus, flags,
+                                              rgb8.data());
         }
     } else if (host_quantise && !p6) {  // float accum -> render_io on the host (rrt_hip_render_ex)
         accum.resize((size_t)w * h * 4);

@@ -1068,6 +1068,7 @@ struct RrtScene {
     float4 *d_prim_motion = nullptr;
     rrt::GPerlin *d_perlin = nullptr;
     rrt::GQuad *d_quads = nullptr;
+    rrt::GQuad64 *d_quads64 = nullptr;  // RRT_FLAG_F64_BOOK2 scenes: the quads unrounded, instead of d_quads
     rrt::GMedium *d_media = nullptr;
     rrt::GLight *d_lights = nullptr;
     uint8_t *d_tex_pool = nullptr;
@@ -1105,6 +1106,7 @@ void free_scene(RrtScene *s) {
     (void)hipFree(s->d_prim_motion);
     (void)hipFree(s->d_perlin);
     (void)hipFree(s->d_quads);
+    (void)hipFree(s->d_quads64);
     (void)hipFree(s->d_media);
     (void)hipFree(s->d_lights);
     (void)hipFree(s->d_tex_pool);
@@ -1368,13 +1370,25 @@ int32_t rrt_device_count(int32_t *count) {
 // A quad with its derived plane (quad.rs:21-37 in f64: n = cross(u, v), normal = n * (1/|n|),
 // D = dot(normal, q), w = n * (1/dot(n, n)); Vec3 / f64 is `(1/rhs) * v`, vec3.rs:142-148), rounded
 // to the device record. Scene creation and rrt_testing_device_ops form their records here.
-static rrt::GQuad form_gquad(const RrtQuad &qd) {
+// form_gquad64 keeps the f64 values unrounded (the f64 kernel's book-2 class, GQuad64).
+static rrt::GQuad64 form_gquad64(const RrtQuad &qd) {
     const D3 q = d3(qd.q[0], qd.q[1], qd.q[2]), u = d3(qd.u[0], qd.u[1], qd.u[2]), v = d3(qd.v[0], qd.v[1], qd.v[2]);
     const D3 n = cross(u, v);
     const double nn = n.x * n.x + n.y * n.y + n.z * n.z;
     const D3 normal = n * (1.0 / std::sqrt(nn));
     const double dd = normal.x * q.x + normal.y * q.y + normal.z * q.z;
     const D3 w = n * (1.0 / nn);
+    rrt::GQuad64 g;
+    const D3 *src[5] = {&q, &u, &v, &normal, &w};
+    double *dst[5] = {g.q, g.u, g.v, g.n, g.w};
+    for (int k = 0; k < 5; ++k) dst[k][0] = src[k]->x, dst[k][1] = src[k]->y, dst[k][2] = src[k]->z;
+    g.D = dd;
+    return g;
+}
+static rrt::GQuad form_gquad(const RrtQuad &qd) {
+    const rrt::GQuad64 g64 = form_gquad64(qd);
+    const D3 normal = d3(g64.n[0], g64.n[1], g64.n[2]), w = d3(g64.w[0], g64.w[1], g64.w[2]);
+    const double dd = g64.D;
     rrt::GQuad g;
     g.q = make_float4(qd.q[0], qd.q[1], qd.q[2], (float)dd);
     g.u = make_float4(qd.u[0], qd.u[1], qd.u[2], 0.0f);
@@ -1434,6 +1448,25 @@ static int32_t scene_create(const RrtCamera *cam, const RrtSphere *spheres, uint
     // Book-2 scenes (moving spheres or checker / noise materials) take the kernel variant that
     // supports them; it reads a motion row per sphere (zero for static spheres).
     const bool book3 = (flags & RRT_FLAG_BOOK3) != 0;
+    // RRT_FLAG_F64_BOOK2 implies RRT_FLAG_F64; what its kernel class does not cover is refused here,
+    // before any device call
+    static_assert(RRT_FLAG_F64_BOOK2 == rrt::kFlagF64Book2, "RRT_FLAG_F64_BOOK2");
+    const bool f64_book2_flag = (flags & RRT_FLAG_F64_BOOK2) != 0;
+    if (f64_book2_flag) {
+        flags |= RRT_FLAG_F64;
+        const std::string no = "RRT_FLAG_F64_BOOK2 renders moving spheres, quads and material kinds 0-5; not ";
+        if (book3) return fail(RRT_E_INVALID, no + "RRT_FLAG_BOOK3");
+        if (ex.n_lights) return fail(RRT_E_INVALID, no + "RrtSceneExt.lights");
+        if (n_perlin) return fail(RRT_E_INVALID, no + "Perlin tables (RrtSceneExt.perlin)");
+        if (n_media) return fail(RRT_E_INVALID, no + "constant media (RrtSceneExt.media)");
+        if (ex.n_bquads) return fail(RRT_E_INVALID, no + "boundary quads (RrtSceneExt.boundary_quads)");
+        for (uint32_t i = 0; i < n_materials && materials; ++i) {
+            if (materials[i].kind == RRT_MAT_NOISE_LAMBERTIAN)
+                return fail(RRT_E_INVALID, no + "material " + std::to_string(i) + " of kind 6 (noise texture)");
+            if (materials[i].kind == RRT_MAT_ISOTROPIC)
+                return fail(RRT_E_INVALID, no + "material " + std::to_string(i) + " of kind 7 (isotropic)");
+        }
+    }
     uint32_t sqrt_spp = 0;
     if (book3) {
         if (!(flags & RRT_FLAG_RAY_TIME)) return fail(RRT_E_INVALID, "RRT_FLAG_BOOK3 needs RRT_FLAG_RAY_TIME");
@@ -1460,7 +1493,12 @@ static int32_t scene_create(const RrtCamera *cam, const RrtSphere *spheres, uint
         bvh_defaults(w, l);
         if (w != 2) return fail(RRT_E_INVALID, "RRT_FLAG_DEVICE_BVH builds binary trees only (RRT_BVH_WIDTH=4 is set)");
     }
-    if (f64 && (book2 || n_perlin || ex.n_lights))
+    // the f64 kernel's book-2 class runs the scenes that have book-2 data; a book-1 scene created with
+    // RRT_FLAG_F64_BOOK2 is an RRT_FLAG_F64 scene (same tree, same kernel class, same bits)
+    const bool f64_book2 = f64_book2_flag && book2;
+    flags &= ~RRT_FLAG_F64_BOOK2;
+    if (f64_book2) flags |= RRT_FLAG_F64_BOOK2;
+    if (f64 && !f64_book2_flag && (book2 || n_perlin || ex.n_lights))
         return fail(RRT_E_INVALID, "RRT_FLAG_F64 renders book-1 scenes (material kinds 0-4, no RrtSceneExt data, "
                                    "not RRT_FLAG_BOOK3)");
     if (!has_motion) motion = nullptr;
@@ -1539,6 +1577,14 @@ static int32_t scene_create(const RrtCamera *cam, const RrtSphere *spheres, uint
             mats[i].a.z = canonical_albedo(mats[i].a.z);
         }
         mats[i].b = make_int4((int)m.kind, ref_bits, (int)m._pad[0], (int)m._pad[1]);
+        if (f64 && m.kind == RRT_MAT_CHECKER_LAMBERTIAN) {  // the odd colour is an attenuation too
+            for (int *w : {&mats[i].b.y, &mats[i].b.z, &mats[i].b.w}) {
+                float c;
+                std::memcpy(&c, w, sizeof(float));
+                c = canonical_albedo(c);
+                std::memcpy(w, &c, sizeof(float));
+            }
+        }
         if (m.kind == RRT_MAT_LAMBERTIAN || m.kind == RRT_MAT_METAL) {
             const float inv_pr = rr_inv_pr(m.albedo_fuzz[0], m.albedo_fuzz[1], m.albedo_fuzz[2]);
             std::memcpy(&mats[i].b.y, &inv_pr, sizeof(float));  // ref_idx: a dielectric's only
@@ -1673,7 +1719,11 @@ static int32_t scene_create(const RrtCamera *cam, const RrtSphere *spheres, uint
             if ((rc = upload(&s->d_prim_diel64, diel.data(), diel.size(), "dielectric constants"))) break;
         }
         if (n_perlin && (rc = upload(&s->d_perlin, perlin.data(), perlin.size(), "Perlin tables"))) break;
-        if (!gquads.empty() && (rc = upload(&s->d_quads, gquads.data(), gquads.size(), "quads"))) break;
+        if (f64_book2) {  // the f64 kernel reads the unrounded records (GQuad64) and no f32 one
+            std::vector<rrt::GQuad64> gquads64(n_quads);
+            for (uint32_t j = 0; j < n_quads; ++j) gquads64[j] = form_gquad64(quads[j]);
+            if (n_quads && (rc = upload(&s->d_quads64, gquads64.data(), gquads64.size(), "f64 quads"))) break;
+        } else if (!gquads.empty() && (rc = upload(&s->d_quads, gquads.data(), gquads.size(), "quads"))) break;
         if (n_media && (rc = upload(&s->d_media, gmedia.data(), gmedia.size(), "media"))) break;
         if (!glights.empty() && (rc = upload(&s->d_lights, glights.data(), glights.size(), "lights"))) break;
         if ((rc = upload(&s->d_tex_pool, tex_pool.data(), tex_pool.size(), "textures"))) break;
@@ -1713,7 +1763,7 @@ static int32_t scene_create(const RrtCamera *cam, const RrtSphere *spheres, uint
     p.prim_motion = s->d_prim_motion;
     p.perlin = s->d_perlin;
     p.n_perlin = n_perlin;
-    p.quads = s->d_quads;
+    p.quads = f64_book2 ? reinterpret_cast<const rrt::GQuad *>(s->d_quads64) : s->d_quads;  // KParams.quads
     p.n_quads = n_quads;
     p.media = s->d_media;
     p.n_media = n_media;
@@ -1809,7 +1859,8 @@ static int32_t scene_create(const RrtCamera *cam, const RrtSphere *spheres, uint
     s->order = order;
     bi.n_unbounded = fb.n_unbounded;
     bi.prim_bytes = (uint64_t)n_prims * (rrt::kPrimBytes + (book2 ? rrt::kMotionBytes : 0)) +
-                    (uint64_t)gquads.size() * sizeof(rrt::GQuad) + (uint64_t)n_media * sizeof(rrt::GMedium);
+                    (uint64_t)gquads.size() * (f64_book2 ? sizeof(rrt::GQuad64) : sizeof(rrt::GQuad)) +
+                    (uint64_t)n_media * sizeof(rrt::GMedium);
     *out = s;
     return RRT_OK;
 }
@@ -2114,7 +2165,11 @@ extern "C" int32_t rrt_testing_launch_plan(const RrtLaunchPlanQuery *q, RrtLaunc
     p.global_waves = q->global_waves ? q->global_waves : 7u;
     // the scenes rrt_scene_create rejects before it plans
     const bool book2 = q->book != 0u;
-    if (q->stack_depth > (uint32_t)rrt::kMaxStackDepth || (q->f64 && (book2 || q->n_perlin || q->n_nodes > 65535u)) ||
+    // RRT_FLAG_F64_BOOK2 on a scene with book-2 data: the f64 kernel's book-2 class (no media, no book 3)
+    const bool f64_book2 = q->f64 && q->f64_book2 && q->book == 2u;
+    if (f64_book2) p.flags |= RRT_FLAG_F64_BOOK2;
+    if (q->stack_depth > (uint32_t)rrt::kMaxStackDepth ||
+        (q->f64 && ((book2 && !f64_book2) || q->n_perlin || q->n_nodes > 65535u)) || (f64_book2 && q->n_media) ||
         (book2 && p.bvh_width != 2u))
         return RRT_OK;
     p.perlin_in_lds = rrt::perlin_fits_lds(p) ? 1u : 0u;
@@ -2246,7 +2301,6 @@ extern "C" int32_t rrt_testing_device_ops(uint32_t op, uint32_t n, const void *i
 // columns (ATT64's word and bytes, TEXEL64's image size) are checked here, so the kernel converts
 // only values in range.
 extern "C" int32_t rrt_testing_device_ops64(uint32_t op, uint32_t n, const void *in, void *out, const void *aux) {
-    (void)aux;  // no op takes auxiliary records yet
     uint32_t cin = 0, cout = 0;
     rrt::device_op64_columns(op, cin, cout);
     if (cin == 0) return fail(RRT_E_INVALID, "rrt_testing_device_ops64: unknown op " + std::to_string(op));
@@ -2262,18 +2316,41 @@ extern "C" int32_t rrt_testing_device_ops64(uint32_t op, uint32_t n, const void 
         if (op == RRT_OP_TEXEL64 && !(whole(x[3], 1.0, 1073741824.0) && whole(x[4], 1.0, 1073741824.0)))
             return fail(RRT_E_INVALID, "rrt_testing_device_ops64: TEXEL64 image size outside [1, 2^30]");
     }
+    // QUAD64: the records as scene creation forms them (form_gquad64), aux laid out as RRT_OP_QUAD's
+    std::vector<rrt::GQuad64> quads64;
+    if (op == RRT_OP_QUAD64) {
+        if (!aux) return fail(RRT_E_INVALID, "rrt_testing_device_ops64: QUAD64 needs quads");
+        uint32_t n_aux = 0;
+        std::memcpy(&n_aux, aux, sizeof(uint32_t));
+        if (n_aux == 0 || n_aux > 65536u) return fail(RRT_E_INVALID, "rrt_testing_device_ops64: quad count");
+        quads64.resize(n_aux);
+        for (uint32_t j = 0; j < n_aux; ++j) {
+            RrtQuad qd;
+            std::memcpy(&qd, static_cast<const uint8_t *>(aux) + 16 + (size_t)j * sizeof(RrtQuad), sizeof(qd));
+            quads64[j] = form_gquad64(qd);
+        }
+        for (uint32_t i = 0; i < n; ++i)
+            if (!whole(rows[(size_t)i * cin + 8], 0.0, (double)(n_aux - 1u)))
+                return fail(RRT_E_INVALID, "rrt_testing_device_ops64: quad index out of range");
+    }
     int count = 0;
     if (hipGetDeviceCount(&count) != hipSuccess || count < 1) return fail(RRT_E_NODEV, "no HIP device");
     const size_t in_bytes = (size_t)n * cin * 8u, out_bytes = (size_t)n * cout * 8u;
-    void *d_in = nullptr, *d_out = nullptr;
+    void *d_in = nullptr, *d_out = nullptr, *d_aux = nullptr;
     hipError_t e = hipMalloc(&d_in, in_bytes);
     if (e == hipSuccess) e = hipMalloc(&d_out, out_bytes);
+    if (e == hipSuccess && !quads64.empty()) e = hipMalloc(&d_aux, quads64.size() * sizeof(rrt::GQuad64));
     if (e == hipSuccess) e = hipMemcpy(d_in, in, in_bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess && d_aux)
+        e = hipMemcpy(d_aux, quads64.data(), quads64.size() * sizeof(rrt::GQuad64), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemset(d_out, 0, out_bytes);
-    if (e == hipSuccess) e = rrt::launch_device_ops64(op, n, static_cast<const double *>(d_in), static_cast<uint64_t *>(d_out), nullptr);
+    if (e == hipSuccess)
+        e = rrt::launch_device_ops64(op, n, static_cast<const double *>(d_in), static_cast<uint64_t *>(d_out), d_aux,
+                                     (uint32_t)quads64.size(), nullptr);
     if (e == hipSuccess) e = hipMemcpy(out, d_out, out_bytes, hipMemcpyDeviceToHost);
     (void)hipFree(d_in);
     (void)hipFree(d_out);
+    (void)hipFree(d_aux);
     if (e != hipSuccess) return fail(RRT_E_HIP, std::string("rrt_testing_device_ops64: ") + hipGetErrorString(e));
     return RRT_OK;
 }
@@ -2519,6 +2596,24 @@ int32_t rrt_hip_render_f64_rgb8(const RrtCamera *cam, const RrtSphere *spheres, 
     if (!rgb8_out) return fail(RRT_E_INVALID, "null camera or rgb8_out");
     return render_frame(cam, spheres, n_spheres, materials, n_materials, textures, n_textures, nullptr, total_spp,
                         n_gpus, flags | RRT_FLAG_F64, nullptr, rgb8_out, nullptr, true);
+}
+
+int32_t rrt_hip_render_f64_ex(const RrtCamera *cam, const RrtSphere *spheres, uint32_t n_spheres,
+                              const RrtMaterial *materials, uint32_t n_materials, const RrtTexture *textures,
+                              uint32_t n_textures, const RrtSceneExt *ext, uint32_t total_spp, uint32_t n_gpus,
+                              uint32_t flags, double *accum_out) {
+    if (!accum_out) return fail(RRT_E_INVALID, "null camera or accum_out");
+    return render_frame(cam, spheres, n_spheres, materials, n_materials, textures, n_textures, ext, total_spp, n_gpus,
+                        flags | RRT_FLAG_F64 | RRT_FLAG_F64_BOOK2, nullptr, nullptr, accum_out);
+}
+
+int32_t rrt_hip_render_f64_rgb8_ex(const RrtCamera *cam, const RrtSphere *spheres, uint32_t n_spheres,
+                                   const RrtMaterial *materials, uint32_t n_materials, const RrtTexture *textures,
+                                   uint32_t n_textures, const RrtSceneExt *ext, uint32_t total_spp, uint32_t n_gpus,
+                                   uint32_t flags, uint8_t *rgb8_out) {
+    if (!rgb8_out) return fail(RRT_E_INVALID, "null camera or rgb8_out");
+    return render_frame(cam, spheres, n_spheres, materials, n_materials, textures, n_textures, ext, total_spp, n_gpus,
+                        flags | RRT_FLAG_F64 | RRT_FLAG_F64_BOOK2, nullptr, rgb8_out, nullptr, true);
 }
 
 int32_t rrt_quantize_accum_books_async(uint32_t n_pixels, const float *d_accum, uint32_t samples_per_pixel,

@@ -80,6 +80,14 @@ struct alignas(16) GQuad {
     float4 n;
     float4 w;
 };
+// The same quad unrounded, for the f64 books kernel's book-2 class (rrt_books64.hip kF64Book2): the f32
+// corner and edges widened, and the derived plane as quad.rs:21-37 forms it in f64 (the values GQuad
+// rounds). 128 B.
+struct alignas(16) GQuad64 {
+    double q[3], u[3], v[3], n[3], w[3];
+    double D;
+};
+static_assert(sizeof(GQuad64) == 128, "GQuad64 must be 128 B");
 
 // ConstantMedium (the_next_week/constant_medium.rs): boundary sphere (xyz, r) or quads
 // [first, first + count) of KParams.quads (after the scene's own quads); neg_inv_density =
@@ -146,7 +154,9 @@ struct KParams {
     const GPerlin *perlin;       // Perlin tables (noise textures)
     const GQuad *quads;          // quads, then media boundary quads; a quad's leaf-order primitive record is
                                  // (q.xyz, -(1 + index)) with (normal.xyz, D) in its motion slot; a
-                                 // medium's (0, 0, 0, -(1 + n_quads + index))
+                                 // medium's (0, 0, 0, -(1 + n_quads + index)). A scene of the f64 kernel's
+                                 // book-2 class (flags & kFlagF64Book2) points this at its GQuad64 records
+                                 // instead (same leaf-order convention; no f32 kernel runs on such a scene)
     const GMedium *media;
     const GLight *lights;        // book 3: the MIS light list
     const uint8_t *tex_pool;
@@ -234,14 +244,16 @@ struct KParams {
     float cam_u[3];
     float cam_v[3];
     // 1 / r per leaf-order sphere in f64 (sphere.rs:48's (p - center) / radius is (1/r) * v,
-    // vec3.rs:142-148: the same IEEE quotient, formed once on the host)
+    // vec3.rs:142-148: the same IEEE quotient, formed once on the host). One entry per leaf-order
+    // primitive: a quad's (book-2 class) holds 1 / its tag and is never read
     const double *prim_inv_r64;
     uint32_t inv_r_in_lds;  // f64 kernel, scene in LDS: the 1/r table staged too (fits the block's 64 KB)
     // the camera block widened to f64 on the host, as camera.rs:136-180 forms it from the f32 ABI
     // values: pixel00, delta_u, delta_v, center, defocus_disk_u = u * radius, defocus_disk_v
     double cam64[6][3];
     // per leaf-order primitive, a dielectric's (1 / eta, r0(1 / eta), r0(eta), 0) in f64, formed on
-    // the host in the reference's operations (material.rs:75-102); zeros for other materials
+    // the host in the reference's operations (material.rs:75-102); zeros for other materials. Spheres
+    // and quads alike (a quad can be dielectric)
     const double4 *prim_diel64;
     // the f32 sphere pre-test (rrt_sphere32.h) is enabled: every sphere center and radius within
     // 2^20 (its proven domain); rec32_in_lds: the widened-record layout also stages the f32 records
@@ -264,6 +276,9 @@ struct KParams {
 
 // RRT_FLAG_F64 (include/rrt_hip.h): the f64 books-arithmetic kernel (rrt_books64.hip)
 constexpr uint32_t kFlagF64 = 0x8u;
+// RRT_FLAG_F64_BOOK2: kept in KParams.flags only for a scene that has book-2 data (the f64 kernel's
+// class kF64Book2); a book-1 scene created with it renders as RRT_FLAG_F64 alone
+constexpr uint32_t kFlagF64Book2 = 0x20u;
 
 // Traversal stack entries held in LDS per lane: up to 64 (BVH depth <= 63).
 constexpr int kMaxStackDepth = 64;
@@ -332,7 +347,7 @@ struct LaunchPlan {
     uint32_t ok;
     uint32_t f64;
     int32_t kclass;         // f32: -2 diffuse, -1 untextured, 0 full book 1, 1-3 book 2 (spheres, quads, media),
-                            // 4 book 3; f64: 0 full, 1 untextured, 2 diffuse
+                            // 4 book 3; f64: 0 full, 1 untextured, 2 diffuse, 3 book 2 (kFlagF64Book2)
     int32_t arm;            // f32: the launch shape's place in rrt_kernel.hip's LaunchArm; f64: the scene mode
                             // (0 global, 1 staged with f32 sphere records, 2 staged with widened records)
     uint32_t stack_bytes;   // per stack entry: 2, or 4 for more than 65535 nodes
@@ -389,7 +404,9 @@ hipError_t launch_sqrt64_check(unsigned long long *d_out, hipStream_t stream);
 // elementwise. device_op64_columns: the f64 columns per row of `in` and the 64-bit words per row of
 // `out` for an RrtDeviceOp64 (0, 0: no such op).
 void device_op64_columns(uint32_t op, uint32_t &cols_in, uint32_t &cols_out);
-hipError_t launch_device_ops64(uint32_t op, uint32_t n, const double *d_in, uint64_t *d_out, hipStream_t stream);
+// d_aux: n_aux GQuad64 records (QUAD64), else null.
+hipError_t launch_device_ops64(uint32_t op, uint32_t n, const double *d_in, uint64_t *d_out, const void *d_aux,
+                               uint32_t n_aux, hipStream_t stream);
 // Implemented in rrt_books64.hip: one sample pass of the f64 books kernel (+ its chunk combine)
 // into p.accum64, and the f64 sums rounded to the f32 RGBA accum of the ABI.
 hipError_t launch_render_pass_f64(const KParams &p, bool count, hipStream_t stream);

@@ -89,11 +89,31 @@ def render(scene: SceneData, spp: Optional[int] = None, n_gpus: int = 1, quiet: 
     return accum
 
 
+def _f64_ex_args(scene: SceneData, spp, n_gpus, quiet, device_bvh, out):
+    """The argument list of the f64 _ex one-shots (RrtSceneExt passed, both f64 flags implied) and what
+    must stay alive during the call."""
+    tex, ntex, keep = _textures(scene)
+    ext, keep_ext = scene_ext(scene)
+    flags = scene.flags | (_lib.FLAG_QUIET if quiet else 0) | (_lib.FLAG_DEVICE_BVH if device_bvh else 0)
+    args = (_lib.ptr(scene.camera), _lib.ptr(scene.spheres), len(scene.spheres), _lib.ptr(scene.materials),
+            len(scene.materials), ctypes.cast(tex, ctypes.c_void_p) if tex is not None else None, ntex,
+            ctypes.byref(ext) if ext is not None else None, int(spp or 0), int(n_gpus), flags, _lib.ptr(out))
+    return args, (keep, keep_ext, ext)
+
+
 def render_f64(scene: SceneData, spp: Optional[int] = None, n_gpus: int = 1, quiet: bool = True,
-               device_bvh: bool = False) -> np.ndarray:
+               device_bvh: bool = False, book2: bool = False) -> np.ndarray:
     """rrt_hip_render_f64: the books path's own f64 arithmetic (RRT_FLAG_F64, book-1 scenes);
-    returns the RGBA float64 accum (H, W, 4) of f64 sums, w = sample count."""
+    returns the RGBA float64 accum (H, W, 4) of f64 sums, w = sample count. book2=True:
+    rrt_hip_render_f64_ex with the scene's RrtSceneExt (RRT_FLAG_F64_BOOK2: moving spheres, quads,
+    checker textures)."""
     lib = _lib.load()
+    if book2:
+        accum = np.zeros((scene.height, scene.width, 4), dtype=np.float64)
+        args, keep = _f64_ex_args(scene, spp, n_gpus, quiet, device_bvh, accum)
+        _lib.check(lib.rrt_hip_render_f64_ex(*args))
+        del keep
+        return accum
     if getattr(scene, "motion", None) is not None or getattr(scene, "quads", None) is not None:
         raise ValueError("render_f64: book-1 scenes only (RRT_FLAG_F64)")
     accum = np.zeros((scene.height, scene.width, 4), dtype=np.float64)
@@ -134,11 +154,18 @@ def quantize_accum_async(n_pixels: int, d_accum_ptr: int, samples_per_pixel: int
 
 
 def render_f64_rgb8(scene: SceneData, spp: Optional[int] = None, n_gpus: int = 1, quiet: bool = True,
-                    device_bvh: bool = False) -> np.ndarray:
+                    device_bvh: bool = False, book2: bool = False) -> np.ndarray:
     """rrt_hip_render_f64_rgb8: the f64 books kernel (RRT_FLAG_F64, book-1 scenes), then the books
     path's quantiser (color.rs) on the device; returns (H, W, 3) uint8, identical to
-    quantize_accum_books_f64(render_f64(scene)) at the same spp."""
+    quantize_accum_books_f64(render_f64(scene)) at the same spp. book2=True: rrt_hip_render_f64_rgb8_ex
+    with the scene's RrtSceneExt (RRT_FLAG_F64_BOOK2)."""
     lib = _lib.load()
+    if book2:
+        out = np.zeros((scene.height, scene.width, 3), dtype=np.uint8)
+        args, keep = _f64_ex_args(scene, spp, n_gpus, quiet, device_bvh, out)
+        _lib.check(lib.rrt_hip_render_f64_rgb8_ex(*args))
+        del keep
+        return out
     if getattr(scene, "motion", None) is not None or getattr(scene, "quads", None) is not None:
         raise ValueError("render_f64_rgb8: book-1 scenes only (RRT_FLAG_F64)")
     out = np.zeros((scene.height, scene.width, 3), dtype=np.uint8)
@@ -332,12 +359,15 @@ def make_tile(band_rows=16, rank=0, n_ranks=1, sample_begin=0, sample_end=0) -> 
 class DeviceScene:
     """RrtScene*: scene + BVH resident on one device; renders tiles asynchronously on a stream."""
 
-    def __init__(self, scene: SceneData, device: int = 0, f64: bool = False, device_bvh: bool = False):
-        """f64=True: the books path's f64 kernel (RRT_FLAG_F64, book-1 scenes). device_bvh=True: the
-        BVH is built on the device (RRT_FLAG_DEVICE_BVH) instead of the host."""
+    def __init__(self, scene: SceneData, device: int = 0, f64: bool = False, device_bvh: bool = False,
+                 f64_book2: bool = False):
+        """f64=True: the books path's f64 kernel (RRT_FLAG_F64, book-1 scenes); with f64_book2=True also
+        moving spheres, quads and checker textures (RRT_FLAG_F64_BOOK2, which implies f64). device_bvh=True:
+        the BVH is built on the device (RRT_FLAG_DEVICE_BVH) instead of the host."""
         lib = _lib.load()
         self.scene = scene
         flags = scene.flags | (_lib.FLAG_F64 if f64 else 0) | (_lib.FLAG_DEVICE_BVH if device_bvh else 0)
+        flags |= _lib.FLAG_F64_BOOK2 if f64_book2 else 0
         self._lib = lib
         self._h = ctypes.c_void_p()
         tex, ntex, keep = _textures(scene)
