@@ -427,6 +427,32 @@ int32_t rrt_build_bvh_binned(const RrtSphere *spheres, uint32_t n_spheres, const
  * rrt_build_bvh_ex cannot reproduce. */
 int32_t rrt_scene_read_bvh(RrtScene *scene, void *nodes_out, size_t nodes_cap, uint32_t *prim_order_out);
 
+/* ---- changing a created scene (additive; RRT_ABI_VERSION is unchanged) ------------------ */
+
+/* Replaces everything scene creation derives from the camera: rays, seed, max_depth, background,
+ * width/height, and for RRT_FLAG_BOOK3 the sqrt_spp rule with its validation. Host state only: it
+ * affects renders enqueued after it returns. Works on every scene; a refused camera leaves the
+ * scene as it was. */
+int32_t rrt_scene_set_camera(RrtScene *scene, const RrtCamera *cam);
+
+/* Replaces the scene's spheres (centers, radii, material_index) and, for a book-2 world, their
+ * motion rows (n_spheres x 4 floats as RrtSceneExt.sphere_motion; NULL = all zero). Rebuilds the BVH
+ * on the device and re-forms every per-primitive table there; the scene then holds, bit for bit,
+ * what rrt_scene_create_ex would make of the new inputs (tree, leaf order, tables, every frame).
+ * n_spheres must equal the scene's. Quads, materials, textures and Perlin tables are kept. Waits
+ * for `stream`, then runs and returns synchronised. From the second update of a scene on, no device
+ * memory is allocated or freed.
+ * Refused with RRT_E_INVALID, before any device call and with the scene untouched: null arguments
+ * or another n_spheres; a material_index out of range; a scene not created with
+ * RRT_FLAG_DEVICE_BVH; a scene with media; an RRT_FLAG_BOOK3 scene; a tree of fewer than 2
+ * primitives; a non-zero motion row on a scene that was not created as a book-2 world (the kernel
+ * class is fixed at creation; a book-2 world accepts any motion, all-zero included).
+ * A failure after device work has begun (a HIP error, or a tree over the depth or node limits of
+ * scene creation) leaves the scene invalid: its renders fail, naming the failed update, until a
+ * later update succeeds. */
+int32_t rrt_scene_update_spheres(RrtScene *scene, const RrtSphere *spheres, uint32_t n_spheres,
+                                 const float *motion, void *stream);
+
 /* ---- host-side callers of the boundary ------------------------------------------------ */
 
 /* == gpu::build_in_one_weekend_scene (gpu/mod.rs:124-301): RTOW final scene from
@@ -660,6 +686,31 @@ void rrt_testing_f64_layout(int32_t layout);
  * count << 28, count > 0). The function the kernel's staging loop applies; no device is needed
  * (tests/test_lds_links.py). */
 uint32_t rrt_testing_lds_node_link(uint32_t link);
+
+/* Test support, not part of the drop-in (RRT_ABI_VERSION is unchanged and the Rust shim does not bind
+ * them). rrt_testing_sphere_boxes: the padded f64 box of each sphere (out: n_spheres x 6 doubles,
+ * min xyz then max xyz; motion as in rrt_scene_update_spheres) by the host compilation of the
+ * function the update runs on the device. rrt_testing_scene_read_table: one of the scene's device
+ * tables (RrtSceneTable; rows in leaf order except the boxes, which are in primitive order and held
+ * only by a scene the device builder built); cap 0 sizes (*bytes_out, 0 for a table the scene does
+ * not hold). rrt_testing_scene_update_stats: the scene's successful updates, and the device
+ * allocations and builder levels of the last one. */
+typedef enum RrtSceneTable {
+    RRT_TABLE_BOXES = 0,        /* 6 doubles per primitive */
+    RRT_TABLE_PRIM_CR = 1,      /* float4 */
+    RRT_TABLE_PRIM_MTL = 2,     /* 32-B material record */
+    RRT_TABLE_PRIM_MOTION = 3,  /* float4, book-2 worlds */
+    RRT_TABLE_PRIM_INV_R64 = 4, /* double, RRT_FLAG_F64 */
+    RRT_TABLE_PRIM_DIEL64 = 5   /* 4 doubles, RRT_FLAG_F64 */
+} RrtSceneTable;
+typedef struct RrtSceneUpdateStats {
+    uint64_t updates;
+    uint64_t last_allocations;
+    uint64_t last_levels;
+} RrtSceneUpdateStats;
+int32_t rrt_testing_sphere_boxes(const RrtSphere *spheres, uint32_t n_spheres, const float *motion, double *out);
+int32_t rrt_testing_scene_read_table(RrtScene *scene, uint32_t what, void *out, size_t cap, size_t *bytes_out);
+int32_t rrt_testing_scene_update_stats(const RrtScene *scene, RrtSceneUpdateStats *out);
 
 /* Test support, not part of the drop-in (no reference counterpart; RRT_ABI_VERSION is unchanged and
  * the Rust shim does not bind it): the launch shape the library picks for a scene, computed on the

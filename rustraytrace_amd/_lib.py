@@ -97,7 +97,22 @@ EXPORTED_SYMBOLS = (
     "rrt_testing_device_ops",
     "rrt_testing_div_check",
     "rrt_testing_device_ops64",
+    "rrt_scene_set_camera",
+    "rrt_scene_update_spheres",
+    "rrt_testing_sphere_boxes",
+    "rrt_testing_scene_read_table",
+    "rrt_testing_scene_update_stats",
 )
+
+# == RrtSceneTable (include/rrt_hip.h, test support): table -> (code, row dtype)
+SCENE_TABLES = {
+    "boxes": (0, np.dtype("<f8")), "prim_cr": (1, np.dtype("<f4")), "prim_mtl": (2, np.dtype("<u4")),
+    "prim_motion": (3, np.dtype("<f4")), "prim_inv_r64": (4, np.dtype("<f8")), "prim_diel64": (5, np.dtype("<f8")),
+}
+
+
+class RrtSceneUpdateStats(ctypes.Structure):  # include/rrt_hip.h, test support
+    _fields_ = [("updates", c_uint64), ("last_allocations", c_uint64), ("last_levels", c_uint64)]
 
 # == RrtDeviceOp (include/rrt_hip.h, test support): op -> (code, f32 columns in, 32-bit words out)
 DEVICE_OPS = {
@@ -280,6 +295,16 @@ def device_ops64(op: str, rows, quads=None) -> np.ndarray:
     return out
 
 
+def sphere_boxes(spheres, motion=None) -> np.ndarray:
+    """rrt_testing_sphere_boxes (test support): each sphere's padded f64 box, (n, 6) float64 (min xyz,
+    max xyz), by the host compilation of the function rrt_scene_update_spheres runs on the device."""
+    sp = np.ascontiguousarray(spheres, dtype=SPHERE_DTYPE)
+    m = None if motion is None else np.ascontiguousarray(motion, dtype=np.float32).reshape(len(sp), 4)
+    out = np.zeros((len(sp), 6), dtype=np.float64)
+    check(load().rrt_testing_sphere_boxes(ptr(sp), len(sp), ptr(m), ptr(out)))
+    return out
+
+
 def div_check(a_values) -> list:
     """rrt_testing_div_check (test support): the eight counters for the divisors a_values."""
     a = np.ascontiguousarray(a_values, dtype=np.float32).ravel()
@@ -378,6 +403,11 @@ def load() -> ctypes.CDLL:
         "rrt_testing_device_ops": (c_int32, [c_uint32, c_uint32, P, P, P]),
         "rrt_testing_device_ops64": (c_int32, [c_uint32, c_uint32, P, P, P]),
         "rrt_testing_div_check": (c_int32, [P, c_uint32, P]),
+        "rrt_scene_set_camera": (c_int32, [P, P]),
+        "rrt_scene_update_spheres": (c_int32, [P, P, c_uint32, P, P]),
+        "rrt_testing_sphere_boxes": (c_int32, [P, c_uint32, P, P]),
+        "rrt_testing_scene_read_table": (c_int32, [P, c_uint32, P, c_size_t, P]),
+        "rrt_testing_scene_update_stats": (c_int32, [P, P]),
     }
     experiment = "RRT_LIB_PATH" in os.environ  # A/B of older builds: tolerate symbols they lack
     for name, (res, args) in sig.items():

@@ -315,8 +315,9 @@ __global__ __launch_bounds__(kBlk) void k_pack(uint32_t n_nodes, const RawNode *
 uint32_t blocks_of(uint32_t n, uint32_t b) { return (n + b - 1u) / b; }
 
 template <class T>
-hipError_t grow(T *&p, size_t &cap, size_t need) {
+hipError_t grow(T *&p, size_t &cap, size_t need, uint64_t &n_alloc) {
     if (need <= cap) return hipSuccess;
+    ++n_alloc;
     if (p) (void)hipFree(p);
     p = nullptr;
     cap = 0;
@@ -351,6 +352,18 @@ struct DeviceBvhBuilder::Impl {
     Slack slack{};
     Summary sum{};
     uint32_t levels = 0;
+    uint64_t n_alloc = 0;  // hipMalloc calls so far (allocations())
+
+    hipError_t grow_scan(size_t n_tasks) {
+        if (n_tasks <= scan_cap) return hipSuccess;
+        (void)hipFree(d_scan);
+        d_scan = nullptr;
+        scan_cap = 0;
+        ++n_alloc;
+        const hipError_t e = hipMalloc((void **)&d_scan, n_tasks * 3 * 4);
+        if (e == hipSuccess) scan_cap = n_tasks;
+        return e;
+    }
 
     ~Impl() {
         (void)hipFree(d_boxes);
@@ -400,8 +413,24 @@ hipError_t DeviceBvhBuilder::upload(const Box6 *boxes, uint32_t n_boxes, const u
     BB_TRY(hipMalloc((void **)&m.d_block, (size_t)nb * 4));
     BB_TRY(hipMalloc((void **)&m.d_totals, 6 * 4));
     BB_TRY(hipMalloc((void **)&m.d_state, sizeof(LevelState)));
+    m.n_alloc += 10;
     return hipSuccess;
 }
+
+// Tasks are disjoint ranges of span >= 2, so a level holds at most n_tree / 2 of them.
+hipError_t DeviceBvhBuilder::reserve() {
+    Impl &m = *impl_;
+    if (m.n_tree < 2u) return hipErrorInvalidValue;
+    const size_t max_tasks = m.n_tree / 2u;
+    for (int k = 0; k < 2; ++k) BB_TRY(grow(m.d_tasks[k], m.tasks_cap[k], max_tasks, m.n_alloc));
+    BB_TRY(grow(m.d_dec, m.dec_cap, max_tasks, m.n_alloc));
+    BB_TRY(grow(m.d_bins, m.bins_cap, max_tasks * (3 * kBins), m.n_alloc));
+    return m.grow_scan(max_tasks);
+}
+
+Box6 *DeviceBvhBuilder::device_boxes() { return impl_->d_boxes; }
+const uint32_t *DeviceBvhBuilder::device_order() const { return impl_->d_order[impl_->cur]; }
+uint64_t DeviceBvhBuilder::allocations() const { return impl_->n_alloc; }
 
 hipError_t DeviceBvhBuilder::build(uint32_t max_leaf, double node_cost, Summary *out) {
     Impl &m = *impl_;
@@ -412,7 +441,7 @@ hipError_t DeviceBvhBuilder::build(uint32_t max_leaf, double node_cost, Summary 
     BB_TRY(hipMemcpy(m.d_order[0], m.d_order0, (size_t)n * 4, hipMemcpyDeviceToDevice));
     BB_TRY(hipMemset(m.d_ptask[0], 0, (size_t)n * 4));  // every primitive in task 0, the root
     BB_TRY(hipMemset(m.d_state, 0, sizeof(LevelState)));
-    BB_TRY(grow(m.d_tasks[0], m.tasks_cap[0], 1));
+    BB_TRY(grow(m.d_tasks[0], m.tasks_cap[0], 1, m.n_alloc));
     Task root;
     root.lo = 0;
     root.hi = n;
@@ -434,16 +463,10 @@ hipError_t DeviceBvhBuilder::build(uint32_t max_leaf, double node_cost, Summary 
         if (level > n) return hipErrorUnknown;  // every split leaves two non-empty sides: depth < n
         const int c = m.cur, o = 1 - m.cur;
         const uint32_t next_cap = std::min<uint64_t>(2ull * n_tasks, n / 2u);
-        BB_TRY(grow(m.d_tasks[o], m.tasks_cap[o], std::max<size_t>(next_cap, 1)));
-        BB_TRY(grow(m.d_dec, m.dec_cap, n_tasks));
-        BB_TRY(grow(m.d_bins, m.bins_cap, (size_t)n_tasks * (3 * kBins)));
-        if (n_tasks > m.scan_cap) {
-            (void)hipFree(m.d_scan);
-            m.d_scan = nullptr;
-            m.scan_cap = 0;
-            BB_TRY(hipMalloc((void **)&m.d_scan, (size_t)n_tasks * 3 * 4));
-            m.scan_cap = n_tasks;
-        }
+        BB_TRY(grow(m.d_tasks[o], m.tasks_cap[o], std::max<size_t>(next_cap, 1), m.n_alloc));
+        BB_TRY(grow(m.d_dec, m.dec_cap, n_tasks, m.n_alloc));
+        BB_TRY(grow(m.d_bins, m.bins_cap, (size_t)n_tasks * (3 * kBins), m.n_alloc));
+        BB_TRY(m.grow_scan(n_tasks));
         uint32_t *s_node = m.d_scan, *s_child = m.d_scan + m.scan_cap, *s_left = m.d_scan + 2 * m.scan_cap;
         const uint64_t bin_words = (uint64_t)n_tasks * kTaskWords;
         const uint32_t tb = blocks_of(n_tasks, 64u);
@@ -485,17 +508,26 @@ hipError_t DeviceBvhBuilder::emit(uint32_t stride, uint8_t **d_nodes_out, uint32
     Impl &m = *impl_;
     if ((stride != 80u && stride != 32u) || m.sum.n_nodes == 0) return hipErrorInvalidValue;
     uint8_t *d = nullptr;
+    ++m.n_alloc;
     BB_TRY(hipMalloc((void **)&d, (size_t)m.sum.n_nodes * stride));
-    hipLaunchKernelGGL(k_pack, dim3(blocks_of(m.sum.n_nodes, kBlk)), dim3(kBlk), 0, 0, m.sum.n_nodes, m.d_raw, m.slack,
-                       stride, (uint32_t *)d);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpy(order_out, m.d_order[m.cur], (size_t)m.n_tree * 4, hipMemcpyDeviceToHost);
+    const hipError_t e = emit_into(stride, d, (size_t)m.sum.n_nodes * stride, order_out);
     if (e != hipSuccess) {
         (void)hipFree(d);
         return e;
     }
     *d_nodes_out = d;
     return hipSuccess;
+}
+
+hipError_t DeviceBvhBuilder::emit_into(uint32_t stride, uint8_t *d_nodes, size_t cap_bytes, uint32_t *order_out) {
+    Impl &m = *impl_;
+    if ((stride != 80u && stride != 32u) || m.sum.n_nodes == 0 || !d_nodes ||
+        (size_t)m.sum.n_nodes * stride > cap_bytes)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_pack, dim3(blocks_of(m.sum.n_nodes, kBlk)), dim3(kBlk), 0, 0, m.sum.n_nodes, m.d_raw, m.slack,
+                       stride, (uint32_t *)d_nodes);
+    BB_TRY(hipGetLastError());
+    return hipMemcpy(order_out, m.d_order[m.cur], (size_t)m.n_tree * 4, hipMemcpyDeviceToHost);
 }
 
 uint32_t DeviceBvhBuilder::levels() const { return impl_->levels; }

@@ -10,10 +10,12 @@
 // without a HIP device every render entry fails with RRT_E_NODEV.
 #include "rrt_internal.h"
 #include "rrt_bvh_binned.h"
+#include "rrt_sphere_box.h"
 #include "../../include/rrt_hip.h"
 
 #include <algorithm>
 #include <limits>
+#include <memory>
 #include <atomic>
 #include <chrono>
 #include <cmath>
@@ -1007,16 +1009,14 @@ FlatBvh flatten_binned(const BinnedTree &bt, uint32_t stride, const BinnedInput 
     return f;
 }
 
-// scene_bvh's composition with the device builder: the LDS shape kept when it fits (and not built
-// when the primitive records alone exceed the budget: it would be discarded), else the global shape
-// in 32-B nodes, else the documented fallback to the caller's leaf size. The nodes stay on the
-// device (d_nodes, owned by the caller); the order and the summary come back. n_tree >= 2.
-// leaf_param: the leaf size of the shape that was kept.
-int scene_bvh_device(const BinnedInput &in, size_t n_prims_all, uint32_t max_leaf, bool book2, bool f64, FlatBvh &fb,
-                     uint8_t **d_nodes, std::vector<uint32_t> &order, uint32_t &leaf_param, uint32_t &levels) {
-    rrt::DeviceBvhBuilder bld;
-    if (bld.upload(in.boxes.data(), (uint32_t)in.boxes.size(), in.objs.data(), (uint32_t)in.objs.size()) != hipSuccess)
-        return fail(RRT_E_HIP, "device BVH: upload failed");
+// scene_bvh's composition with the device builder, over a builder that holds the boxes: the LDS
+// shape kept when it fits (and not built when the primitive records alone exceed the budget: it
+// would be discarded), else the global shape in 32-B nodes, else the documented fallback to the
+// caller's leaf size. sum / stride / leaf_param describe the shape that was kept (leaf_param: its
+// leaf size) and the builder holds its tree. Scene creation and rrt_scene_update_spheres both choose
+// here.
+int bvh_device_shape(rrt::DeviceBvhBuilder &bld, size_t n_prims_all, uint32_t max_leaf, bool book2, bool f64,
+                     bvhb::Summary &sum, uint32_t &stride, uint32_t &leaf_param, uint32_t &levels) {
     auto cost = [](double c) {
         if (const char *e = std::getenv("RRT_SAH_CT")) return std::atof(e);
         return c;
@@ -1026,9 +1026,9 @@ int scene_bvh_device(const BinnedInput &in, size_t n_prims_all, uint32_t max_lea
         if (f64) return rrt::f64_lds_min_bytes(s.n_nodes, (uint32_t)n_prims_all, s.max_depth + 1) <= 64u * 1024u;
         return scene_lds_fit((size_t)s.n_nodes * sizeof(rrt::GNode), n_prims_all, book2);
     };
-    bvhb::Summary sum{};
+    sum = bvhb::Summary{};
     levels = 0;
-    uint32_t stride = 0;
+    stride = 0;
     bvhb::Summary none{};
     none.n_nodes = 1, none.max_depth = 1;
     if (fits(none)) {  // the primitive records leave room for a node
@@ -1048,6 +1048,19 @@ int scene_bvh_device(const BinnedInput &in, size_t n_prims_all, uint32_t max_lea
             levels += bld.levels();
         }
     }
+    return RRT_OK;
+}
+
+// Scene creation's device build: upload, the shape choice, and the nodes emitted to a fresh device
+// array (d_nodes, owned by the caller); the order and the summary come back. n_tree >= 2.
+int scene_bvh_device(rrt::DeviceBvhBuilder &bld, const BinnedInput &in, size_t n_prims_all, uint32_t max_leaf, bool book2,
+                     bool f64, FlatBvh &fb, uint8_t **d_nodes, std::vector<uint32_t> &order, uint32_t &leaf_param,
+                     uint32_t &levels) {
+    if (bld.upload(in.boxes.data(), (uint32_t)in.boxes.size(), in.objs.data(), (uint32_t)in.objs.size()) != hipSuccess)
+        return fail(RRT_E_HIP, "device BVH: upload failed");
+    bvhb::Summary sum{};
+    uint32_t stride = 0;
+    if (int rc = bvh_device_shape(bld, n_prims_all, max_leaf, book2, f64, sum, stride, leaf_param, levels)) return rc;
     fb = flat_of_summary(sum, stride, in);
     order.assign(in.objs.size(), 0u);
     if (bld.emit(stride, d_nodes, order.data()) != hipSuccess) return fail(RRT_E_HIP, "device BVH: emit failed");
@@ -1091,6 +1104,23 @@ struct RrtScene {
     rrt::KParams base{};
     RrtBvhInfo info{};
     std::vector<uint32_t> order;  // the leaf order (rrt_scene_read_bvh)
+    bool book2 = false;           // the book-2/3 kernel variant (fixed at creation)
+    // rrt_scene_update_spheres: what a scene built by the device builder keeps between frames. The
+    // builder holds the padded boxes of every primitive and all its workspace; the source-order
+    // tables below are what the leaf-order tables are re-formed from.
+    bool device_bvh = false;                  // created with RRT_FLAG_DEVICE_BVH
+    rrt::DeviceBvhBuilder *builder = nullptr; // kept when it built the tree (>= 2 primitives)
+    uint32_t n_spheres = 0, n_materials = 0, max_leaf = 0;
+    bool quads_in_sphere32 = true;            // the quads' prim_cr rows pass the sphere32 range check
+    rrt::GMaterial *d_src_mats = nullptr;     // the GMaterial table
+    double4 *d_src_diel = nullptr;            // f64: per material, a dielectric's f64 constants
+    float4 *d_quad_rows = nullptr;            // per quad: its prim_cr row and its prim_motion row
+    uint32_t *d_quad_mat = nullptr;           // per quad: its material index
+    RrtSphere *d_src_spheres = nullptr;       // the last update's spheres and motion rows (first update on)
+    float *d_src_motion = nullptr;
+    size_t nodes_cap = 0;                     // bytes of d_nodes once it holds the largest tree (first update on)
+    uint64_t n_updates = 0, last_update_allocs = 0, last_update_levels = 0;
+    std::string failed_update;                // non-empty: an update failed midway, renders are refused
 };
 
 namespace {
@@ -1119,6 +1149,13 @@ void free_scene(RrtScene *s) {
     (void)hipFree(s->d_accum64);
     (void)hipFree(s->d_seq64);
     (void)hipFree(s->d_hist);
+    (void)hipFree(s->d_src_mats);
+    (void)hipFree(s->d_src_diel);
+    (void)hipFree(s->d_quad_rows);
+    (void)hipFree(s->d_quad_mat);
+    (void)hipFree(s->d_src_spheres);
+    (void)hipFree(s->d_src_motion);
+    delete s->builder;
     delete s;
 }
 
@@ -1157,6 +1194,9 @@ int check_tile_shape(const RrtTile *t) {
 
 int check_tile(const RrtScene *s, const RrtTile *t) {
     if (!s) return fail(RRT_E_INVALID, "null scene");
+    if (!s->failed_update.empty())
+        return fail(RRT_E_INVALID, "the scene is invalid since rrt_scene_update_spheres failed (" + s->failed_update +
+                                       "); a later update that succeeds makes it valid again");
     if (int rc = check_tile_shape(t)) return rc;
     const uint32_t sq = s->base.sqrt_spp;
     if (sq && (uint64_t)t->sample_end > (uint64_t)sq * sq)  // book 3: s = s_j * sqrt_spp + s_i
@@ -1408,6 +1448,130 @@ static bool pack_perlin(const RrtPerlin &src, rrt::GPerlin &dst) {
     return true;
 }
 
+// ---- what scene creation derives, in functions rrt_scene_set_camera and rrt_scene_update_spheres
+// call too: an updated scene equals a fresh one because both run these.
+// Book 3's stratified sampling: samples_per_pixel must be a square (camera.rs:115-117).
+static int32_t camera_sqrt_spp(const RrtCamera *cam, uint32_t &sqrt_spp) {
+    const uint32_t spp = (uint32_t)std::max(cam->params_f[3], 1.0f);
+    sqrt_spp = (uint32_t)std::sqrt((double)spp);
+    if (sqrt_spp * sqrt_spp != spp)
+        return fail(RRT_E_INVALID, "RRT_FLAG_BOOK3 samples_per_pixel must be a square (sqrt_spp^2, camera.rs:115-117)");
+    return RRT_OK;
+}
+static int32_t camera_size_check(const RrtCamera *cam) {
+    const float wf = cam->params_f[1], hf = cam->params_f[2];
+    if (!(wf >= 1.0f) || !(hf >= 1.0f) || wf > 65536.0f || hf > 65536.0f)
+        return fail(RRT_E_INVALID, "camera params_f[1..2] (width/height) out of range");
+    return RRT_OK;
+}
+// A material's f64 dielectric constants (KParams.prim_diel64): zeros unless it is a dielectric.
+static double4 material_diel64(const rrt::GMaterial &m) {
+    if (m.b.x != RRT_MAT_DIELECTRIC) return make_double4(0.0, 0.0, 0.0, 0.0);
+    float eta32;
+    std::memcpy(&eta32, &m.b.y, sizeof(float));
+    double inv_eta, r0_front, r0_back;
+    dielectric_consts64((double)eta32, inv_eta, r0_front, r0_back);
+    return make_double4(inv_eta, r0_front, r0_back, 0.0);
+}
+// The camera block of KParams (sqrt_spp: 0 unless RRT_FLAG_BOOK3).
+static void camera_params(const RrtCamera *cam, uint32_t sqrt_spp, rrt::KParams &p) {
+    p.sqrt_spp = sqrt_spp;
+    p.recip_sqrt_spp = sqrt_spp ? (float)(1.0 / (double)sqrt_spp) : 0.0f;  // camera.rs:117
+    const float radius = cam->params_f[0];
+    for (int i = 0; i < 3; ++i) {
+        p.p00[i] = cam->pixel00[i];
+        p.du[i] = cam->pixel_delta_u[i];
+        p.dv[i] = cam->pixel_delta_v[i];
+        p.center[i] = cam->origin[i];
+        p.disk_u[i] = cam->u[i] * radius;  // defocus_disk_u = u * defocus_radius (camera.rs:136-138)
+        p.disk_v[i] = cam->v[i] * radius;
+        p.cam_u[i] = cam->u[i];
+        p.cam_v[i] = cam->v[i];
+        p.background[i] = cam->background[i];
+        p.cam64[0][i] = (double)cam->pixel00[i];
+        p.cam64[1][i] = (double)cam->pixel_delta_u[i];
+        p.cam64[2][i] = (double)cam->pixel_delta_v[i];
+        p.cam64[3][i] = (double)cam->origin[i];
+        p.cam64[4][i] = (double)cam->u[i] * (double)radius;  // camera.rs:136-138 in f64
+        p.cam64[5][i] = (double)cam->v[i] * (double)radius;
+    }
+    p.defocus_radius = radius;
+    p.max_depth = cam->params_u[0];
+    p.seed = cam->params_u[1];
+    p.bg_mode = cam->params_u[3];
+    p.width = (uint32_t)cam->params_f[1];
+    p.height = (uint32_t)cam->params_f[2];
+}
+
+// The f64 kernel's f32 sphere pre-test (rrt_sphere32.h) holds for centers and radii within 2^20:
+// one prim_cr row's test, and the flag from all rows' (RRT_F64_PRETEST=0 switches it off).
+static bool row_in_sphere32(float x, float y, float z, float w) {
+    return std::fabs(x) <= 0x1.0p20f && std::fabs(y) <= 0x1.0p20f && std::fabs(z) <= 0x1.0p20f && std::fabs(w) <= 0x1.0p20f;
+}
+static uint32_t sphere32_flag(bool all_rows_in) {
+    uint32_t on = all_rows_in ? 1u : 0u;
+    if (const char *e = std::getenv("RRT_F64_PRETEST")) on = on && std::atoi(e) != 0;
+    return on;
+}
+
+// What follows from the tree: its counts, where the scene is staged, the traversal thresholds and
+// where the Perlin tables go. Reads p.flags, p.n_quads, p.n_media, p.min_waves and p.global_waves.
+static void tree_params(rrt::KParams &p, const FlatBvh &fb, size_t node_bytes, bool book2) {
+    p.n_nodes = fb.n_nodes;
+    p.n_unbounded = fb.n_unbounded;
+    p.stack_depth = fb.stack_need;
+    p.bvh_width = fb.width;
+    // BVH2: the node layout already encodes the choice (80-B sign-ordered nodes are the LDS ones)
+    p.scene_in_lds = fb.width == 2 ? fb.stride == (uint32_t)sizeof(rrt::GNode)
+                                   : scene_lds_fit(node_bytes, p.n_prims, book2);
+    // traversal exit / leaf batch thresholds (x/256 of the live lanes), same-box sweeps against 32/32:
+    // book-1 LDS scenes 56/56 (C2 +0.6 %, C4 +0.25 %); L2 scenes 64/48 (C5 +2.0 %, final_scene and
+    // bouncing spheres +4 %). Book-2/3 LDS scenes by kernel class (round 6, after the class launch
+    // shapes): spheres only 32/32; quads 48/48 (cornell_box +3.6 %); media 24/24 (cornell_smoke
+    // +3.2 %); book 3 48/32 (+1.4 %) (profiles/r6_thresholds_sweep.log)
+    {
+        const int cls = (p.flags & RRT_FLAG_BOOK3) ? 4 : p.n_media ? 3 : p.n_quads ? 2 : 1;
+        const uint32_t b2_trav = cls == 2 || cls == 4 ? 48u : cls == 3 ? 24u : 32u;
+        const uint32_t b2_leaf = cls == 2 ? 48u : cls == 3 ? 24u : 32u;
+        p.trav_frac = p.scene_in_lds ? (book2 ? b2_trav : 56u) : 64u;
+        p.leaf_frac = p.scene_in_lds ? (book2 ? b2_leaf : 56u) : 48u;
+    }
+    if (const char *e = std::getenv("RRT_TRAV_FRAC")) p.trav_frac = (uint32_t)std::min(256, std::max(0, std::atoi(e)));
+    if (const char *e = std::getenv("RRT_LEAF_FRAC")) p.leaf_frac = (uint32_t)std::min(256, std::max(0, std::atoi(e)));
+    // Perlin tables in LDS when the block that launches (rrt::plan_launch) still fits 64 KB with them
+    p.perlin_in_lds = rrt::perlin_fits_lds(p) ? 1u : 0u;
+    if (const char *e = std::getenv("RRT_PERLIN_IN_LDS")) p.perlin_in_lds = p.perlin_in_lds && std::atoi(e) != 0;
+}
+// Every render of the scene launches rrt::plan_launch(p); a scene without a plan is refused.
+static int32_t plan_check(const rrt::KParams &p) {
+    if (rrt::plan_launch(p).ok) return RRT_OK;
+    return fail(RRT_E_INVALID, "no launch shape holds the scene's traversal stack (" + std::to_string(p.stack_depth) +
+                                   " entries) and staged data within a block's " +
+                                   std::to_string(rrt::kLdsBlockMax / 1024u) + " KiB of LDS");
+}
+// The limits every tree must keep, whichever builder made it.
+static int32_t tree_limits(const FlatBvh &fb, bool f64) {
+    if (fb.stack_need > (uint32_t)rrt::kMaxStackDepth)
+        return fail(RRT_E_INVALID, "BVH depth " + std::to_string(fb.max_depth) + " exceeds the LDS stack");
+    if (f64 && fb.n_nodes > 65535u) return fail(RRT_E_INVALID, "RRT_FLAG_F64: more than 65535 BVH nodes");
+    // postponed leaf tests pack (first primitive, count) as first | count << 28
+    if (fb.max_leaf > (fb.width == 2 ? rrt::kMaxLeafPrims : 15u)) return fail(RRT_E_INVALID, "leaf size too large");
+    if (!fb.sibling_leaves_adjacent) return fail(RRT_E_INVALID, "internal: BVH2 sibling leaves not adjacent");
+    return RRT_OK;
+}
+// The tree's part of RrtBvhInfo (prim_bytes depends on the primitive counts alone).
+static void bvh_info_tree(RrtBvhInfo &bi, const FlatBvh &fb, size_t node_bytes, uint32_t leaf_param) {
+    bi.n_nodes = fb.n_nodes;
+    bi.n_leaves = fb.n_leaves;
+    bi.max_depth = fb.max_depth;
+    bi.max_leaf_size = fb.max_leaf;
+    bi.node_bytes = node_bytes;
+    bi.node_stride = fb.stride;
+    bi.width = fb.width;
+    bi.max_leaf_param = leaf_param;
+    bi.n_unbounded = fb.n_unbounded;
+}
+
 static int32_t scene_create(const RrtCamera *cam, const RrtSphere *spheres, uint32_t n_spheres,
                             const RrtMaterial *materials, uint32_t n_materials, const RrtTexture *textures,
                             uint32_t n_textures, const RrtSceneExt *ext, uint32_t flags, int32_t device,
@@ -1471,10 +1635,7 @@ static int32_t scene_create(const RrtCamera *cam, const RrtSphere *spheres, uint
     if (book3) {
         if (!(flags & RRT_FLAG_RAY_TIME)) return fail(RRT_E_INVALID, "RRT_FLAG_BOOK3 needs RRT_FLAG_RAY_TIME");
         if (ex.n_lights == 0) return fail(RRT_E_INVALID, "RRT_FLAG_BOOK3 needs a non-empty RrtSceneExt.lights");
-        const uint32_t spp = (uint32_t)std::max(cam->params_f[3], 1.0f);
-        sqrt_spp = (uint32_t)std::sqrt((double)spp);
-        if (sqrt_spp * sqrt_spp != spp)
-            return fail(RRT_E_INVALID, "RRT_FLAG_BOOK3 samples_per_pixel must be a square (sqrt_spp^2, camera.rs:115-117)");
+        if (int rc = camera_sqrt_spp(cam, sqrt_spp)) return rc;
         for (uint32_t l = 0; l < ex.n_lights; ++l)
             if (ex.lights[l].kind > RRT_LIGHT_SPHERE)
                 return fail(RRT_E_INVALID, "light " + std::to_string(l) + ": unknown kind");
@@ -1506,9 +1667,7 @@ static int32_t scene_create(const RrtCamera *cam, const RrtSphere *spheres, uint
     if (n_materials && !materials) return fail(RRT_E_INVALID, "null materials");
     if (n_textures && !textures) return fail(RRT_E_INVALID, "null textures");
     *out = nullptr;
-    const float wf = cam->params_f[1], hf = cam->params_f[2];
-    if (!(wf >= 1.0f) || !(hf >= 1.0f) || wf > 65536.0f || hf > 65536.0f)
-        return fail(RRT_E_INVALID, "camera params_f[1..2] (width/height) out of range");
+    if (int rc = camera_size_check(cam)) return rc;
     for (uint32_t i = 0; i < n_spheres; ++i)
         if (spheres[i].material_index >= n_materials)
             return fail(RRT_E_INVALID, "sphere " + std::to_string(i) + " material_index out of range");
@@ -1542,25 +1701,22 @@ static int32_t scene_create(const RrtCamera *cam, const RrtSphere *spheres, uint
     } dev_nodes;
     uint32_t leaf_param = max_leaf;
     bool built_on_device = false;
+    std::unique_ptr<rrt::DeviceBvhBuilder> builder;  // the scene keeps it (rrt_scene_update_spheres)
     if (device_bvh) {
         const BinnedInput in = binned_input(spheres, n_spheres, ex);
         if (in.objs.size() > 1) {
             if (hipSetDevice(device) != hipSuccess) return fail(RRT_E_HIP, "hipSetDevice failed");
             uint32_t levels = 0;
-            if (int rc = scene_bvh_device(in, (size_t)n_spheres + n_quads + n_media, max_leaf, book2, f64, fb, &dev_nodes.p,
-                                          order, leaf_param, levels))
+            builder.reset(new rrt::DeviceBvhBuilder);
+            if (int rc = scene_bvh_device(*builder, in, (size_t)n_spheres + n_quads + n_media, max_leaf, book2, f64, fb,
+                                          &dev_nodes.p, order, leaf_param, levels))
                 return rc;
             built_on_device = true;
         }
     }
     if (!built_on_device) fb = scene_bvh(spheres, n_spheres, ex, width, max_leaf, book2, f64, order);
     const size_t node_bytes = built_on_device ? (size_t)fb.n_nodes * fb.stride : fb.bytes.size();
-    if (fb.stack_need > (uint32_t)rrt::kMaxStackDepth)
-        return fail(RRT_E_INVALID, "BVH depth " + std::to_string(fb.max_depth) + " exceeds the LDS stack");
-    if (f64 && fb.n_nodes > 65535u) return fail(RRT_E_INVALID, "RRT_FLAG_F64: more than 65535 BVH nodes");
-    // postponed leaf tests pack (first primitive, count) as first | count << 28
-    if (fb.max_leaf > (fb.width == 2 ? rrt::kMaxLeafPrims : 15u)) return fail(RRT_E_INVALID, "leaf size too large");
-    if (!fb.sibling_leaves_adjacent) return fail(RRT_E_INVALID, "internal: BVH2 sibling leaves not adjacent");
+    if (int rc = tree_limits(fb, f64)) return rc;
     const uint32_t n_prims = n_spheres + n_quads + n_media;
 
     std::vector<rrt::GMaterial> mats(n_materials);
@@ -1693,6 +1849,12 @@ static int32_t scene_create(const RrtCamera *cam, const RrtSphere *spheres, uint
     RrtScene *s = new RrtScene();
     s->device = device;
     s->f64 = f64;
+    s->book2 = book2;
+    s->device_bvh = device_bvh;
+    s->n_spheres = n_spheres;
+    s->n_materials = n_materials;
+    s->max_leaf = max_leaf;
+    if (built_on_device) s->builder = builder.release();
     int rc = RRT_OK;
     do {
         if (hipSetDevice(device) != hipSuccess) { rc = fail(RRT_E_HIP, "hipSetDevice failed"); break; }
@@ -1708,15 +1870,32 @@ static int32_t scene_create(const RrtCamera *cam, const RrtSphere *spheres, uint
             for (uint32_t i = 0; i < n_prims; ++i) inv_r[i] = 1.0 / (double)prim_cr[i].w;
             if ((rc = upload(&s->d_prim_inv_r64, inv_r.data(), inv_r.size(), "sphere 1/r"))) break;
             std::vector<double4> diel(n_prims, make_double4(0.0, 0.0, 0.0, 0.0));
-            for (uint32_t i = 0; i < n_prims; ++i) {
-                if (prim_mtl[i].b.x != RRT_MAT_DIELECTRIC) continue;
-                float eta32;
-                std::memcpy(&eta32, &prim_mtl[i].b.y, sizeof(float));
-                double inv_eta, r0_front, r0_back;
-                dielectric_consts64((double)eta32, inv_eta, r0_front, r0_back);
-                diel[i] = make_double4(inv_eta, r0_front, r0_back, 0.0);
-            }
+            for (uint32_t i = 0; i < n_prims; ++i) diel[i] = material_diel64(prim_mtl[i]);
             if ((rc = upload(&s->d_prim_diel64, diel.data(), diel.size(), "dielectric constants"))) break;
+        }
+        // rrt_scene_update_spheres re-forms the tables above on the device, from these in source order
+        if (built_on_device && !n_media && !book3) {
+            if ((rc = upload(&s->d_src_mats, mats.data(), mats.size(), "material table"))) break;
+            if (f64) {
+                std::vector<double4> mat_diel(n_materials);
+                for (uint32_t k = 0; k < n_materials; ++k) mat_diel[k] = material_diel64(mats[k]);
+                if ((rc = upload(&s->d_src_diel, mat_diel.data(), mat_diel.size(), "material dielectric constants"))) break;
+            }
+            if (n_quads) {
+                std::vector<float4> rows(2 * (size_t)n_quads);
+                std::vector<uint32_t> quad_mat(n_quads);
+                for (uint32_t i = 0; i < n_prims; ++i) {
+                    if (order[i] < n_spheres) continue;
+                    const uint32_t j = order[i] - n_spheres;
+                    rows[2 * (size_t)j] = prim_cr[i];
+                    rows[2 * (size_t)j + 1] = prim_motion[i];
+                    quad_mat[j] = quads[j].material_index;
+                    s->quads_in_sphere32 = s->quads_in_sphere32 &&
+                                           row_in_sphere32(prim_cr[i].x, prim_cr[i].y, prim_cr[i].z, prim_cr[i].w);
+                }
+                if ((rc = upload(&s->d_quad_rows, rows.data(), rows.size(), "quad rows"))) break;
+                if ((rc = upload(&s->d_quad_mat, quad_mat.data(), quad_mat.size(), "quad materials"))) break;
+            }
         }
         if (n_perlin && (rc = upload(&s->d_perlin, perlin.data(), perlin.size(), "Perlin tables"))) break;
         if (f64_book2) {  // the f64 kernel reads the unrounded records (GQuad64) and no f32 one
@@ -1756,9 +1935,8 @@ static int32_t scene_create(const RrtCamera *cam, const RrtSphere *spheres, uint
     if (f64) {
         bool in = true;
         for (uint32_t i = 0; i < n_prims && in; ++i)
-            for (int k = 0; k < 4; ++k) in = in && std::fabs((&prim_cr[i].x)[k]) <= 0x1.0p20f;
-        p.sphere32 = in ? 1u : 0u;
-        if (const char *e = std::getenv("RRT_F64_PRETEST")) p.sphere32 = p.sphere32 && std::atoi(e) != 0;
+            in = row_in_sphere32(prim_cr[i].x, prim_cr[i].y, prim_cr[i].z, prim_cr[i].w);
+        p.sphere32 = sphere32_flag(in);
     }
     p.prim_motion = s->d_prim_motion;
     p.perlin = s->d_perlin;
@@ -1769,61 +1947,17 @@ static int32_t scene_create(const RrtCamera *cam, const RrtSphere *spheres, uint
     p.n_media = n_media;
     p.lights = s->d_lights;
     p.n_lights = (uint32_t)glights.size();
-    p.sqrt_spp = sqrt_spp;
     p.image_tex = 0;
     for (uint32_t i = 0; i < n_materials; ++i) p.image_tex |= materials[i].kind == RRT_MAT_TEXTURED_LAMBERTIAN ? 1u : 0u;
     p.specular = 0;
     for (uint32_t i = 0; i < n_materials; ++i)
         p.specular |= materials[i].kind == RRT_MAT_METAL || materials[i].kind == RRT_MAT_DIELECTRIC ? 1u : 0u;
-    p.recip_sqrt_spp = sqrt_spp ? (float)(1.0 / (double)sqrt_spp) : 0.0f;  // camera.rs:117
     p.tex_pool = s->d_tex_pool;
     p.texs = s->d_texs;
     p.counters = s->d_counters;
-    const float radius = cam->params_f[0];
-    for (int i = 0; i < 3; ++i) {
-        p.p00[i] = cam->pixel00[i];
-        p.du[i] = cam->pixel_delta_u[i];
-        p.dv[i] = cam->pixel_delta_v[i];
-        p.center[i] = cam->origin[i];
-        p.disk_u[i] = cam->u[i] * radius;  // defocus_disk_u = u * defocus_radius (camera.rs:136-138)
-        p.disk_v[i] = cam->v[i] * radius;
-        p.cam_u[i] = cam->u[i];
-        p.cam_v[i] = cam->v[i];
-        p.background[i] = cam->background[i];
-        p.cam64[0][i] = (double)cam->pixel00[i];
-        p.cam64[1][i] = (double)cam->pixel_delta_u[i];
-        p.cam64[2][i] = (double)cam->pixel_delta_v[i];
-        p.cam64[3][i] = (double)cam->origin[i];
-        p.cam64[4][i] = (double)cam->u[i] * (double)radius;  // camera.rs:136-138 in f64
-        p.cam64[5][i] = (double)cam->v[i] * (double)radius;
-    }
-    p.defocus_radius = radius;
-    p.max_depth = cam->params_u[0];
-    p.seed = cam->params_u[1];
-    p.bg_mode = cam->params_u[3];
+    camera_params(cam, sqrt_spp, p);
     p.flags = flags;
-    p.width = (uint32_t)wf;
-    p.height = (uint32_t)hf;
-    p.n_nodes = fb.n_nodes;
     p.n_prims = n_prims;
-    p.n_unbounded = fb.n_unbounded;
-    p.stack_depth = fb.stack_need;
-    p.bvh_width = fb.width;
-    // BVH2: the node layout already encodes the choice (80-B sign-ordered nodes are the LDS ones)
-    p.scene_in_lds = fb.width == 2 ? fb.stride == (uint32_t)sizeof(rrt::GNode)
-                                   : scene_lds_fit(node_bytes, n_prims, book2);
-    // traversal exit / leaf batch thresholds (x/256 of the live lanes), same-box sweeps against 32/32:
-    // book-1 LDS scenes 56/56 (C2 +0.6 %, C4 +0.25 %); L2 scenes 64/48 (C5 +2.0 %, final_scene and
-    // bouncing spheres +4 %). Book-2/3 LDS scenes by kernel class (round 6, after the class launch
-    // shapes): spheres only 32/32; quads 48/48 (cornell_box +3.6 %); media 24/24 (cornell_smoke
-    // +3.2 %); book 3 48/32 (+1.4 %) (profiles/r6_thresholds_sweep.log)
-    {
-        const int cls = book3 ? 4 : n_media ? 3 : n_quads ? 2 : 1;
-        const uint32_t b2_trav = cls == 2 || cls == 4 ? 48u : cls == 3 ? 24u : 32u;
-        const uint32_t b2_leaf = cls == 2 ? 48u : cls == 3 ? 24u : 32u;
-        p.trav_frac = p.scene_in_lds ? (book2 ? b2_trav : 56u) : 64u;
-        p.leaf_frac = p.scene_in_lds ? (book2 ? b2_leaf : 56u) : 48u;
-    }
     p.min_waves = 6;
     p.chunk = accum_chunk();
     {
@@ -1834,30 +1968,16 @@ static int32_t scene_create(const RrtCamera *cam, const RrtSphere *spheres, uint
     if (const char *e = std::getenv("RRT_MIN_WAVES")) p.min_waves = (uint32_t)std::atoi(e);
     p.global_waves = 7;  // L2 scenes: 256 x 7 (rrt_kernel.hip launch_width); 6 = 512 x 6, < 6 no bound
     if (const char *e = std::getenv("RRT_GLOBAL_WAVES")) p.global_waves = (uint32_t)std::atoi(e);
-    if (const char *e = std::getenv("RRT_TRAV_FRAC")) p.trav_frac = (uint32_t)std::min(256, std::max(0, std::atoi(e)));
-    if (const char *e = std::getenv("RRT_LEAF_FRAC")) p.leaf_frac = (uint32_t)std::min(256, std::max(0, std::atoi(e)));
-    // Perlin tables in LDS when the block that launches (rrt::plan_launch) still fits 64 KB with them
-    p.perlin_in_lds = rrt::perlin_fits_lds(p) ? 1u : 0u;
-    if (const char *e = std::getenv("RRT_PERLIN_IN_LDS")) p.perlin_in_lds = p.perlin_in_lds && std::atoi(e) != 0;
-    // every render of the scene launches this plan; a scene without one fails here, not at a launch
-    if (!rrt::plan_launch(p).ok) {
+    tree_params(p, fb, node_bytes, book2);
+    // a scene without a launch plan fails here, not at a launch
+    if (int rc = plan_check(p)) {
         free_scene(s);
-        return fail(RRT_E_INVALID, "no launch shape holds the scene's traversal stack (" + std::to_string(fb.stack_need) +
-                                       " entries) and staged data within a block's " +
-                                       std::to_string(rrt::kLdsBlockMax / 1024u) + " KiB of LDS");
+        return rc;
     }
 
     RrtBvhInfo &bi = s->info;
-    bi.n_nodes = fb.n_nodes;
-    bi.n_leaves = fb.n_leaves;
-    bi.max_depth = fb.max_depth;
-    bi.max_leaf_size = fb.max_leaf;
-    bi.node_bytes = node_bytes;
-    bi.node_stride = fb.stride;
-    bi.width = fb.width;
-    bi.max_leaf_param = built_on_device ? leaf_param : max_leaf;  // the device builder reports the kept shape's
+    bvh_info_tree(bi, fb, node_bytes, built_on_device ? leaf_param : max_leaf);  // the device builder reports the kept shape's
     s->order = order;
-    bi.n_unbounded = fb.n_unbounded;
     bi.prim_bytes = (uint64_t)n_prims * (rrt::kPrimBytes + (book2 ? rrt::kMotionBytes : 0)) +
                     (uint64_t)gquads.size() * (f64_book2 ? sizeof(rrt::GQuad64) : sizeof(rrt::GQuad)) +
                     (uint64_t)n_media * sizeof(rrt::GMedium);
@@ -1950,6 +2070,134 @@ int32_t rrt_scene_read_bvh(RrtScene *scene, void *nodes_out, size_t nodes_cap, u
     HIP_TRY(hipSetDevice(scene->device), "hipSetDevice");
     HIP_TRY(hipMemcpy(nodes_out, scene->d_nodes, bytes, hipMemcpyDeviceToHost), "copy nodes");
     if (scene->order.size()) std::memcpy(prim_order_out, scene->order.data(), scene->order.size() * sizeof(uint32_t));
+    return RRT_OK;
+}
+
+int32_t rrt_scene_set_camera(RrtScene *scene, const RrtCamera *cam) {
+    if (!scene || !cam) return fail(RRT_E_INVALID, "rrt_scene_set_camera: null scene or camera");
+    uint32_t sqrt_spp = 0;
+    if (scene->base.flags & RRT_FLAG_BOOK3)
+        if (int rc = camera_sqrt_spp(cam, sqrt_spp)) return rc;
+    if (int rc = camera_size_check(cam)) return rc;
+    camera_params(cam, sqrt_spp, scene->base);
+    return RRT_OK;
+}
+
+int32_t rrt_scene_update_spheres(RrtScene *scene, const RrtSphere *spheres, uint32_t n_spheres, const float *motion,
+                                 void *stream) {
+    const std::string fn = "rrt_scene_update_spheres: ";
+    RrtScene *s = scene;
+    if (!s) return fail(RRT_E_INVALID, fn + "null scene");
+    if (n_spheres != s->n_spheres)
+        return fail(RRT_E_INVALID, fn + "n_spheres is " + std::to_string(n_spheres) + ", the scene's is " +
+                                       std::to_string(s->n_spheres) + " (the primitive count is fixed at creation)");
+    if (n_spheres && !spheres) return fail(RRT_E_INVALID, fn + "null spheres");
+    if (!s->device_bvh)
+        return fail(RRT_E_INVALID, fn + "the scene was not created with RRT_FLAG_DEVICE_BVH (the update rebuilds its "
+                                        "tree with the device builder)");
+    if (s->base.n_media)
+        return fail(RRT_E_INVALID, fn + "scenes with constant media are not updated (which media are unbounded "
+                                        "depends on every sphere)");
+    if (s->base.flags & RRT_FLAG_BOOK3)
+        return fail(RRT_E_INVALID, fn + "RRT_FLAG_BOOK3 scenes are not updated (their light list restates geometry)");
+    if (!s->builder)
+        return fail(RRT_E_INVALID, fn + "a tree of fewer than 2 primitives is the root-leaf form the host builder writes");
+    for (uint32_t i = 0; i < n_spheres; ++i)
+        if (spheres[i].material_index >= s->n_materials)
+            return fail(RRT_E_INVALID, fn + "sphere " + std::to_string(i) + " material_index out of range");
+    bool has_motion = false;
+    if (motion)
+        for (size_t i = 0; i < (size_t)n_spheres * 4 && !has_motion; ++i)
+            has_motion = (i % 4 != 3) && motion[i] != 0.0f;
+    if (has_motion && !s->book2)
+        return fail(RRT_E_INVALID, fn + "a non-zero motion row needs a scene created as a book-2 world (the kernel "
+                                        "class is fixed at creation)");
+    if (has_motion && !(s->base.flags & RRT_FLAG_RAY_TIME))
+        return fail(RRT_E_INVALID, fn + "moving spheres need RRT_FLAG_RAY_TIME (rays carry the camera's time draw)");
+
+    // ---- device work, on the default stream after `stream` has drained. The first update's
+    // allocations fail without touching the scene; a failure after them leaves it invalid (broke).
+    HIP_TRY(hipSetDevice(s->device), "hipSetDevice");
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream), "hipStreamSynchronize");
+    rrt::KParams &p = s->base;
+    const uint32_t n_prims = p.n_prims;
+    const uint64_t allocs_before = s->builder->allocations();
+    uint64_t own_allocs = 0;
+    if (!s->d_src_spheres) {  // the first update: staging, the node buffer at capacity, the builder's reserve
+        ++own_allocs;
+        HIP_TRY(hipMalloc((void **)&s->d_src_spheres, std::max<size_t>(n_spheres, 1) * sizeof(RrtSphere)), "hipMalloc spheres");
+    }
+    if (s->book2 && !s->d_src_motion) {
+        ++own_allocs;
+        HIP_TRY(hipMalloc((void **)&s->d_src_motion, std::max<size_t>(n_spheres, 1) * 4 * sizeof(float)), "hipMalloc motion");
+    }
+    if (!s->nodes_cap) {
+        const size_t cap = (size_t)(n_prims - 1u) * sizeof(rrt::GNode);  // a binary tree's internal nodes, 80-B form
+        uint8_t *d = nullptr;
+        ++own_allocs;
+        HIP_TRY(hipMalloc((void **)&d, cap), "hipMalloc nodes");
+        const hipError_t e = hipMemcpy(d, s->d_nodes, (size_t)s->info.node_bytes, hipMemcpyDeviceToDevice);
+        if (e != hipSuccess) {
+            (void)hipFree(d);
+            return fail(RRT_E_HIP, std::string("copy nodes failed: ") + hipGetErrorString(e));
+        }
+        (void)hipFree(s->d_nodes);
+        s->d_nodes = d;
+        p.nodes = d;
+        s->nodes_cap = cap;
+        if (s->builder->reserve() != hipSuccess) return fail(RRT_E_NOMEM, fn + "reserving the builder's workspace failed");
+    }
+    auto broke = [&](int code, const std::string &msg) {
+        s->failed_update = msg;
+        return fail(code, fn + msg);
+    };
+    if (n_spheres && hipMemcpy(s->d_src_spheres, spheres, (size_t)n_spheres * sizeof(RrtSphere), hipMemcpyHostToDevice) != hipSuccess)
+        return broke(RRT_E_HIP, "copying the spheres failed");
+    if (has_motion && hipMemcpy(s->d_src_motion, motion, (size_t)n_spheres * 4 * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
+        return broke(RRT_E_HIP, "copying the motion rows failed");
+    const float *d_motion = has_motion ? s->d_src_motion : nullptr;
+    if (rrt::launch_sphere_boxes(n_spheres, s->d_src_spheres, d_motion, s->builder->device_boxes()) != hipSuccess)
+        return broke(RRT_E_HIP, "the sphere-box launch failed");
+    bvhb::Summary sum{};
+    uint32_t stride = 0, leaf_param = s->max_leaf, levels = 0;
+    if (int rc = bvh_device_shape(*s->builder, n_prims, s->max_leaf, s->book2, s->f64, sum, stride, leaf_param, levels))
+        return broke(rc, g_err);
+    const FlatBvh fb = flat_of_summary(sum, stride, BinnedInput{});
+    if (int rc = tree_limits(fb, s->f64)) return broke(rc, g_err);
+    const size_t node_bytes = (size_t)fb.n_nodes * fb.stride;
+    if (s->builder->emit_into(stride, s->d_nodes, s->nodes_cap, s->order.data()) != hipSuccess)
+        return broke(RRT_E_HIP, "device BVH: emit failed");
+    rrt::LeafTables t{};
+    t.n_prims = n_prims, t.n_spheres = n_spheres, t.book2 = s->book2 ? 1u : 0u, t.f64 = s->f64 ? 1u : 0u;
+    t.order = s->builder->device_order();
+    t.spheres = s->d_src_spheres;
+    t.motion = d_motion;
+    t.mats = s->d_src_mats;
+    t.mat_diel = s->d_src_diel;
+    t.quad_rows = s->d_quad_rows;
+    t.quad_mat = s->d_quad_mat;
+    t.prim_cr = s->d_prim_cr;
+    t.prim_mtl = s->d_prim_mtl;
+    t.prim_motion = s->d_prim_motion;
+    t.prim_inv_r64 = s->d_prim_inv_r64;
+    t.prim_diel64 = s->d_prim_diel64;
+    if (rrt::launch_leaf_tables(t) != hipSuccess) return broke(RRT_E_HIP, "the leaf-table launch failed");
+    if (s->f64) {  // scene creation's range check over the prim_cr rows: (center, max(r, 0)) and the quads'
+        bool in = s->quads_in_sphere32;
+        for (uint32_t i = 0; i < n_spheres && in; ++i) {
+            const float *c = spheres[i].center_radius;
+            in = row_in_sphere32(c[0], c[1], c[2], std::max(c[3], 0.0f));
+        }
+        p.sphere32 = sphere32_flag(in);
+    }
+    tree_params(p, fb, node_bytes, s->book2);
+    if (int rc = plan_check(p)) return broke(rc, g_err);
+    bvh_info_tree(s->info, fb, node_bytes, leaf_param);
+    if (hipDeviceSynchronize() != hipSuccess) return broke(RRT_E_HIP, "hipDeviceSynchronize failed");
+    s->failed_update.clear();
+    s->n_updates++;
+    s->last_update_allocs = own_allocs + (s->builder->allocations() - allocs_before);
+    s->last_update_levels = levels;
     return RRT_OK;
 }
 
@@ -2137,6 +2385,50 @@ extern "C" void rrt_testing_f64_layout(int32_t layout) { rrt::set_f64_layout(lay
 
 // Test support (rrt_testing_lds_node_link): the link rule of the f32 kernel's LDS staging loop.
 extern "C" uint32_t rrt_testing_lds_node_link(uint32_t link) { return rrt::lds_node_link(link); }
+
+// Test support: the host compilation of rrt_sphere_box.h (the device's is k_sphere_boxes).
+extern "C" int32_t rrt_testing_sphere_boxes(const RrtSphere *spheres, uint32_t n_spheres, const float *motion, double *out) {
+    if (!out || (n_spheres && !spheres)) return fail(RRT_E_INVALID, "rrt_testing_sphere_boxes: null argument");
+    for (uint32_t i = 0; i < n_spheres; ++i) {
+        const bvhb::Box6 b = rrt::sphere_box(spheres[i].center_radius, motion ? motion + 4 * (size_t)i : nullptr);
+        for (int a = 0; a < 3; ++a) out[6 * (size_t)i + a] = b.mn[a], out[6 * (size_t)i + 3 + a] = b.mx[a];
+    }
+    return RRT_OK;
+}
+
+// Test support: one of the scene's device tables, copied back.
+extern "C" int32_t rrt_testing_scene_read_table(RrtScene *scene, uint32_t what, void *out, size_t cap, size_t *bytes_out) {
+    if (!scene || !bytes_out) return fail(RRT_E_INVALID, "rrt_testing_scene_read_table: null scene or bytes_out");
+    const size_t n = scene->base.n_prims;
+    const void *src = nullptr;
+    size_t bytes = 0;
+    switch (what) {
+    case RRT_TABLE_BOXES:
+        if (scene->builder) src = scene->builder->device_boxes(), bytes = n * sizeof(bvhb::Box6);
+        break;
+    case RRT_TABLE_PRIM_CR: src = scene->d_prim_cr, bytes = n * sizeof(float4); break;
+    case RRT_TABLE_PRIM_MTL: src = scene->d_prim_mtl, bytes = n * sizeof(rrt::GMaterial); break;
+    case RRT_TABLE_PRIM_MOTION: src = scene->d_prim_motion, bytes = n * sizeof(float4); break;
+    case RRT_TABLE_PRIM_INV_R64: src = scene->d_prim_inv_r64, bytes = n * sizeof(double); break;
+    case RRT_TABLE_PRIM_DIEL64: src = scene->d_prim_diel64, bytes = n * sizeof(double4); break;
+    default: return fail(RRT_E_INVALID, "rrt_testing_scene_read_table: unknown table");
+    }
+    if (!src) bytes = 0;  // a table this scene does not hold
+    *bytes_out = bytes;
+    if (cap == 0 || bytes == 0) return RRT_OK;
+    if (!out || cap < bytes) return fail(RRT_E_INVALID, "rrt_testing_scene_read_table: buffer too small");
+    HIP_TRY(hipSetDevice(scene->device), "hipSetDevice");
+    HIP_TRY(hipMemcpy(out, src, bytes, hipMemcpyDeviceToHost), "copy table");
+    return RRT_OK;
+}
+
+extern "C" int32_t rrt_testing_scene_update_stats(const RrtScene *scene, RrtSceneUpdateStats *out) {
+    if (!scene || !out) return fail(RRT_E_INVALID, "rrt_testing_scene_update_stats: null scene or out");
+    out->updates = scene->n_updates;
+    out->last_allocations = scene->last_update_allocs;
+    out->last_levels = scene->last_update_levels;
+    return RRT_OK;
+}
 
 // Test support (rrt_testing_launch_plan): the launch plan of a scene given by its counts, through the
 // same rrt::plan_launch / perlin_fits_lds the launches and scene creation use; no device needed.

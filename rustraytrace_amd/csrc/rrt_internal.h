@@ -442,10 +442,44 @@ public:
     hipError_t build(uint32_t max_leaf, double node_cost, bvhb::Summary *out);
     hipError_t emit(uint32_t stride, uint8_t **d_nodes_out, uint32_t *order_out);
     uint32_t levels() const;  // of the last build: one blocking read each
+    // A builder kept by its scene (rrt_scene_update_spheres) is built again over new boxes without
+    // another upload: the caller rewrites device_boxes() in place (n_boxes rows, same primitives),
+    // build() starts from the uploaded order again, and emit_into() packs the nodes into a buffer the
+    // caller owns (cap_bytes >= n_nodes x stride, else hipErrorInvalidValue). reserve() sizes the
+    // per-level arrays for the widest level any tree of n_tree primitives can have (n_tree / 2
+    // tasks), after which build() allocates nothing. device_order(): the last build's leaf order on
+    // the device. allocations(): hipMalloc calls made by this builder so far.
+    bvhb::Box6 *device_boxes();
+    const uint32_t *device_order() const;
+    hipError_t reserve();
+    hipError_t emit_into(uint32_t stride, uint8_t *d_nodes, size_t cap_bytes, uint32_t *order_out);
+    uint64_t allocations() const;
 
 private:
     struct Impl;
     Impl *impl_;
 };
+
+// The scene-update kernels (rrt_scene_update.hip), on the default stream:
+//   launch_sphere_boxes  one lane per sphere: its padded f64 box (rrt_sphere_box.h) into boxes[i];
+//                        spheres = RrtSphere records, motion = n x 4 floats or null
+//   launch_leaf_tables   one lane per leaf position: the per-primitive tables scene creation forms
+struct LeafTables {
+    uint32_t n_prims, n_spheres, book2, f64;
+    const uint32_t *order;     // leaf position -> primitive (spheres, then quads as n_spheres + j)
+    const void *spheres;       // RrtSphere[n_spheres], source order
+    const float *motion;       // n_spheres x 4, or null (all zero)
+    const GMaterial *mats;     // the material table, source order
+    const double4 *mat_diel;   // f64: per material, a dielectric's constants (zeros otherwise)
+    const float4 *quad_rows;   // per quad: its prim_cr row, its prim_motion row
+    const uint32_t *quad_mat;  // per quad: its material index
+    float4 *prim_cr;
+    GMaterial *prim_mtl;
+    float4 *prim_motion;       // book2
+    double *prim_inv_r64;      // f64
+    double4 *prim_diel64;      // f64
+};
+hipError_t launch_sphere_boxes(uint32_t n, const void *d_spheres, const float *d_motion, void *d_boxes);
+hipError_t launch_leaf_tables(const LeafTables &t);
 
 }  // namespace rrt

@@ -1,0 +1,93 @@
+// rrt_scene_update.hip — the device side of rrt_scene_update_spheres: the spheres' padded boxes for
+// the builder (rrt_bvh_build.hip) and, after the build, the per-primitive tables in leaf order. Both
+// kernels restate what scene creation computes on the host (rrt_host.cpp prim_boxes and
+// prim_table_row) so that an updated scene holds the bytes of a freshly created one. One lane per
+// row, plain vector stores; nothing here is worth tuning (a 10^5-sphere scene moves ~10 MB).
+#include "rrt_internal.h"
+#include "rrt_sphere_box.h"
+#include "../../include/rrt_hip.h"
+
+namespace rrt {
+
+namespace {
+
+constexpr int kBlk = 256;
+static_assert(sizeof(RrtSphere) == 32, "RrtSphere is 32 B");
+
+__global__ __launch_bounds__(kBlk) void k_sphere_boxes(uint32_t n, const RrtSphere *spheres, const float *motion,
+                                                       bvhb::Box6 *boxes) {
+    const uint32_t i = blockIdx.x * kBlk + threadIdx.x;
+    if (i >= n) return;
+    const float4 cr4 = *reinterpret_cast<const float4 *>(spheres[i].center_radius);
+    const float cr[4] = {cr4.x, cr4.y, cr4.z, cr4.w};
+    if (motion) {
+        const float4 m4 = reinterpret_cast<const float4 *>(motion)[i];
+        const float m[3] = {m4.x, m4.y, m4.z};
+        boxes[i] = sphere_box(cr, m);
+    } else {
+        boxes[i] = sphere_box(cr, nullptr);
+    }
+}
+
+// 1 / r as scene creation's `1.0f / r` (the correctly rounded f32 quotient, +inf at r = 0): the f64
+// quotient rounded to f32. A 24-bit divisor's reciprocal is a power of two or at least 2^-48 (relative)
+// away from every f32 rounding boundary, which the f64 quotient's 2^-53 cannot bridge, so the two
+// roundings give the one; f64 division here is IEEE (no fast-math) and keeps f32's subnormal quotients.
+__device__ __forceinline__ float recip_f32(float r) { return (float)(1.0 / (double)r); }
+
+__global__ __launch_bounds__(kBlk) void k_leaf_tables(LeafTables t) {
+    const uint32_t i = blockIdx.x * kBlk + threadIdx.x;
+    if (i >= t.n_prims) return;
+    const uint32_t o = t.order[i];
+    float4 cr, mo = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    GMaterial mtl;
+    uint32_t mat;
+    if (o >= t.n_spheres) {  // a quad: its stored plane, (q, tag) and (normal, D)
+        const uint32_t j = o - t.n_spheres;
+        cr = t.quad_rows[2u * j];
+        mo = t.quad_rows[2u * j + 1u];
+        mat = t.quad_mat[j];
+        mtl = t.mats[mat];
+    } else {
+        const RrtSphere *sp = reinterpret_cast<const RrtSphere *>(t.spheres) + o;
+        const float4 c = *reinterpret_cast<const float4 *>(sp->center_radius);
+        const float r = c.w < 0.0f ? 0.0f : c.w;  // max(radius, 0)
+        mat = sp->material_index;
+        mtl = t.mats[mat];
+        if (t.book2 || t.f64) {
+            cr = make_float4(c.x, c.y, c.z, r);
+        } else {  // book-1 layout: r * r rounded once in f32, 1 / r in b.w
+            cr = make_float4(c.x, c.y, c.z, __fmul_rn(r, r));
+            mtl.b.w = __float_as_int(recip_f32(r));
+        }
+        if (t.motion) {
+            const float4 m = reinterpret_cast<const float4 *>(t.motion)[o];
+            mo = make_float4(m.x, m.y, m.z, 0.0f);
+        }
+        if (t.book2) mo.w = recip_f32(r);
+    }
+    t.prim_cr[i] = cr;
+    t.prim_mtl[i] = mtl;
+    if (t.book2) t.prim_motion[i] = mo;
+    if (t.f64) {
+        t.prim_inv_r64[i] = 1.0 / (double)cr.w;
+        t.prim_diel64[i] = mtl.b.x == (int)RRT_MAT_DIELECTRIC ? t.mat_diel[mat] : make_double4(0.0, 0.0, 0.0, 0.0);
+    }
+}
+
+}  // namespace
+
+hipError_t launch_sphere_boxes(uint32_t n, const void *d_spheres, const float *d_motion, void *d_boxes) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_sphere_boxes, dim3((n + kBlk - 1) / kBlk), dim3(kBlk), 0, 0, n,
+                       reinterpret_cast<const RrtSphere *>(d_spheres), d_motion, reinterpret_cast<bvhb::Box6 *>(d_boxes));
+    return hipGetLastError();
+}
+
+hipError_t launch_leaf_tables(const LeafTables &t) {
+    if (t.n_prims == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_leaf_tables, dim3((t.n_prims + kBlk - 1) / kBlk), dim3(kBlk), 0, 0, t);
+    return hipGetLastError();
+}
+
+}  // namespace rrt

@@ -9,6 +9,7 @@
 from __future__ import annotations
 
 import ctypes
+import dataclasses
 from typing import Optional
 
 import numpy as np
@@ -429,6 +430,45 @@ class DeviceScene:
         c = _lib.RrtCounters()
         _lib.check(self._lib.rrt_scene_count_work(self._h, ctypes.byref(tile), ctypes.byref(c)))
         return c.as_dict()
+
+    def set_camera(self, camera) -> None:
+        """rrt_scene_set_camera: replaces what scene creation derived from the camera (rays, seed,
+        max_depth, background, width / height, book 3's sqrt_spp); renders enqueued afterwards use it."""
+        cam = np.ascontiguousarray(camera, dtype=_lib.CAMERA_DTYPE).reshape(1)
+        _lib.check(self._lib.rrt_scene_set_camera(self._h, _lib.ptr(cam)))
+        self.scene = dataclasses.replace(self.scene, camera=cam.copy())
+
+    def update_spheres(self, spheres, motion=None, stream_ptr: int = 0) -> None:
+        """rrt_scene_update_spheres: replaces the spheres (and, for a book-2 world, their motion rows;
+        None = all zero) of a DeviceScene(device_bvh=True), rebuilds the BVH on the device and re-forms
+        the per-primitive tables; the scene then equals one freshly created from the new inputs. Waits
+        for the stream, returns synchronised."""
+        sp = np.ascontiguousarray(spheres, dtype=_lib.SPHERE_DTYPE)
+        m = None
+        if motion is not None:
+            m = np.ascontiguousarray(motion, dtype=np.float32)
+            assert m.shape == (len(sp), 4), "motion is (n_spheres, 4) float32"
+        _lib.check(self._lib.rrt_scene_update_spheres(self._h, _lib.ptr(sp), len(sp), _lib.ptr(m),
+                                                      ctypes.c_void_p(stream_ptr)))
+        self.scene = dataclasses.replace(self.scene, spheres=sp.copy(), motion=None if m is None else m.copy())
+
+    def read_table(self, name: str) -> np.ndarray:
+        """rrt_testing_scene_read_table (test support): one of the scene's device tables (a
+        _lib.SCENE_TABLES name) as a flat array; empty when the scene does not hold it."""
+        code, dtype = _lib.SCENE_TABLES[name]
+        n = ctypes.c_size_t(0)
+        _lib.check(self._lib.rrt_testing_scene_read_table(self._h, code, None, 0, ctypes.byref(n)))
+        out = np.zeros(n.value // dtype.itemsize, dtype=dtype)
+        if n.value:
+            _lib.check(self._lib.rrt_testing_scene_read_table(self._h, code, _lib.ptr(out), n.value, ctypes.byref(n)))
+        return out
+
+    def update_stats(self) -> dict:
+        """rrt_testing_scene_update_stats (test support): updates so far, and the device allocations
+        and builder levels of the last one."""
+        st = _lib.RrtSceneUpdateStats()
+        _lib.check(self._lib.rrt_testing_scene_update_stats(self._h, ctypes.byref(st)))
+        return {k: int(getattr(st, k)) for k, _ in st._fields_}
 
     def bvh_info(self) -> dict:
         b = _lib.RrtBvhInfo()
