@@ -723,7 +723,8 @@ int32_t rrt_testing_scene_update_stats(const RrtScene *scene, RrtSceneUpdateStat
  * image-textured; n_perlin, n_media, n_quads as in RrtSceneExt; f64: RRT_FLAG_F64; f64_book2:
  * RRT_FLAG_F64_BOOK2 (with f64 = 1 and book = 2: the f64 kernel's book-2 class, ok = 0 with n_perlin or
  * n_media; 0 leaves every other answer as it was); min_waves /
- * global_waves: 0 for the defaults (the RRT_MIN_WAVES / RRT_GLOBAL_WAVES overrides otherwise).
+ * global_waves: 0 for the defaults (the RRT_MIN_WAVES / RRT_GLOBAL_WAVES overrides otherwise). The
+ * RRT_PERLIN_IN_LDS=0 override of the environment is honoured as scene creation honours it.
  * Result: ok = 0 when rrt_scene_create refuses such a scene (no launch shape), else the kernel class
  * (f32: -2 diffuse, -1 untextured, 0 full book 1, 1-3 book 2 spheres / quads / media, 4 book 3; f64:
  * 0 full, 1 untextured, 2 diffuse, 3 book 2), its block (threads, launch-bounds waves per SIMD, 1 = none),

@@ -1514,6 +1514,15 @@ static uint32_t sphere32_flag(bool all_rows_in) {
     return on;
 }
 
+// Perlin tables in LDS when the block that launches (rrt::plan_launch) still fits 64 KB with them
+// (RRT_PERLIN_IN_LDS=0 leaves them in global memory). Scene creation and rrt_testing_launch_plan
+// both decide here.
+static uint32_t perlin_placement(const rrt::KParams &p) {
+    uint32_t in_lds = rrt::perlin_fits_lds(p) ? 1u : 0u;
+    if (const char *e = std::getenv("RRT_PERLIN_IN_LDS")) in_lds = in_lds && std::atoi(e) != 0;
+    return in_lds;
+}
+
 // What follows from the tree: its counts, where the scene is staged, the traversal thresholds and
 // where the Perlin tables go. Reads p.flags, p.n_quads, p.n_media, p.min_waves and p.global_waves.
 static void tree_params(rrt::KParams &p, const FlatBvh &fb, size_t node_bytes, bool book2) {
@@ -1538,9 +1547,7 @@ static void tree_params(rrt::KParams &p, const FlatBvh &fb, size_t node_bytes, b
     }
     if (const char *e = std::getenv("RRT_TRAV_FRAC")) p.trav_frac = (uint32_t)std::min(256, std::max(0, std::atoi(e)));
     if (const char *e = std::getenv("RRT_LEAF_FRAC")) p.leaf_frac = (uint32_t)std::min(256, std::max(0, std::atoi(e)));
-    // Perlin tables in LDS when the block that launches (rrt::plan_launch) still fits 64 KB with them
-    p.perlin_in_lds = rrt::perlin_fits_lds(p) ? 1u : 0u;
-    if (const char *e = std::getenv("RRT_PERLIN_IN_LDS")) p.perlin_in_lds = p.perlin_in_lds && std::atoi(e) != 0;
+    p.perlin_in_lds = perlin_placement(p);
 }
 // Every render of the scene launches rrt::plan_launch(p); a scene without a plan is refused.
 static int32_t plan_check(const rrt::KParams &p) {
@@ -2464,7 +2471,7 @@ extern "C" int32_t rrt_testing_launch_plan(const RrtLaunchPlanQuery *q, RrtLaunc
         (q->f64 && ((book2 && !f64_book2) || q->n_perlin || q->n_nodes > 65535u)) || (f64_book2 && q->n_media) ||
         (book2 && p.bvh_width != 2u))
         return RRT_OK;
-    p.perlin_in_lds = rrt::perlin_fits_lds(p) ? 1u : 0u;
+    p.perlin_in_lds = perlin_placement(p);
     const rrt::LaunchPlan pl = rrt::plan_launch(p);
     out->ok = pl.ok;
     if (!pl.ok) return RRT_OK;

@@ -1,7 +1,8 @@
 """GPU parity for book-2 breadth: moving spheres, checker and Perlin
 textures, quads (scenes 5-7: quads, simple_light, cornell_box with baked instanced boxes) through the C-ABI (rrt_hip_render_ex / rrt_scene_create_ex), bit-exact against the
 oracle's f32 twin (its own tree) and its KBVH mode (the kernel's tree), the same bar as book 1.
-The oracle's book-2 restatement is pinned in tests/test_book2.py."""
+The oracle's book-2 restatement is pinned in tests/test_book2.py.
+Every instantiation of the book-2/3 classes on composite scenes: tests/test_gpu_book2_classes.py."""
 import numpy as np
 import pytest
 
