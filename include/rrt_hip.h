@@ -388,8 +388,8 @@ typedef struct RrtBvhInfo {
     uint64_t prim_bytes;
     uint32_t width;          /* 2: binary nodes, 4: 128-B 4-wide nodes */
     uint32_t max_leaf_param; /* leaf size the builder was asked for */
-    uint32_t node_stride;    /* bytes per node: 80 (BVH2 staged in LDS: sign-ordered planes), 64 (BVH2 read
-                                from global memory), 128 (BVH4); layouts in DESIGN.md */
+    uint32_t node_stride;    /* bytes per node: 80 (BVH2 staged in LDS: sign-ordered planes), 32 (BVH2 read
+                                from global memory: GNodeH, f16 planes), 128 (BVH4); layouts in DESIGN.md */
     uint32_t n_unbounded;    /* the last n_unbounded primitives of the leaf order are not in the tree: media
                                 whose boundary sphere holds the whole scene, tested after the walk (ABI v6) */
 } RrtBvhInfo;
@@ -397,7 +397,7 @@ int32_t rrt_scene_bvh_info(const RrtScene *scene, RrtBvhInfo *out);
 
 /* Host-only: the BVH rrt_scene_create would build for these spheres (width / max_leaf 0 =
  * the defaults; max_leaf <= 7 for width 2, <= 15 for width 4), as the device node array (80-B or
- * 64-B BVH2 nodes — info->node_stride, the layout scene creation picks — or 128-B BVH4 nodes,
+ * 32-B BVH2 nodes — info->node_stride, the layout scene creation picks — or 128-B BVH4 nodes,
  * layouts in DESIGN.md) and the leaf-order permutation of the spheres.
  * Call with nodes_cap 0 to size (info->node_bytes). Lets a checker walk exactly the tree the
  * kernel walks. */
@@ -795,6 +795,13 @@ int32_t rrt_testing_sqrt64_check(uint64_t *out);
  *                                                 test_range's decision against `closest` with the IEEE division
  *                                                 (hit u32, t), the same with the per-ray reciprocal (hit, t); last
  *                                                 sphere_root over (0.001, inf) (u32). 13 words. r < 0 is taken as 0.
+ *   LIGHTS_PDF  o.xyz, d.xyz                      lights_pdf(P, o, d): book 3's HittableList::pdf_value over the light list
+ *   LIGHTS_RANDOM  o.xyz, seed, pixel, sample     lights_random(P, o, rng) 3, then the number of draws it took from the
+ *               (the last three as u32 bit        stream (u32). The lane seeds its stream as the render seeds the path
+ *               patterns)                         (seed, pixel, sample): the first draw is the path's first.
+ *                                                 aux of both: u32 count, 12 bytes of padding, then count RrtLight records
+ *                                                 (device records and the quads' derived planes formed by scene
+ *                                                 creation's code); 1 <= count <= 65536
  * div_by_a<true> / <false> (and with them exact_root<true> / <false> and test_range's two divisions)
  * are the same function since div_by_a guards its own range; both instantiations are still run.
  * Every input, NaN and infinities included, is ordinary arithmetic. */
@@ -811,7 +818,9 @@ enum RrtDeviceOp {
     RRT_OP_PERLIN = 9,
     RRT_OP_VEC = 10,
     RRT_OP_QUAD = 11,
-    RRT_OP_SPHERE = 12
+    RRT_OP_SPHERE = 12,
+    RRT_OP_LIGHTS_PDF = 13,
+    RRT_OP_LIGHTS_RANDOM = 14
 };
 int32_t rrt_testing_device_ops(uint32_t op, uint32_t n, const void *in, void *out, const void *aux);
 

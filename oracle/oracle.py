@@ -82,6 +82,8 @@ def load() -> ctypes.CDLL:
                        ("oracle_floor_i32", [c_uint32, P, P]), ("oracle_vec_f32", [c_uint32, P, P]),
                        ("oracle_quad_hit_f32", [c_uint32, P, c_uint32, P, P, P]),
                        ("oracle_sphere_hit_f32", [c_uint32, P, P, P]),
+                       ("oracle_lights_pdf_f32", [c_uint32, P, c_uint32, P, P]),
+                       ("oracle_lights_random_f32", [c_uint32, P, c_uint32, P, P]),
                        ("oracle_texel_index_f64", [c_uint32, P, P]), ("oracle_as_i32_f64", [c_uint32, P, P]),
                        ("oracle_texel_channels_f64", [P]), ("oracle_vec_f64", [c_uint32, P, P]),
                        ("oracle_sphere_hit_f64", [c_uint32, P, P, P])):
@@ -379,6 +381,29 @@ def sphere_hit_f32(rows):
     hit, t = np.zeros((len(r), 5), np.uint32), np.zeros((len(r), 4), np.float32)
     load().oracle_sphere_hit_f32(len(r), _p(r), _p(hit), _p(t))
     return hit, t
+
+
+def _lights(lights):
+    lt = np.ascontiguousarray(lights)
+    assert lt.dtype.itemsize == 64 and len(lt) > 0, "RrtLight records"
+    return lt
+
+
+def lights_pdf_f32(lights, rows):
+    """Rows (o, d) over RrtLight records -> the f32 twin's lights_pdf (HittableList::pdf_value)."""
+    lt, r = _lights(lights), _rows(rows, 6)
+    out = np.zeros(len(r), np.float32)
+    load().oracle_lights_pdf_f32(len(lt), _p(lt), len(r), _p(r), _p(out))
+    return out
+
+
+def lights_random_f32(lights, rows):
+    """Rows (o, seed, pixel, sample: the key as u32 bit patterns) over RrtLight records -> the f32 twin's
+    lights_random on the stream path_stream(seed, pixel, sample) names: (direction (n, 3), draws taken)."""
+    lt, r = _lights(lights), _rows(rows, 6)
+    out = np.zeros((len(r), 4), np.float32)
+    load().oracle_lights_random_f32(len(lt), _p(lt), len(r), _p(r), _p(out))
+    return out[:, :3].copy(), out[:, 3].copy().view(np.uint32)
 
 
 def _rows64(x, cols):

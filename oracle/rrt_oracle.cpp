@@ -1057,6 +1057,26 @@ std::vector<uint32_t> unbounded_media(const RrtSphere *s, uint32_t n, const RrtS
     return out;
 }
 
+// The light list as the render holds it (RrtLight -> LightT; a quad's area is |u x v| in f64, quad.rs:28).
+template <class T> void add_lights(World<T> &w, const RrtLight *lights, uint32_t nl) {
+    auto v3 = [](const float *p) { return mk<T>((T)p[0], (T)p[1], (T)p[2]); };
+    for (uint32_t l = 0; l < nl; ++l) {
+        const RrtLight &L = lights[l];
+        typename World<T>::LightT lt{};
+        lt.kind = L.kind;
+        lt.center = v3(L.a);
+        lt.radius = std::max((T)L.a[3], T(0));
+        if (L.kind == RRT_LIGHT_QUAD) {
+            RrtQuad rq{};
+            for (int i = 0; i < 3; ++i) rq.q[i] = L.a[i], rq.u[i] = L.u[i], rq.v[i] = L.v[i];
+            lt.quad = make_quad<T>(rq);
+            const Vec3<double> nv = cross(mk<double>(L.u[0], L.u[1], L.u[2]), mk<double>(L.v[0], L.v[1], L.v[2]));
+            lt.area = (T)length(nv);  // quad.rs:28
+        }
+        w.lights.push_back(lt);
+    }
+}
+
 template <class T>
 void load_world(World<T> &w, Cam<T> &cam, const RrtCamera *c, const RrtSphere *s, uint32_t n, const RrtMaterial *m,
                 uint32_t nm, const RrtTexture *tex, uint32_t ntex, uint32_t flags, const RrtSceneExt *ext,
@@ -1152,22 +1172,7 @@ void load_world(World<T> &w, Cam<T> &cam, const RrtCamera *c, const RrtSphere *s
             }
             w.perlin.push_back(pt);
         }
-    const uint32_t nl = ext && ext->lights ? ext->n_lights : 0u;
-    for (uint32_t l = 0; l < nl; ++l) {
-        const RrtLight &L = ext->lights[l];
-        typename World<T>::LightT lt{};
-        lt.kind = L.kind;
-        lt.center = v3(L.a);
-        lt.radius = std::max((T)L.a[3], T(0));
-        if (L.kind == RRT_LIGHT_QUAD) {
-            RrtQuad rq{};
-            for (int i = 0; i < 3; ++i) rq.q[i] = L.a[i], rq.u[i] = L.u[i], rq.v[i] = L.v[i];
-            lt.quad = make_quad<T>(rq);
-            const Vec3<double> nv = cross(mk<double>(L.u[0], L.u[1], L.u[2]), mk<double>(L.v[0], L.v[1], L.v[2]));
-            lt.area = (T)length(nv);  // quad.rs:28
-        }
-        w.lights.push_back(lt);
-    }
+    add_lights(w, ext ? ext->lights : nullptr, ext && ext->lights ? ext->n_lights : 0u);
     const uint32_t np = n + nq + nmd;
     std::vector<int32_t> objs;
     std::vector<bool> out_of_tree(np, false);
@@ -2158,6 +2163,41 @@ void oracle_sphere_hit_f32(uint32_t n, const float *in, uint32_t *hit, float *t_
         }
         T t;
         hit[5 * (size_t)i + 4] = World<T>::sphere_root(c, r, O, D, Interval<T>{T(0.001f), inf}, t) ? 1u : 0u;
+    }
+}
+
+// rows (o, d) -> lights_pdf over the RrtLight list (include/rrt_hip.h rrt_testing_device_ops LIGHTS_PDF)
+void oracle_lights_pdf_f32(uint32_t n_lights, const RrtLight *lights, uint32_t n, const float *in, float *out) {
+    using T = float;
+    World<T> w;
+    add_lights(w, lights, n_lights);
+    for (uint32_t i = 0; i < n; ++i) {
+        const float *x = in + 6 * (size_t)i;
+        out[i] = lights_pdf(w, mk(x[0], x[1], x[2]), mk(x[3], x[4], x[5]));
+    }
+}
+
+// rows (o, seed, pixel, sample: the last three u32 bit patterns) -> lights_random on the stream of path
+// (seed, pixel, sample) from its start (oracle_path_stream's draws): direction 3, draws taken (u32 bits)
+void oracle_lights_random_f32(uint32_t n_lights, const RrtLight *lights, uint32_t n, const float *in, float *out) {
+    using T = float;
+    World<T> w;
+    add_lights(w, lights, n_lights);
+    for (uint32_t i = 0; i < n; ++i) {
+        const float *x = in + 6 * (size_t)i;
+        uint32_t k[3];
+        std::memcpy(k, x + 3, sizeof(k));
+        const uint64_t key = splitmix64(((uint64_t)k[0] << 32) ^ (uint64_t)k[1]);
+        PathRng rng(splitmix64(key + k[2]), key), replay = rng;
+        const Vec3<T> d = lights_random(w, mk(x[0], x[1], x[2]), rng);
+        uint32_t draws = 0;
+        while (draws < 16u && !(replay.a == rng.a && replay.b == rng.b && replay.c == rng.c && replay.d == rng.d)) {
+            replay.next();
+            ++draws;
+        }
+        float *r = out + 4 * (size_t)i;
+        for (int c = 0; c < 3; ++c) r[c] = d[c];
+        std::memcpy(r + 3, &draws, sizeof(draws));
     }
 }
 

@@ -119,6 +119,7 @@ DEVICE_OPS = {
     "SIN": (0, 1, 1), "COS": (1, 1, 1), "LOG": (2, 1, 1), "ACOS": (3, 1, 1), "ATAN2": (4, 2, 1),
     "DIV_A": (5, 2, 4), "DIV_CONST": (6, 1, 4), "FLOOR_I32": (7, 1, 1), "CHECKER": (8, 4, 1),
     "PERLIN": (9, 3, 8), "VEC": (10, 9, 13), "QUAD": (11, 9, 2), "SPHERE": (12, 11, 13),
+    "LIGHTS_PDF": (13, 6, 1), "LIGHTS_RANDOM": (14, 6, 4),
 }
 
 # == RrtDeviceOp64 (include/rrt_hip.h, test support): op -> (code, f64 columns in, 64-bit words out)
@@ -256,11 +257,12 @@ def launch_plan(**query) -> dict:
     return out.as_dict()
 
 
-def device_ops(op: str, rows, quads=None, perlin=None, scale=0.0) -> np.ndarray:
+def device_ops(op: str, rows, quads=None, perlin=None, scale=0.0, lights=None) -> np.ndarray:
     """rrt_testing_device_ops (test support): the f32 kernel's building block `op` (a DEVICE_OPS
     name) on each row of `rows` (float32, n x columns in); returns the n x words-out results as
     uint32 (view as float32 where the op returns floats). quads: QUAD_DTYPE records for QUAD;
-    perlin: one PERLIN_DTYPE table and `scale` for PERLIN."""
+    perlin: one PERLIN_DTYPE table and `scale` for PERLIN; lights: LIGHT_DTYPE records for LIGHTS_PDF
+    and LIGHTS_RANDOM."""
     code, cin, cout = DEVICE_OPS[op]
     x = np.ascontiguousarray(rows, dtype=np.float32).reshape(-1, cin)
     out = np.zeros((len(x), cout), dtype=np.uint32)
@@ -270,6 +272,11 @@ def device_ops(op: str, rows, quads=None, perlin=None, scale=0.0) -> np.ndarray:
         aux = np.zeros(16 + q.nbytes, dtype=np.uint8)
         aux[:4] = np.frombuffer(np.uint32(len(q)).tobytes(), dtype=np.uint8)
         aux[16:] = np.frombuffer(q.tobytes(), dtype=np.uint8)
+    elif op in ("LIGHTS_PDF", "LIGHTS_RANDOM"):
+        lt = np.ascontiguousarray(lights, dtype=LIGHT_DTYPE)
+        aux = np.zeros(16 + lt.nbytes, dtype=np.uint8)
+        aux[:4] = np.frombuffer(np.uint32(len(lt)).tobytes(), dtype=np.uint8)
+        aux[16:] = np.frombuffer(lt.tobytes(), dtype=np.uint8)
     elif op == "PERLIN":
         t = np.ascontiguousarray(perlin, dtype=PERLIN_DTYPE).reshape(-1)[:1]
         aux = np.frombuffer(t.tobytes() + np.float32(scale).tobytes(), dtype=np.uint8).copy()

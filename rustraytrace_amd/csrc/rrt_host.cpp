@@ -1438,6 +1438,30 @@ static rrt::GQuad form_gquad(const RrtQuad &qd) {
     return g;
 }
 
+// The book-3 light list as device records: a sphere as it is (radius max(r, 0)), a quad as its area
+// |u x v| (quad.rs:28, f64 rounded) and the index first_quad + k of its k-th entry in `light_quads`,
+// which the caller appends to its GQuad array. Scene creation and rrt_testing_device_ops form their
+// records here.
+static std::vector<rrt::GLight> form_glights(const RrtLight *lights, uint32_t n_lights, uint32_t first_quad,
+                                             std::vector<RrtQuad> &light_quads) {
+    std::vector<rrt::GLight> glights(n_lights);
+    for (uint32_t l = 0; l < glights.size(); ++l) {
+        const RrtLight &L = lights[l];
+        rrt::GLight &g = glights[l];
+        g.kind = L.kind;
+        g.sphere = make_float4(L.a[0], L.a[1], L.a[2], std::max(L.a[3], 0.0f));
+        if (L.kind == RRT_LIGHT_QUAD) {
+            RrtQuad q{};
+            for (int i = 0; i < 3; ++i) q.q[i] = L.a[i], q.u[i] = L.u[i], q.v[i] = L.v[i];
+            g.quad = first_quad + (uint32_t)light_quads.size();
+            const D3 n = cross(d3(L.u[0], L.u[1], L.u[2]), d3(L.v[0], L.v[1], L.v[2]));
+            g.area = (float)std::sqrt(n.x * n.x + n.y * n.y + n.z * n.z);  // quad.rs:28 area = |n|
+            light_quads.push_back(q);
+        }
+    }
+    return glights;
+}
+
 // A Perlin table packed for the device (GPerlin); false when a permutation entry exceeds 255.
 static bool pack_perlin(const RrtPerlin &src, rrt::GPerlin &dst) {
     for (int i = 0; i < 256; ++i) {
@@ -1763,21 +1787,7 @@ static int32_t scene_create(const RrtCamera *cam, const RrtSphere *spheres, uint
     // Quads with their derived plane (form_gquad).
     // GQuad array: the scene's quads, media boundary quads, book-3 light quads
     std::vector<RrtQuad> light_quads;
-    std::vector<rrt::GLight> glights(book3 ? ex.n_lights : 0);
-    for (uint32_t l = 0; l < glights.size(); ++l) {
-        const RrtLight &L = ex.lights[l];
-        rrt::GLight &g = glights[l];
-        g.kind = L.kind;
-        g.sphere = make_float4(L.a[0], L.a[1], L.a[2], std::max(L.a[3], 0.0f));
-        if (L.kind == RRT_LIGHT_QUAD) {
-            RrtQuad q{};
-            for (int i = 0; i < 3; ++i) q.q[i] = L.a[i], q.u[i] = L.u[i], q.v[i] = L.v[i];
-            g.quad = n_quads + ex.n_bquads + (uint32_t)light_quads.size();
-            const D3 n = cross(d3(L.u[0], L.u[1], L.u[2]), d3(L.v[0], L.v[1], L.v[2]));
-            g.area = (float)std::sqrt(n.x * n.x + n.y * n.y + n.z * n.z);  // quad.rs:28 area = |n|
-            light_quads.push_back(q);
-        }
-    }
+    const std::vector<rrt::GLight> glights = form_glights(ex.lights, book3 ? ex.n_lights : 0, n_quads + ex.n_bquads, light_quads);
     std::vector<rrt::GQuad> gquads(n_quads + (size_t)ex.n_bquads + light_quads.size());
     for (uint32_t j = 0; j < gquads.size(); ++j) {
         const RrtQuad &qd = j < n_quads ? quads[j]
@@ -2537,7 +2547,7 @@ extern "C" int32_t rrt_testing_trig32_check(double *out) {
 }
 
 // Test support (rrt_testing_device_ops): rows in, rows out; the aux records are formed by the code
-// scene creation uses (form_gquad, pack_perlin).
+// scene creation uses (form_gquad, pack_perlin, form_glights).
 extern "C" int32_t rrt_testing_device_ops(uint32_t op, uint32_t n, const void *in, void *out, const void *aux) {
     uint32_t cin = 0, cout = 0;
     rrt::device_op_columns(op, cin, cout);
@@ -2573,6 +2583,23 @@ extern "C" int32_t rrt_testing_device_ops(uint32_t op, uint32_t n, const void *i
         for (uint32_t i = 0; i < n; ++i) {
             const float j = rows[(size_t)i * cin + 8];
             if (!(j >= 0.0f && j < (float)n_aux)) return fail(RRT_E_INVALID, "rrt_testing_device_ops: quad index out of range");
+        }
+    } else if (op == RRT_OP_LIGHTS_PDF || op == RRT_OP_LIGHTS_RANDOM) {
+        // aux: u32 count, then RrtLight records at byte 16 -> n_aux GLight, then their GQuad records
+        if (!aux) return fail(RRT_E_INVALID, "rrt_testing_device_ops: the light ops need a light list");
+        std::memcpy(&n_aux, aux, sizeof(uint32_t));
+        if (n_aux == 0 || n_aux > 65536u) return fail(RRT_E_INVALID, "rrt_testing_device_ops: light count");
+        std::vector<RrtLight> lights(n_aux);
+        std::memcpy(lights.data(), static_cast<const uint8_t *>(aux) + 16, (size_t)n_aux * sizeof(RrtLight));
+        for (const RrtLight &L : lights)
+            if (L.kind > RRT_LIGHT_SPHERE) return fail(RRT_E_INVALID, "rrt_testing_device_ops: unknown light kind");
+        std::vector<RrtQuad> light_quads;
+        const std::vector<rrt::GLight> glights = form_glights(lights.data(), n_aux, 0, light_quads);
+        aux_bytes.resize(glights.size() * sizeof(rrt::GLight) + light_quads.size() * sizeof(rrt::GQuad));
+        std::memcpy(aux_bytes.data(), glights.data(), glights.size() * sizeof(rrt::GLight));
+        for (size_t j = 0; j < light_quads.size(); ++j) {
+            const rrt::GQuad g = form_gquad(light_quads[j]);
+            std::memcpy(aux_bytes.data() + glights.size() * sizeof(rrt::GLight) + j * sizeof(g), &g, sizeof(g));
         }
     }
     int count = 0;

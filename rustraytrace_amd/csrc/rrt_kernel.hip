@@ -2172,7 +2172,8 @@ __global__ __launch_bounds__(256) void rrt_recip_check(unsigned long long *out) 
 // rows of `in`, results as 32-bit words in the rows of `out` (columns per op: include/rrt_hip.h
 // RrtDeviceOp, device_op_columns). The functions themselves, in this translation unit, with the
 // megakernel's flags. PERLIN: aux = one GPerlin table, staged into LDS for the LdsPerlin variants as
-// the render stages it; QUAD: aux = n_aux GQuad records.
+// the render stages it; QUAD: aux = n_aux GQuad records; LIGHTS_PDF, LIGHTS_RANDOM: aux = n_aux GLight
+// records followed by the GQuad records of the list's quads.
 __device__ __forceinline__ V3 ld3(const float *p) { return v3(p[0], p[1], p[2]); }
 __device__ __forceinline__ void st3(uint32_t *p, V3 v) {
     p[0] = __float_as_uint(v.x);
@@ -2206,6 +2207,12 @@ __global__ __launch_bounds__(256) void rrt_device_ops(uint32_t op, uint32_t n, u
         uint32_t *dst = reinterpret_cast<uint32_t *>(&lds_table);
         for (uint32_t k = threadIdx.x; k < sizeof(GPerlin) / 4u; k += 256u) dst[k] = src[k];
         __syncthreads();
+    }
+    KParams LP{};  // the light ops: n_aux GLight records, then the GQuad records their quads index
+    if (op == RRT_OP_LIGHTS_PDF || op == RRT_OP_LIGHTS_RANDOM) {
+        LP.lights = reinterpret_cast<const GLight *>(aux);
+        LP.quads = reinterpret_cast<const GQuad *>(LP.lights + n_aux);
+        LP.n_lights = n_aux;
     }
     for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n; i += gridDim.x * 256u) {
         const float *x = in + (size_t)i * cin;
@@ -2269,6 +2276,21 @@ __global__ __launch_bounds__(256) void rrt_device_ops(uint32_t op, uint32_t n, u
             sphere_ops<0>(make_float4(x[6], x[7], x[8], rad * rad), o, d, rk, x[10], r);  // book 1: r * r in w
             sphere_ops<1>(make_float4(x[6], x[7], x[8], rad), o, d, rk, x[10], r + 6);     // book 2: r
             r[12] = sphere_root(make_float4(x[6], x[7], x[8], rad), o, d, 0.001f) ? 1u : 0u;
+            break;
+        }
+        case RRT_OP_LIGHTS_PDF: r[0] = __float_as_uint(lights_pdf(LP, ld3(x), ld3(x + 3))); break;
+        case RRT_OP_LIGHTS_RANDOM: {
+            KParams Q = LP;  // the path key: pixel_key reads seed and y * width + x
+            Q.seed = __float_as_uint(x[3]);
+            RngState rng = path_rng(Q, __float_as_uint(x[4]), 0u, __float_as_uint(x[5]));
+            RngState replay = rng;
+            st3(r, lights_random(LP, ld3(x), rng));
+            uint32_t draws = 0;  // the stream position lights_random left, found by replaying the stream
+            while (draws < 16u && !(replay.a == rng.a && replay.b == rng.b && replay.c == rng.c && replay.d == rng.d)) {
+                rng_next(replay);
+                ++draws;
+            }
+            r[3] = draws;
             break;
         }
         default: break;
@@ -2337,6 +2359,8 @@ void device_op_columns(uint32_t op, uint32_t &cols_in, uint32_t &cols_out) {
     case RRT_OP_VEC: cols_in = 9, cols_out = 13; break;
     case RRT_OP_QUAD: cols_in = 9, cols_out = 2; break;
     case RRT_OP_SPHERE: cols_in = 11, cols_out = 13; break;
+    case RRT_OP_LIGHTS_PDF: cols_in = 6, cols_out = 1; break;
+    case RRT_OP_LIGHTS_RANDOM: cols_in = 6, cols_out = 4; break;
     default: cols_in = cols_out = 0; break;
     }
 }

@@ -405,3 +405,149 @@ def sphere_cases():
     closest = rng.choice([np.inf, 0.5, 1.0, 2.0], (4096, 1))
     out["random"] = np.concatenate([o, d, c, r, closest], axis=1)
     return {k: f32(v) for k, v in out.items()}
+
+
+# ---- book 3's light list: lights_pdf, lights_random -------------------------------------------------
+LIGHT_QUADS = (  # (q, u, v): exactly representable
+    ((343, 554, 332), (-130, 0, 0), (0, 0, -105)),  # 0: the stock scene's ceiling light, normal -y
+    ((60, 250, 420), (90, 0, 0), (0, 70, 0)),       # 1: upright, normal +z
+    ((1, 2, 3), (3, 4, 0), (0, 0, 5)),              # 2: rotated, 3-4-5 edge
+)
+# (centre, radius). 3: r^2 = 1.5 - 2^-23 in f32 and |oc|^2 = 1.5 from (-r, -2^-11.5, 0), so r^2 / d^2 is
+# the largest float below 1 (light_origins' just_outside); 4: the tangent rays of sphere_cases
+LIGHT_SPHERES = (((190, 90, 190), 90), ((0, 0, -4), 1), ((278, 500, 278), 0.05), ((0, 0, 0), float(F(np.sqrt(1.5)))),
+                 ((1, 0, -1), 1))
+LIGHT_LISTS = {  # n_lights -> entries ("q", index) / ("s", index); 1 / 3, 1 / 5 and 1 / 7 are inexact
+    1: (("s", 0),),
+    2: (("q", 0), ("s", 0)),
+    3: (("q", 1), ("s", 3), ("q", 0)),
+    5: (("q", 0), ("q", 1), ("s", 0), ("s", 1), ("s", 2)),
+    7: (("q", 0), ("s", 0), ("q", 1), ("s", 1), ("q", 2), ("s", 2), ("s", 4)),
+}
+# Path keys (seed, pixel, sample) whose first draw is 0xffffff * 2^-24, the largest value rnd returns:
+# found by evaluating the stream's first word over pixels 0 .. 2^22 of seeds 1, 2, ... (the CPU test
+# checks them against oracle.path_stream). random_int's index is then n - 1, never n.
+MAX_DRAW_KEYS = ((1, 1151665, 2), (2, 2552861, 1), (5, 3719686, 0), (5, 2071782, 1), (6, 1157237, 0), (6, 2444515, 3))
+
+
+def light_records(n):
+    from rustraytrace_amd import _lib
+
+    out = np.zeros(n, dtype=_lib.LIGHT_DTYPE)
+    for k, (kind, j) in enumerate(LIGHT_LISTS[n]):
+        if kind == "q":
+            out[k]["kind"] = 0
+            out[k]["a"][:3], out[k]["u"][:3], out[k]["v"][:3] = LIGHT_QUADS[j]
+        else:
+            out[k]["kind"] = 1
+            out[k]["a"] = [*LIGHT_SPHERES[j][0], LIGHT_SPHERES[j][1]]
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def light_origins(n):
+    """Origin classes for the list of n lights: dict class -> (k, 3) float32."""
+    rng = np.random.default_rng(0x11E7 + n)
+    out = {"general": rng.uniform(20.0, 535.0, (6, 3))}
+    plane, surface, inside, outside, far, centre = [], [], [], [], [], []
+    for kind, j in LIGHT_LISTS[n]:
+        if kind == "q":
+            q, u, v = (np.array(x, np.float64) for x in LIGHT_QUADS[j])
+            nrm = np.cross(u, v) / np.linalg.norm(np.cross(u, v))
+            for al, be in ((0.5, 0.5), (1.5, 0.25)):  # inside the quad's outline and beside it
+                p = q + al * u + be * v
+                plane += [p, p + 0.001 * nrm, p - 0.001 * nrm, p + 0.0005 * nrm, p - 0.002 * nrm]
+        else:
+            c, r = np.array(LIGHT_SPHERES[j][0], np.float64), float(LIGHT_SPHERES[j][1])
+            surface += [c + (r, 0, 0), c - (0, r, 0), c + (0, 0, r)]
+            inside += [c + (0.5 * r, 0, 0), c + (0.25 * r, -0.5 * r, 0.125 * r), c + (0, 0, -0.999 * r)]
+            outside += [c + (float(step(F(r), 1)), 0, 0), c - (r, 2.0 ** -11.5, 0), c + (0, 1.001 * r, 0)]
+            far += [c + (4096.5 * r, 0, 0), c + (3000 * r, -5000 * r, 100 * r), c - (0, 0, 1e6 * r)]
+            centre += [c]
+    for name, pts in (("quad_plane", plane), ("sphere_surface", surface), ("sphere_inside", inside),
+                      ("sphere_just_outside", outside), ("sphere_far", far), ("sphere_centre", centre)):
+        if pts:
+            out[name] = np.array(pts)
+    return {k: f32(v) for k, v in out.items()}
+
+
+def _light_dirs(n, o):
+    """Direction classes from the origin o (float64 (3,)) for the list of n lights."""
+    out = {k: [] for k in ("quad_interior", "quad_edges", "quad_corners", "quad_parallel", "sphere_centre",
+                           "sphere_tangent", "away", "special")}
+    for kind, j in LIGHT_LISTS[n]:
+        if kind == "q":
+            q, u, v = (np.array(x, np.float64) for x in LIGHT_QUADS[j])
+            nrm = np.cross(u, v) / np.linalg.norm(np.cross(u, v))
+            out["quad_interior"] += [q + 0.5 * u + 0.5 * v - o, q + 0.125 * u + 0.75 * v - o]
+            out["quad_edges"] += [q + 0.5 * u - o, q + u + 0.5 * v - o, q + 0.5 * v - o, q + 0.5 * u + v - o]
+            out["quad_corners"] += [q - o, q + u - o, q + v - o, q + u + v - o]
+            # |dot(normal, d)| at and around quad_hit's 1e-8 cut, both signs, and exactly parallel
+            uh = u / np.linalg.norm(u)
+            out["quad_parallel"] += [uh, v] + [uh + s * float(e) * nrm for e in around(F(1e-8), 1) for s in (1, -1)]
+            out["away"] += [o - (q + 0.5 * u + 0.5 * v)]
+        else:
+            c, r = np.array(LIGHT_SPHERES[j][0], np.float64), float(LIGHT_SPHERES[j][1])
+            oc = c - o
+            out["sphere_centre"] += [oc, 0.001 * oc]
+            d = np.linalg.norm(oc)
+            if d > r:  # the tangent cone's edge, just inside and just outside it
+                w = oc / d
+                a = np.cross(w, (0.0, 1.0, 0.0) if abs(w[0]) > 0.9 else (1.0, 0.0, 0.0))
+                a /= np.linalg.norm(a)
+                sin_t = r / d
+                for k in (1.0 - 1e-6, 1.0, 1.0 + 1e-6):
+                    out["sphere_tangent"] += [np.sqrt(max(1.0 - (sin_t * k) ** 2, 0.0)) * w + sin_t * k * a]
+            out["away"] += [-oc]
+    out["special"] = [(0, 0, 0), (0, -0.0, 0), (np.inf, 0, 0), (0, -np.inf, 1), (np.nan, 1, 0), (1, 1, np.nan),
+                      (DENORM_MIN, 0, 0), (1e-30, 1e-30, -1e-30), (1e30, -1e30, 1e30)]
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def lights_pdf_cases(n):
+    """Rows (o, d) for the list of n lights: dict "<origin class>/<direction class>" -> rows."""
+    out = {}
+    for oname, os_ in light_origins(n).items():
+        for o in os_.astype(np.float64):
+            for dname, ds in _light_dirs(n, o).items():
+                out.setdefault(f"{oname}/{dname}", []).extend([*o, *d] for d in ds)
+    # disc = 0 exactly and one step either side (sphere 4 from the origin, straight down -z: sphere_cases)
+    if ("s", 4) in LIGHT_LISTS[n]:
+        out["tangent_exact/disc"] = [[x, 0, 0, 0, 0, -1] for x in (0.0, -(2.0 ** -23), 2.0 ** -24, 2.0 ** -12)]
+    return {k: f32(v) for k, v in out.items() if len(v)}
+
+
+@functools.lru_cache(maxsize=None)
+def light_keys(n):
+    """Path keys (seed, pixel, sample) for the list of n lights: 8 per index value, from the stream's first
+    draw as the kernel turns it into an index (float32 u * n, truncated), then MAX_DRAW_KEYS."""
+    from oracle import oracle
+
+    per = {k: [] for k in range(n)}
+    pixel = 0
+    while any(len(v) < 8 for v in per.values()):
+        key = (0xB3, pixel, pixel % 4)
+        u = F(oracle.path_stream(*key, 1)[0] >> 8) * F(2.0 ** -24)
+        idx = int(u * F(n) + F(0))
+        if len(per[idx]) < 8:
+            per[idx].append(key)
+        pixel += 1
+    return per, MAX_DRAW_KEYS
+
+
+@functools.lru_cache(maxsize=None)
+def lights_random_cases(n):
+    """Rows (o, seed, pixel, sample as u32 bit patterns): every origin of light_origins(n) with one key per
+    index value (cycling through the 8) and every MAX_DRAW_KEYS key from the first origin of each class."""
+    per, top = light_keys(n)
+    out, turn = {}, 0
+    for oname, os_ in light_origins(n).items():
+        rows_ = []
+        for i, o in enumerate(os_):
+            keys = [per[k][(turn + i) % 8] for k in range(n)] + (list(top) if i == 0 else [])
+            for key in keys:
+                rows_.append(np.concatenate([o, np.array(key, np.uint32).view(F)]))
+        turn += 1
+        out[oname] = f32(rows_)
+    return out

@@ -226,3 +226,124 @@ def test_twins_are_accurate_on_the_full_sets():
     yx = C.atan2_cases()["unit_circle"]
     yx64 = yx.astype(np.float64)
     assert np.abs(oracle.atan2_f32(yx) - np.arctan2(yx64[:, 0], yx64[:, 1])).max() < 4e-7
+
+
+# ---- book 3's light list ----------------------------------------------------------------------------
+def _ratio(n, sphere, o):
+    """r * r / dot(oc, oc) in float32, as lights_pdf and lights_random form it."""
+    c, r = C.LIGHT_SPHERES[sphere]
+    oc = C.f32(c) - C.f32(o)
+    d2 = F(F(oc[0] * oc[0]) + F(oc[1] * oc[1])) + F(oc[2] * oc[2])
+    with np.errstate(divide="ignore"):
+        return F(F(r) * F(r)) / F(d2)
+
+
+def test_light_lists_and_origin_classes():
+    assert sorted(C.LIGHT_LISTS) == [1, 2, 3, 5, 7]
+    for n in C.LIGHT_LISTS:
+        lt = C.light_records(n)
+        assert len(lt) == n and set(lt["kind"]) <= {0, 1}
+        if n > 2:
+            assert float(F(1) / F(n)) != 1.0 / n  # the weight is inexact
+        org = C.light_origins(n)
+        assert {"general", "sphere_surface", "sphere_inside", "sphere_just_outside", "sphere_far", "sphere_centre"} <= set(org)
+        assert ("quad_plane" in org) == (n > 1)
+        spheres = [j for kind, j in C.LIGHT_LISTS[n] if kind == "s"]
+        for k, j in enumerate(spheres):
+            on = [_ratio(n, j, o) for o in org["sphere_surface"][3 * k:3 * k + 3]]
+            # dist == r exactly, cos_max = 0 (the tiny sphere's origins round: on either side of its surface)
+            assert all(r == 1 for r in on) if j != 2 else all(abs(float(r) - 1) < 1e-3 for r in on)
+            assert all(_ratio(n, j, o) > 1 for o in org["sphere_inside"][3 * k:3 * k + 3])  # sqrt of a negative
+            out3 = [_ratio(n, j, o) for o in org["sphere_just_outside"][3 * k:3 * k + 3]]
+            # the origin's own rounding moves the tiny sphere's ratios either way; one at least is just below 1
+            assert all(0.99 < r < 1.01 for r in out3) and any(r < 1 for r in out3)
+            far3 = [_ratio(n, j, o) for o in org["sphere_far"][3 * k:3 * k + 3]]
+            assert far3[0] < F(2.0 ** -23) and far3[1] < F(2.0 ** -25) and far3[2] < F(2.0 ** -25)  # 1 - x == 1
+            assert _ratio(n, j, org["sphere_centre"][k]) == np.inf
+        for a, b in zip(org.get("quad_plane", [])[0::5], org.get("quad_plane", [])[1::5]):
+            assert 0.0005 < np.abs(a - b).max() <= 0.00101  # on the plane and within 0.001 of it
+    # the largest ratio below 1: sphere 3 from (-r, -2^-11.5, 0)
+    o = [x for x in C.light_origins(3)["sphere_just_outside"] if x[1] != 0 and x[0] < 0][0]
+    assert _ratio(3, 3, o) == F(1) - F(2.0 ** -24)
+
+
+def test_light_pdf_direction_classes_on_the_twin():
+    total = 0
+    for n in C.LIGHT_LISTS:
+        lt, cases = C.light_records(n), C.lights_pdf_cases(n)
+        names = {k.split("/")[1] for k in cases}
+        assert {"sphere_centre", "sphere_tangent", "away", "special"} <= names
+        assert ({"quad_interior", "quad_edges", "quad_corners", "quad_parallel"} <= names) == (n > 1)
+        rows = C.rows(cases)
+        total += len(rows)
+        pdf = oracle.lights_pdf_f32(lt, rows)
+        # every outcome occurs: a miss, a finite density, 1 / 0 from a far sphere, NaN from inside one
+        assert (pdf == 0).any() and (np.isfinite(pdf) & (pdf > 0)).any() and np.isposinf(pdf).any() and np.isnan(pdf).any()
+        assert np.isnan(rows[:, 3:]).any() and np.isinf(rows[:, 3:]).any() and (rows[:, 3:] == 0).all(axis=1).any()
+        with np.errstate(invalid="ignore"):
+            assert not (pdf < 0).any()
+        inside = oracle.lights_pdf_f32(lt, cases["sphere_inside/sphere_centre"])
+        assert np.isnan(inside).mean() > 0.5  # all but where the exit lies within tmin of a long direction
+        far = oracle.lights_pdf_f32(lt, cases["sphere_far/sphere_centre"])
+        assert np.isposinf(far).any()
+        if n > 1:  # around the parallel cut some rows hit and some miss; the interiors hit from general origins
+            par = oracle.lights_pdf_f32(lt, cases["general/quad_parallel"])
+            assert (par == 0).any()
+            assert not (oracle.lights_pdf_f32(lt, cases["general/quad_interior"]) == 0).any()
+    # disc = 0 hits and one step outside misses sphere 4; the ray down -z hits sphere 1 as well in every row
+    t = oracle.lights_pdf_f32(C.light_records(7), C.lights_pdf_cases(7)["tangent_exact/disc"])
+    assert 0 < t[1] < min(t[0], t[2])
+    print(f"LIGHTS_PDF: {total} rows")
+    assert 2000 < total < 20000
+
+
+def test_light_keys_reach_every_index_and_the_largest_draw():
+    total = 0
+    for n in C.LIGHT_LISTS:
+        per, top = C.light_keys(n)
+        lt = C.light_records(n)
+        for idx, keys in per.items():
+            assert len(keys) == 8
+            for key in keys:
+                u = F(oracle.path_stream(*key, 1)[0] >> 8) * F(2.0 ** -24)
+                assert int(u * F(n)) == idx
+        for key in top:
+            assert oracle.path_stream(*key, 1)[0] >> 8 == 0xFFFFFF
+            assert int(F(0xFFFFFF) * F(2.0 ** -24) * F(n)) == n - 1  # never n: the product rounds below n
+        rows = C.rows(C.lights_random_cases(n))
+        total += len(rows)
+        d, draws = oracle.lights_random_f32(lt, rows)
+        assert (draws == 3).all()  # the index, then two more, for a quad and for a sphere alike
+        # the direction identifies the light drawn: from a general origin, the sampled direction hits list
+        # entry idx alone among single-entry lists more often than not; here only that every entry's kind is met
+        assert np.isnan(d).any() and np.isfinite(d).all(axis=1).any()
+        # a far sphere: z = 1, the direction is the axis to the centre, of unit length
+        far = C.lights_random_cases(n)["sphere_far"]
+        fd, _ = oracle.lights_random_f32(lt, far)
+        unit = np.abs(np.linalg.norm(fd.astype(np.float64), axis=1) - 1) < 1e-6
+        assert unit.any()
+    print(f"LIGHTS_RANDOM: {total} rows")
+    assert 500 < total < 5000
+
+
+def test_light_twins_against_float64():
+    """lights_pdf's twin against the closed forms in float64 at well-conditioned rows: a lone sphere seen
+    from outside, 1 / (2 pi (1 - cos_max)); a quad, dist^2 / (cosine area); weights 1 / n."""
+    lt = C.light_records(1)
+    (c, r), rng = C.LIGHT_SPHERES[0], np.random.default_rng(7)
+    o = np.array(c) + rng.normal(size=(64, 3)) * 400
+    o = o[np.linalg.norm(o - c, axis=1) > 2 * r]
+    rows = np.concatenate([o, np.array(c) - o], axis=1)
+    want = 1 / (2 * np.pi * (1 - np.sqrt(1 - r * r / ((o - c) ** 2).sum(axis=1))))
+    got = oracle.lights_pdf_f32(lt, rows).astype(np.float64)
+    assert np.abs(got / want - 1).max() < 1e-4
+    lt2 = C.light_records(2)
+    q, u, v = (np.array(x, np.float64) for x in C.LIGHT_QUADS[0])
+    o = np.array([[278.0, 100.0, 278.0], [100.0, 300.0, 400.0]])
+    tgt = q + 0.5 * u + 0.5 * v
+    d = tgt - o
+    dist2 = (d * d).sum(axis=1)
+    cosine = np.abs(d[:, 1]) / np.sqrt(dist2)
+    want = 0.5 * dist2 / (cosine * 130 * 105)
+    got = oracle.lights_pdf_f32(lt2, np.concatenate([o, d], axis=1)).astype(np.float64)
+    assert np.abs(got / want - 1).max() < 1e-5  # the sphere of list 2 is not on these rays

@@ -172,3 +172,22 @@ def test_div_check():
     # sends them to the IEEE division), so this counter is pinned too
     assert out[3] == 0, "div_by_a differs from n / a on a subnormal or zero quotient"
     assert out[4] == 0 and out[5] == 0, "div_by_const differs from x / c on its proved domain"
+
+
+@pytest.mark.parametrize("n", sorted(C.LIGHT_LISTS))
+def test_lights_pdf(n):
+    """lights_pdf over a list of n lights (1 / n inexact for 3, 5, 7): origins on, inside, just outside and
+    far from the light spheres and on the quads' planes; directions through the quads' interiors, edges and
+    corners, parallel to them, tangent to the spheres, away, and with zero, infinite and NaN components."""
+    rows, lights = C.rows(C.lights_pdf_cases(n)), C.light_records(n)
+    assert_same(f"LIGHTS_PDF n={n}", _lib.device_ops("LIGHTS_PDF", rows, lights=lights), oracle.lights_pdf_f32(lights, rows), rows)
+
+
+@pytest.mark.parametrize("n", sorted(C.LIGHT_LISTS))
+def test_lights_random(n):
+    """lights_random from the start of a path's stream: keys that draw every index of the list, and keys
+    whose first draw is the largest rnd returns. Direction and the number of draws taken."""
+    rows, lights = C.rows(C.lights_random_cases(n)), C.light_records(n)
+    d, draws = oracle.lights_random_f32(lights, rows)
+    out = _lib.device_ops("LIGHTS_RANDOM", rows, lights=lights)
+    assert_same(f"LIGHTS_RANDOM n={n}", out, np.concatenate([u32(d), draws[:, None]], axis=1), rows)
