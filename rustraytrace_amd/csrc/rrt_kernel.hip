@@ -377,11 +377,22 @@ __device__ __forceinline__ RayK ray_consts(V3 o, V3 d) {
 __device__ __forceinline__ float div_by_a(float n, const RayK &rk) {
     const float q0 = n * rk.ra;
     const float m = __builtin_fabsf(q0);
-    if (!(m >= 0x1.0p-30f && m < __builtin_inff())) return n / rk.a;
+    const bool outside = !(m >= 0x1.0p-30f && m < __builtin_inff());
     const float e0 = __builtin_fmaf(-rk.a, q0, n);
     const float q1 = __builtin_fmaf(e0, rk.ra, q0);
     const float e1 = __builtin_fmaf(-rk.a, q1, n);
-    return __builtin_fmaf(e1, rk.ra, q1);
+    float q = __builtin_fmaf(e1, rk.ra, q1);
+    // The range check is one ballot over the active lanes and a scalar branch (as in sqrt_rn): the
+    // four fmas run straight-line, and only a wave that holds a lane outside the range enters the
+    // per-lane IEEE division, which replaces that lane's quotient. (The empty asm keeps the arm
+    // behind its branch: a plain division is cheap enough for the compiler to run it in every wave
+    // and select.)
+    if (__ballot(outside) != 0) {
+        float nn = n;
+        asm volatile("" : "+v"(nn));
+        if (outside) q = nn / rk.a;
+    }
+    return q;
 }
 
 // Sphere centers as the sphere test sees them: static, or (book-2 scenes) a moving sphere's
@@ -589,6 +600,50 @@ __device__ __forceinline__ float exact_root(const PR &prim_cr, int i, V3 o, V3 d
     if (!(0.001f < root)) root = div_by_a(h + sq, rk);
     return root;
 }
+// One primitive of a leaf range against the ray: a sphere's root (or, book 2, a quad's or a medium's
+// t) replaces `closest` when it lies in (0.001, closest), and its index `i` replaces `hit_prim`. The
+// accept is two selects on one lane mask, not a divergent region: the strict `<` keeps the earlier
+// primitive of two with equal roots.
+template <class PR>
+__device__ __forceinline__ void test_prim(const PR &prim_cr, float4 cr, float4 m, int i, V3 o, V3 d,
+                                          const RayK &rk, float &closest, int &hit_prim, Counters &cnt) {
+    if constexpr (PR::kHasQuads) {
+        if (cr.w < 0.0f) {
+            const int j = (int)(-cr.w) - 1;
+            float tq;
+            bool h;
+            if (PR::kHasMedia && j >= (int)prim_cr.n_quads) h = medium_hit(prim_cr, j - (int)prim_cr.n_quads, o, d, rk, closest, tq);
+            else h = quad_hit_leaf(prim_cr.qd + j, cr, m, o, d, closest, tq);
+            if (h) {
+                closest = tq;
+                hit_prim = i;
+            }
+            return;
+        }
+    }
+    if constexpr (!PR::kR2) {  // Prims::at
+        cr.x = cr.x + prim_cr.time * m.x;
+        cr.y = cr.y + prim_cr.time * m.y;
+        cr.z = cr.z + prim_cr.time * m.z;
+    }
+    const V3 oc = v3(cr.x - o.x, cr.y - o.y, cr.z - o.z);
+    const float h = dot(d, oc);
+    const float c = dot(oc, oc) - (PR::kR2 ? cr.w : cr.w * cr.w);
+    const float disc = __builtin_fmaf(h, h, -(rk.a * c));
+    // The far root (h + sq) / a is needed only when the near one is at or behind tmin (the
+    // ray starts inside the sphere): r1 >= r0 always (sq >= 0, a > 0, correctly rounded
+    // quotients are monotone), so r0 >= closest rejects both. A wave skips that rare branch
+    // when no lane takes it.
+    if (disc < 0.0f) return;
+    if constexpr (RRT_PHASE_TIMING == 3) cnt.d2 += 1;
+    const float sq = sqrt_rn(disc);
+    float root = div_by_a(h - sq, rk);
+    if (!(0.001f < root)) root = div_by_a(h + sq, rk);
+    const bool accept = 0.001f < root && root < closest;
+    closest = accept ? root : closest;
+    hit_prim = accept ? i : hit_prim;
+}
+
 // Leaf primitives [first, first + count): the hit leaf children of one node visit, which are
 // adjacent in primitive order (sibling leaves split one range, rrt_host.cpp flatten2).
 // `skip` is the primitive the ray is leaving (exit_skip): it can never be accepted, so it is left
@@ -598,57 +653,20 @@ __device__ __forceinline__ float exact_root(const PR &prim_cr, int i, V3 o, V3 d
 template <bool kCount, class PR>
 __device__ __forceinline__ void test_range(const PR &prim_cr, int first, int count, V3 o, V3 d, const RayK &rk,
                                            int skip, float &closest, int &hit_prim, Counters &cnt) {
-    const float a = rk.a;
+    if (kCount) cnt.spheres += (uint32_t)count;  // every primitive of the range, the skipped one too
     const bool trim = (uint32_t)(skip - first) < (uint32_t)count;
     const int n = count - (trim ? 1 : 0);
     const int gap = trim ? skip : 0x7fffffff;
-    if (kCount && trim) cnt.spheres++;
     for (int k = 0; k < n; ++k) {
         const int i = first + k + (first + k >= gap ? 1 : 0);
-        if (kCount) cnt.spheres++;
         if constexpr (RRT_PHASE_TIMING == 3) {
             cnt.d0 += wave_slot();
             cnt.d1 += 1;
         }
-        float4 cr;
-        if constexpr (PR::kHasQuads) {
-            cr = prim_cr.cr[i];
-            const float4 m = prim_cr.mo[i];
-            if (cr.w < 0.0f) {
-                const int j = (int)(-cr.w) - 1;
-                float tq;
-                bool hit;
-                if (PR::kHasMedia && j >= (int)prim_cr.n_quads) hit = medium_hit(prim_cr, j - (int)prim_cr.n_quads, o, d, rk, closest, tq);
-                else hit = quad_hit_leaf(prim_cr.qd + j, cr, m, o, d, closest, tq);
-                if (hit) {
-                    closest = tq;
-                    hit_prim = i;
-                }
-                continue;
-            }
-            cr.x = cr.x + prim_cr.time * m.x;  // Prims::at
-            cr.y = cr.y + prim_cr.time * m.y;
-            cr.z = cr.z + prim_cr.time * m.z;
-        } else {
-            cr = prim_cr.at(i);
-        }
-        const V3 oc = v3(cr.x - o.x, cr.y - o.y, cr.z - o.z);
-        const float h = dot(d, oc);
-        const float c = dot(oc, oc) - (PR::kR2 ? cr.w : cr.w * cr.w);
-        const float disc = __builtin_fmaf(h, h, -(a * c));
-        // The far root (h + sq) / a is needed only when the near one is at or behind tmin (the
-        // ray starts inside the sphere): r1 >= r0 always (sq >= 0, a > 0, correctly rounded
-        // quotients are monotone), so r0 >= closest rejects both. A wave skips that rare branch
-        // when no lane takes it.
-        if (disc < 0.0f) continue;
-        if constexpr (RRT_PHASE_TIMING == 3) cnt.d2 += 1;
-        const float sq = sqrt_rn(disc);
-        float root = div_by_a(h - sq, rk);
-        if (!(0.001f < root)) root = div_by_a(h + sq, rk);
-        if (0.001f < root && root < closest) {
-            closest = root;
-            hit_prim = i;
-        }
+        const float4 cr = prim_cr.cr[i];
+        float4 m = cr;
+        if constexpr (!PR::kR2) m = prim_cr.mo[i];
+        test_prim(prim_cr, cr, m, i, o, d, rk, closest, hit_prim, cnt);
     }
 }
 
@@ -1700,11 +1718,19 @@ __device__ __forceinline__ void render_body(const KParams &P) {
                 // pm = lanes waiting on leaf tests, tm = lanes still in the tree (pm is a subset)
                 const uint64_t pm = __ballot(lv != 0);
                 const uint64_t nm = __ballot(tr.node >= 0);
-                const uint64_t tm = nm | pm;
-                const bool leave = (uint32_t)__popcll(tm) <= min_active;
-                const bool batch = ((uint32_t)__popcll(pm) > leaf_min) | leave | (tm == pm);
+                // Lanes still in the tree are the waiting ones and the stepping ones (disjoint), so
+                // the three thresholds are sign bits of differences of the two popcounts — 32-bit
+                // scalar arithmetic, no 64-bit boolean masks: leave when waiting + stepping <=
+                // min_active; run the leaf batch when more than leaf_min lanes wait, or on leaving,
+                // or when no lane can step. (With no lane waiting the batch's body runs no lane.)
                 step = nm & ~pm;
-                if ((pm != 0) & batch) {
+                // (min_active and leaf_min are (live * fraction) >> 8 with live <= 64 and a fraction the
+                // host clamps to 256, so at most 64: the casts to int32_t below keep their values; a
+                // threshold of 2^31 or more, such as a sentinel, would flip these signs)
+                const int32_t waiting = __popcll(pm), stepping = __popcll(step);
+                const int32_t leave = waiting + stepping - (int32_t)min_active - 1;  // < 0: leave
+                const int32_t batch = ((int32_t)leaf_min - waiting) | leave | (stepping - 1);  // < 0: batch
+                if (batch < 0) {
                     __builtin_amdgcn_s_setprio(RRT_PRIO_LEAF);
                     if (__builtin_amdgcn_inverse_ballot_w64(pm)) {
                         trav_leaves<kCount, kHoldRa>(pr, lv, ps.o, ps.d, rk, ps.skip, tr, cnt);
@@ -1713,7 +1739,7 @@ __device__ __forceinline__ void render_body(const KParams &P) {
                     step = nm;  // the batch tests every pending range and leaves tr.node alone
                     __builtin_amdgcn_s_setprio(RRT_PRIO_NODE);
                 }
-                if (leave) break;
+                if (leave < 0) break;
             }
         }
         __builtin_amdgcn_s_setprio(RRT_PRIO_SHADE);
