@@ -440,8 +440,8 @@ int32_t rrt_scene_set_camera(RrtScene *scene, const RrtCamera *cam);
  * on the device and re-forms every per-primitive table there; the scene then holds, bit for bit,
  * what rrt_scene_create_ex would make of the new inputs (tree, leaf order, tables, every frame).
  * n_spheres must equal the scene's. Quads, materials, textures and Perlin tables are kept. Waits
- * for `stream`, then runs and returns synchronised. From the second update of a scene on, no device
- * memory is allocated or freed.
+ * for `stream` (and for a refit still in flight), then runs and returns synchronised. From the
+ * second update of a scene on, no device memory is allocated or freed.
  * Refused with RRT_E_INVALID, before any device call and with the scene untouched: null arguments
  * or another n_spheres; a material_index out of range; a scene not created with
  * RRT_FLAG_DEVICE_BVH; a scene with media; an RRT_FLAG_BOOK3 scene; a tree of fewer than 2
@@ -452,6 +452,49 @@ int32_t rrt_scene_set_camera(RrtScene *scene, const RrtCamera *cam);
  * later update succeeds. */
 int32_t rrt_scene_update_spheres(RrtScene *scene, const RrtSphere *spheres, uint32_t n_spheres,
                                  const float *motion, void *stream);
+
+/* Refit: the same replacement of the spheres (and motion rows) as rrt_scene_update_spheres, with the
+ * same arguments and the same refusals before any device call, but the tree keeps the topology and
+ * leaf order of the last build (scene creation or the last update): only its boxes are recomputed,
+ * bottom-up from the moved spheres, on the device. The result is, bit for bit, the tree of
+ * rrt_refit_bvh_binned and the per-primitive tables of a fresh scene in the kept leaf order; frames are
+ * correct for the new spheres (every stored box contains its primitives), and an RRT_FLAG_F64
+ * scene's are bit for bit a fresh scene's. RrtBvhInfo, depth and the launch plan cannot change.
+ * Everything is enqueued on `stream` (NULL: the default stream): the copy of the rows, the boxes, the
+ * refit, the node pack and the tables. The call returns without waiting for the device, the caller's
+ * arrays may be reused as soon as it returns, and a render enqueued on `stream` afterwards sees the
+ * refitted scene; work on another stream is the caller's to order. The first change of a scene
+ * allocates (and waits for `stream` if it has to replace the node array); later refits allocate and
+ * free nothing. Refits compose; a later rrt_scene_update_spheres rebuilds, after which the scene is
+ * again the freshly created one. A refitted tree renders more slowly the further the spheres have
+ * moved: rrt_scene_tree_cost tells when to rebuild. A HIP error after device work began leaves the
+ * scene invalid exactly as a failed update does. */
+int32_t rrt_scene_refit_spheres(RrtScene *scene, const RrtSphere *spheres, uint32_t n_spheres,
+                                const float *motion, void *stream);
+
+/* The SAH cost of the tree the scene holds now (sah), of the tree its last build made (sah_at_build)
+ * and the refits since. Over the builder's unrounded f64 boxes: node k's term is w0 A(box0) + w1
+ * A(box1), A the surface area, w a leaf child's primitive count or the kept shape's node price for a
+ * node child; the terms are summed for k = 0 .. n-1 in that order and divided by the root box's
+ * area, so the value is defined bit for bit (rrt_refit_bvh_binned's sah_out). Synchronises the
+ * scene's device; on demand, not for every frame. Needs a scene the device builder built. */
+typedef struct RrtTreeCost {
+    double sah;
+    double sah_at_build;
+    uint64_t refits_since_build;
+} RrtTreeCost;
+int32_t rrt_scene_tree_cost(RrtScene *scene, RrtTreeCost *out);
+
+/* Host-only: the specification the device refit is held to. Builds the tree of rrt_build_bvh_binned
+ * over the built_* inputs, recomputes its boxes over the new spheres and motion rows (NULL = all
+ * zero; quads and media keep their boxes), and writes the nodes with the new root box's slack. Same
+ * sizing protocol and refusals as rrt_build_bvh_binned; the leaf order and info are the built
+ * tree's. sah_out (may be NULL): the refitted tree's cost as rrt_scene_tree_cost defines it. */
+int32_t rrt_refit_bvh_binned(const RrtSphere *built_spheres, uint32_t n_spheres, const RrtSceneExt *built_ext,
+                             uint32_t max_leaf, double node_cost, uint32_t node_stride,
+                             const RrtSphere *new_spheres, const float *new_motion,
+                             void *nodes_out, size_t nodes_cap, uint32_t *prim_order_out,
+                             RrtBvhInfo *info, double *sah_out);
 
 /* ---- host-side callers of the boundary ------------------------------------------------ */
 
@@ -711,6 +754,22 @@ typedef struct RrtSceneUpdateStats {
 int32_t rrt_testing_sphere_boxes(const RrtSphere *spheres, uint32_t n_spheres, const float *motion, double *out);
 int32_t rrt_testing_scene_read_table(RrtScene *scene, uint32_t what, void *out, size_t cap, size_t *bytes_out);
 int32_t rrt_testing_scene_update_stats(const RrtScene *scene, RrtSceneUpdateStats *out);
+
+/* Test support, not part of the drop-in. rrt_testing_scene_refit_stats: the scene's refits so far,
+ * and of the last one the device allocations, the kernel launches and the form of the bottom-up
+ * pass (1: one workgroup looping over the levels, 0: one launch per level).
+ * rrt_testing_refit_form: forces the per-level launches (0) or the single workgroup (1) whatever the
+ * tree's size; -1 (the default at every load) restores the automatic choice. With the single
+ * workgroup forced, a refit of a tree over its node bound is refused. Both forms write the same
+ * bytes (tests/test_gpu_scene_refit.py). Process-wide. */
+typedef struct RrtSceneRefitStats {
+    uint64_t refits;
+    uint64_t last_allocations;
+    uint64_t last_launches;
+    uint64_t last_form;
+} RrtSceneRefitStats;
+int32_t rrt_testing_scene_refit_stats(const RrtScene *scene, RrtSceneRefitStats *out);
+int32_t rrt_testing_refit_form(int32_t form);
 
 /* Test support, not part of the drop-in (no reference counterpart; RRT_ABI_VERSION is unchanged and
  * the Rust shim does not bind it): the launch shape the library picks for a scene, computed on the

@@ -102,6 +102,11 @@ EXPORTED_SYMBOLS = (
     "rrt_testing_sphere_boxes",
     "rrt_testing_scene_read_table",
     "rrt_testing_scene_update_stats",
+    "rrt_scene_refit_spheres",
+    "rrt_scene_tree_cost",
+    "rrt_refit_bvh_binned",
+    "rrt_testing_scene_refit_stats",
+    "rrt_testing_refit_form",
 )
 
 # == RrtSceneTable (include/rrt_hip.h, test support): table -> (code, row dtype)
@@ -113,6 +118,20 @@ SCENE_TABLES = {
 
 class RrtSceneUpdateStats(ctypes.Structure):  # include/rrt_hip.h, test support
     _fields_ = [("updates", c_uint64), ("last_allocations", c_uint64), ("last_levels", c_uint64)]
+
+
+class RrtSceneRefitStats(ctypes.Structure):  # include/rrt_hip.h, test support
+    _fields_ = [("refits", c_uint64), ("last_allocations", c_uint64), ("last_launches", c_uint64), ("last_form", c_uint64)]
+
+
+class RrtTreeCost(ctypes.Structure):  # include/rrt_hip.h
+    _fields_ = [("sah", c_double), ("sah_at_build", c_double), ("refits_since_build", c_uint64)]
+
+
+def refit_form(form: int) -> None:
+    """rrt_testing_refit_form (test support): force the refit's per-level launches (0) or its single
+    workgroup (1); -1 restores the automatic choice."""
+    check(load().rrt_testing_refit_form(int(form)))
 
 # == RrtDeviceOp (include/rrt_hip.h, test support): op -> (code, f32 columns in, 32-bit words out)
 DEVICE_OPS = {
@@ -415,6 +434,11 @@ def load() -> ctypes.CDLL:
         "rrt_testing_sphere_boxes": (c_int32, [P, c_uint32, P, P]),
         "rrt_testing_scene_read_table": (c_int32, [P, c_uint32, P, c_size_t, P]),
         "rrt_testing_scene_update_stats": (c_int32, [P, P]),
+        "rrt_scene_refit_spheres": (c_int32, [P, P, c_uint32, P, P]),
+        "rrt_scene_tree_cost": (c_int32, [P, P]),
+        "rrt_refit_bvh_binned": (c_int32, [P, c_uint32, P, c_uint32, c_double, c_uint32, P, P, P, c_size_t, P, P, P]),
+        "rrt_testing_scene_refit_stats": (c_int32, [P, P]),
+        "rrt_testing_refit_form": (c_int32, [c_int32]),
     }
     experiment = "RRT_LIB_PATH" in os.environ  # A/B of older builds: tolerate symbols they lack
     for name, (res, args) in sig.items():

@@ -350,6 +350,69 @@ RRT_BB_HD void pack_node(const RawNode &r, const Slack &slack, uint32_t stride, 
     else pack_node32(lo, hi, r.link, w);
 }
 
+// ---- refit -------------------------------------------------------------------------------------
+// The boxes of a built tree recomputed bottom-up from moved primitives; links and leaf order stay.
+// A link of 0 is the never-hit slot of the root-leaf form (a node link is never 0: the root is no
+// child, and a leaf link has count > 0): its box is kept and it takes no part in a union. Unions are
+// the builder's: integer min / max of f64_key (-0 < +0), so a refit over the boxes the tree was built
+// from reproduces the builder's bytes, in any evaluation order.
+RRT_BB_HD bool link_is_leaf(uint32_t link) { return (link >> kLeafShift) != 0; }
+RRT_BB_HD void box6_merge_keys(uint64_t *k /* 6: mn xyz, mx xyz */, const double *mn, const double *mx) {
+    for (int a = 0; a < 3; ++a) {
+        const uint64_t lo = f64_key(mn[a]), hi = f64_key(mx[a]);
+        if (lo < k[a]) k[a] = lo;
+        if (hi > k[3 + a]) k[3 + a] = hi;
+    }
+}
+// Child c of node k from the level below (a node link's two child boxes) or from its primitives.
+RRT_BB_HD void refit_child(RawNode *raw, uint32_t k, int c, const uint32_t *order, const Box6 *boxes) {
+    const uint32_t link = raw[k].link[c];
+    if (link == 0u) return;
+    uint64_t key[6] = {kKeyPosInf, kKeyPosInf, kKeyPosInf, kKeyNegInf, kKeyNegInf, kKeyNegInf};
+    if (link_is_leaf(link)) {
+        const uint32_t first = link & ((1u << kLeafShift) - 1u), count = link >> kLeafShift;
+        for (uint32_t i = first; i < first + count; ++i) {
+            const Box6 &b = boxes[order[i]];
+            box6_merge_keys(key, b.mn, b.mx);
+        }
+    } else {
+        for (int cc = 0; cc < 2; ++cc) box6_merge_keys(key, raw[link].box[cc], raw[link].box[cc] + 3);
+    }
+    for (int j = 0; j < 6; ++j) raw[k].box[c][j] = key_f64(key[j]);
+}
+// The sequential refit: children carry larger numbers than their parents, so k runs downward.
+inline void refit_raw(RawNode *raw, uint32_t n_nodes, const uint32_t *order, const Box6 *boxes) {
+    for (uint32_t k = n_nodes; k-- > 0;)
+        for (int c = 0; c < 2; ++c) refit_child(raw, k, c, order, boxes);
+}
+// The root's box: the union of node 0's child boxes (without a never-hit slot).
+RRT_BB_HD void root_box_of(const RawNode &root, double *out /* 6 */) {
+    uint64_t key[6] = {kKeyPosInf, kKeyPosInf, kKeyPosInf, kKeyNegInf, kKeyNegInf, kKeyNegInf};
+    for (int c = 0; c < 2; ++c)
+        if (root.link[c] != 0u) box6_merge_keys(key, root.box[c], root.box[c] + 3);
+    for (int j = 0; j < 6; ++j) out[j] = key_f64(key[j]);
+}
+
+// The tree's SAH cost: node k's term is w0 * A(box0) + w1 * A(box1), A = box_area's operations, w =
+// a leaf child's primitive count or node_cost for a node child (0 for a never-hit slot); the cost is
+// the terms summed for k = 0 .. n-1 in that order, divided by the root box's area.
+RRT_BB_HD double box6_area(const double *box) {
+    const double a = box[3] - box[0], c1 = box[4] - box[1], c2 = box[5] - box[2];
+    return 2.0 * (a * c1 + a * c2 + c1 * c2);
+}
+RRT_BB_HD double sah_term(const RawNode &r, double node_cost) {
+    double w[2];
+    for (int c = 0; c < 2; ++c) w[c] = r.link[c] == 0u ? 0.0 : (link_is_leaf(r.link[c]) ? (double)(r.link[c] >> kLeafShift) : node_cost);
+    return w[0] * box6_area(r.box[0]) + w[1] * box6_area(r.box[1]);
+}
+inline double sah_of_terms(const double *terms, uint32_t n_nodes, const RawNode &root) {
+    double sum = 0.0;
+    for (uint32_t k = 0; k < n_nodes; ++k) sum += terms[k];
+    double rb[6];
+    root_box_of(root, rb);
+    return sum / box6_area(rb);
+}
+
 // What the build reports besides nodes and order.
 struct Summary {
     uint32_t n_nodes, n_leaves, max_depth, max_leaf;  // max_leaf: the largest leaf's count

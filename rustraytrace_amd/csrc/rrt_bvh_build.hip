@@ -15,6 +15,7 @@
 #include "rrt_internal.h"
 
 #include <algorithm>
+#include <atomic>
 #include <vector>
 
 namespace rrt {
@@ -25,6 +26,10 @@ namespace {
 
 constexpr int kBlk = 256;
 constexpr int kScanBlk = 1024;
+// Trees of at most this many nodes refit in one workgroup (k_refit_small); larger ones take one
+// launch per level. Measured on MI355X: the single workgroup wins up to 16,384 nodes
+// (0.180 against 0.197 ms for the whole refit) and loses at 32,402 (0.337 against 0.318 ms).
+constexpr uint32_t kRefitSmallMaxNodes = 16384;
 constexpr uint32_t kBinWords = 13;                       // u64 words of a Bin: n, k[12]
 constexpr uint32_t kTaskWords = 3 * kBins * kBinWords;   // of a task's bins
 static_assert(sizeof(Bin) == kBinWords * 8, "Bin is 13 packed u64");
@@ -312,6 +317,72 @@ __global__ __launch_bounds__(kBlk) void k_pack(uint32_t n_nodes, const RawNode *
     for (uint32_t j = 0; j < words; ++j) out[(size_t)k * words + j] = w[j];
 }
 
+// k_pack with the slack read from device memory (the refit never brings the root box to the host).
+__global__ __launch_bounds__(kBlk) void k_pack_dev(uint32_t n_nodes, const RawNode *raw, const Slack *slack, uint32_t stride,
+                                                   uint32_t *out) {
+    const uint32_t k = blockIdx.x * kBlk + threadIdx.x;
+    if (k >= n_nodes) return;
+    uint32_t w[20];
+    pack_node(raw[k], *slack, stride, w);
+    const uint32_t words = stride / 4u;
+    for (uint32_t j = 0; j < words; ++j) out[(size_t)k * words + j] = w[j];
+}
+
+// ---- refit: the header's refit_child, one lane per (node, child) -------------------------------
+// A link the build wrote stays inside the tree; a lane that finds another one (never expected) leaves
+// its box alone instead of reading outside the arrays.
+__device__ __forceinline__ void refit_lane(RawNode *raw, uint32_t n_nodes, uint32_t n_tree, uint32_t k, int c,
+                                           const uint32_t *order, const Box6 *boxes) {
+    const uint32_t link = raw[k].link[c];
+    if (link_is_leaf(link)) {
+        const uint32_t first = link & ((1u << kLeafShift) - 1u), count = link >> kLeafShift;
+        if (first + count > n_tree) return;
+    } else if (link <= k || link >= n_nodes) {
+        return;  // 0: the never-hit slot
+    }
+    refit_child(raw, k, c, order, boxes);
+}
+
+// The per-level form: the nodes [base, end) of one level. The level below is complete (the kernel
+// boundary on the stream), and lanes of one level write disjoint boxes and read none of their level.
+__global__ __launch_bounds__(kBlk) void k_refit_level(uint32_t base, uint32_t end, RawNode *raw, uint32_t n_nodes,
+                                                      uint32_t n_tree, const uint32_t *order, const Box6 *boxes) {
+    const uint32_t lane = blockIdx.x * kBlk + threadIdx.x;
+    const uint32_t k = base + (lane >> 1);
+    if (k >= end) return;
+    refit_lane(raw, n_nodes, n_tree, k, (int)(lane & 1u), order, boxes);
+}
+
+__device__ __forceinline__ void write_slack(const RawNode *raw, Slack *slack) {
+    double rb[6];
+    root_box_of(raw[0], rb);
+    *slack = slack_of(rb);
+}
+__global__ void k_refit_slack(const RawNode *raw, Slack *slack) { write_slack(raw, slack); }
+
+// The single-workgroup form: every level in one launch, deepest first, a barrier between levels (one
+// workgroup's global stores are visible to its own waves after __syncthreads), then the slack.
+__global__ __launch_bounds__(kScanBlk) void k_refit_small(uint32_t n_levels, const uint32_t *level_base, RawNode *raw,
+                                                          uint32_t n_nodes, uint32_t n_tree, const uint32_t *order,
+                                                          const Box6 *boxes, Slack *slack) {
+    for (uint32_t l = n_levels; l-- > 0;) {
+        const uint32_t base = level_base[l], end = level_base[l + 1u];
+        for (uint32_t lane = threadIdx.x; lane < 2u * (end - base); lane += kScanBlk)
+            refit_lane(raw, n_nodes, n_tree, base + (lane >> 1), (int)(lane & 1u), order, boxes);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) write_slack(raw, slack);
+}
+
+// The SAH terms (rrt_scene_tree_cost): one lane per node.
+__global__ __launch_bounds__(kBlk) void k_sah_terms(uint32_t n_nodes, const RawNode *raw, double node_cost, double *terms,
+                                                    RawNode *root_out) {
+    const uint32_t k = blockIdx.x * kBlk + threadIdx.x;
+    if (k >= n_nodes) return;
+    terms[k] = sah_term(raw[k], node_cost);
+    if (k == 0) *root_out = raw[0];
+}
+
 uint32_t blocks_of(uint32_t n, uint32_t b) { return (n + b - 1u) / b; }
 
 template <class T>
@@ -353,6 +424,24 @@ struct DeviceBvhBuilder::Impl {
     Summary sum{};
     uint32_t levels = 0;
     uint64_t n_alloc = 0;  // hipMalloc calls so far (allocations())
+    // refit: the first node of every level that holds nodes, then n_nodes (host and device), the
+    // kept build's node price, the slack on the device, and the SAH terms
+    std::vector<uint32_t> level_base;
+    uint32_t *d_level_base = nullptr;  // n_tree + 1 entries
+    double node_cost = 0.0;
+    Slack *d_slack = nullptr;
+    double *d_terms = nullptr;
+    size_t terms_cap = 0;
+    std::vector<double> terms;
+    // the last build's cost: its terms and root node are set aside on the device by the first refit
+    // after it (before any box changes) and summed when tree_cost() first asks
+    double *d_terms_build = nullptr;
+    size_t terms_build_cap = 0;
+    RawNode *d_root_build = nullptr;
+    bool build_captured = false, build_sah_known = false;
+    double build_sah = 0.0;
+    uint64_t refits = 0;  // since the last build
+        uint32_t last_refit_launches = 0, last_refit_form = 0;
 
     hipError_t grow_scan(size_t n_tasks) {
         if (n_tasks <= scan_cap) return hipSuccess;
@@ -381,6 +470,11 @@ struct DeviceBvhBuilder::Impl {
         (void)hipFree(d_block);
         (void)hipFree(d_totals);
         (void)hipFree(d_state);
+        (void)hipFree(d_level_base);
+        (void)hipFree(d_slack);
+        (void)hipFree(d_terms);
+        (void)hipFree(d_terms_build);
+        (void)hipFree(d_root_build);
     }
 };
 
@@ -413,7 +507,9 @@ hipError_t DeviceBvhBuilder::upload(const Box6 *boxes, uint32_t n_boxes, const u
     BB_TRY(hipMalloc((void **)&m.d_block, (size_t)nb * 4));
     BB_TRY(hipMalloc((void **)&m.d_totals, 6 * 4));
     BB_TRY(hipMalloc((void **)&m.d_state, sizeof(LevelState)));
-    m.n_alloc += 10;
+    BB_TRY(hipMalloc((void **)&m.d_level_base, ((size_t)n_tree + 1) * 4));  // a level holds a node: <= n_tree - 1 levels
+    BB_TRY(hipMalloc((void **)&m.d_slack, sizeof(Slack)));
+    m.n_alloc += 12;
     return hipSuccess;
 }
 
@@ -459,6 +555,10 @@ hipError_t DeviceBvhBuilder::build(uint32_t max_leaf, double node_cost, Summary 
 
     uint32_t n_tasks = 1, level = 0, max_depth = 0;
     LevelState st{};
+    m.level_base.clear();
+    m.node_cost = node_cost;
+    m.build_captured = m.build_sah_known = false;
+    m.refits = 0;
     while (n_tasks > 0) {
         if (level > n) return hipErrorUnknown;  // every split leaves two non-empty sides: depth < n
         const int c = m.cur, o = 1 - m.cur;
@@ -489,7 +589,10 @@ hipError_t DeviceBvhBuilder::build(uint32_t max_leaf, double node_cost, Summary 
         BB_TRY(hipGetLastError());
         BB_TRY(hipMemcpy(&st, m.d_state, sizeof(LevelState), hipMemcpyDeviceToHost));  // the per-level blocking read
         if (st.error || st.n_next > next_cap) return hipErrorUnknown;
-        if (st.n_split) max_depth = level + 1;
+        if (st.n_split) {
+            max_depth = level + 1;
+            m.level_base.push_back(st.node_base);
+        }
         m.cur = o;
         n_tasks = st.n_next;
         ++level;
@@ -500,7 +603,117 @@ hipError_t DeviceBvhBuilder::build(uint32_t max_leaf, double node_cost, Summary 
     m.sum.max_depth = std::max(max_depth, 1u);  // a root leaf: depth 1
     m.sum.max_leaf = st.max_leaf;
     if (m.sum.n_nodes == 0 || m.sum.n_nodes > n) return hipErrorUnknown;
+    if (m.level_base.empty()) m.level_base.push_back(0u);  // the root-leaf form: node 0 alone
+    m.level_base.push_back(m.sum.n_nodes);
+    if (m.level_base.size() > (size_t)n + 1) return hipErrorUnknown;
+    BB_TRY(hipMemcpy(m.d_level_base, m.level_base.data(), m.level_base.size() * 4, hipMemcpyHostToDevice));
     if (out) *out = m.sum;
+    return hipSuccess;
+}
+
+namespace {
+std::atomic<int> g_refit_form{-1};  // rrt_testing_refit_form
+}
+bool set_refit_form(int form) {
+    if (form < -1 || form > 1) return false;
+    g_refit_form.store(form);
+    return true;
+}
+
+bool DeviceBvhBuilder::refit_form_ok() const { return g_refit_form.load() != 1 || impl_->sum.n_nodes <= kRefitSmallMaxNodes; }
+uint32_t DeviceBvhBuilder::refit_small_max_nodes() { return kRefitSmallMaxNodes; }
+
+hipError_t DeviceBvhBuilder::refit(hipStream_t stream) {
+    Impl &m = *impl_;
+    const uint32_t n_nodes = m.sum.n_nodes;
+    if (n_nodes == 0 || m.level_base.size() < 2) return hipErrorInvalidValue;
+    const int forced = g_refit_form.load();
+    if (forced == 1 && n_nodes > kRefitSmallMaxNodes) return hipErrorInvalidValue;
+    const bool small = forced < 0 ? n_nodes <= kRefitSmallMaxNodes : forced == 1;
+    const uint32_t n_levels = (uint32_t)m.level_base.size() - 1u;
+    const uint32_t *order = m.d_order[m.cur];
+    uint32_t launches = 0;
+    if (!m.build_captured) {  // the build's cost terms and root, while the tree still holds them
+        if (m.terms_build_cap < n_nodes || !m.d_root_build) return hipErrorInvalidValue;  // reserve_refit() first
+        hipLaunchKernelGGL(k_sah_terms, dim3(blocks_of(n_nodes, kBlk)), dim3(kBlk), 0, stream, n_nodes, m.d_raw, m.node_cost,
+                           m.d_terms_build, m.d_root_build);
+        BB_TRY(hipGetLastError());
+        m.build_captured = true;
+        launches = 1;
+    }
+    if (small) {
+        hipLaunchKernelGGL(k_refit_small, dim3(1), dim3(kScanBlk), 0, stream, n_levels, m.d_level_base, m.d_raw, n_nodes,
+                           m.n_tree, order, m.d_boxes, m.d_slack);
+        m.last_refit_launches = launches + 1u;
+    } else {
+        for (uint32_t l = n_levels; l-- > 0;) {
+            const uint32_t base = m.level_base[l], end = m.level_base[l + 1];
+            hipLaunchKernelGGL(k_refit_level, dim3(blocks_of(2u * (end - base), kBlk)), dim3(kBlk), 0, stream, base, end,
+                               m.d_raw, n_nodes, m.n_tree, order, m.d_boxes);
+        }
+        hipLaunchKernelGGL(k_refit_slack, dim3(1), dim3(1), 0, stream, m.d_raw, m.d_slack);
+        m.last_refit_launches = launches + n_levels + 1u;
+    }
+    m.last_refit_form = small ? 1u : 0u;
+    m.refits++;
+    return hipGetLastError();
+}
+
+hipError_t DeviceBvhBuilder::emit_refit(uint32_t stride, uint8_t *d_nodes, size_t cap_bytes, hipStream_t stream) {
+    Impl &m = *impl_;
+    if ((stride != 80u && stride != 32u) || m.sum.n_nodes == 0 || !d_nodes ||
+        (size_t)m.sum.n_nodes * stride > cap_bytes)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_pack_dev, dim3(blocks_of(m.sum.n_nodes, kBlk)), dim3(kBlk), 0, stream, m.sum.n_nodes, m.d_raw,
+                       m.d_slack, stride, (uint32_t *)d_nodes);
+    return hipGetLastError();
+}
+
+uint32_t DeviceBvhBuilder::refit_launches() const { return impl_->last_refit_launches; }
+uint32_t DeviceBvhBuilder::refit_form() const { return impl_->last_refit_form; }
+
+hipError_t DeviceBvhBuilder::reserve_cost() {
+    Impl &m = *impl_;
+    BB_TRY(grow(m.d_terms, m.terms_cap, (size_t)m.n_tree, m.n_alloc));
+    if (!m.d_root_build) {
+        ++m.n_alloc;
+        BB_TRY(hipMalloc((void **)&m.d_root_build, 2 * sizeof(RawNode)));  // [0]: the build's root, [1]: the current one
+    }
+    return hipSuccess;
+}
+hipError_t DeviceBvhBuilder::reserve_refit() {
+    Impl &m = *impl_;
+    BB_TRY(reserve_cost());
+    return grow(m.d_terms_build, m.terms_build_cap, (size_t)m.n_tree, m.n_alloc);
+}
+uint64_t DeviceBvhBuilder::refits_since_build() const { return impl_->refits; }
+
+// The SAH cost of the tree held now (rrt_bvh_binned.h): the terms by one launch on the default
+// stream, copied back and summed here in node order. The caller has synchronised the device.
+hipError_t DeviceBvhBuilder::tree_cost(double *sah, double *sah_at_build) {
+    Impl &m = *impl_;
+    const uint32_t n_nodes = m.sum.n_nodes;
+    if (n_nodes == 0 || !sah || !sah_at_build) return hipErrorInvalidValue;
+    BB_TRY(reserve_cost());
+    hipLaunchKernelGGL(k_sah_terms, dim3(blocks_of(n_nodes, kBlk)), dim3(kBlk), 0, 0, n_nodes, m.d_raw, m.node_cost,
+                       m.d_terms, m.d_root_build + 1);
+    BB_TRY(hipGetLastError());
+    m.terms.resize(n_nodes);
+    RawNode root;
+    BB_TRY(hipMemcpy(m.terms.data(), m.d_terms, (size_t)n_nodes * 8, hipMemcpyDeviceToHost));
+    BB_TRY(hipMemcpy(&root, m.d_root_build + 1, sizeof(RawNode), hipMemcpyDeviceToHost));
+    *sah = sah_of_terms(m.terms.data(), n_nodes, root);
+    if (!m.build_sah_known) {
+        if (m.build_captured) {  // refitted since: the terms set aside by the first refit
+            BB_TRY(hipMemcpy(m.terms.data(), m.d_terms_build, (size_t)n_nodes * 8, hipMemcpyDeviceToHost));
+            BB_TRY(hipMemcpy(&root, m.d_root_build, sizeof(RawNode), hipMemcpyDeviceToHost));
+            m.build_sah = sah_of_terms(m.terms.data(), n_nodes, root);
+        } else {
+            m.build_sah = *sah;
+        }
+        m.build_sah_known = true;
+    }
+    *sah_at_build = m.build_sah;
     return hipSuccess;
 }
 

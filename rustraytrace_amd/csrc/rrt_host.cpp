@@ -1121,6 +1121,11 @@ struct RrtScene {
     size_t nodes_cap = 0;                     // bytes of d_nodes once it holds the largest tree (first update on)
     uint64_t n_updates = 0, last_update_allocs = 0, last_update_levels = 0;
     std::string failed_update;                // non-empty: an update failed midway, renders are refused
+    // rrt_scene_refit_spheres: pinned staging for the caller's rows (spheres, then motion) and two
+    // events on the refit's stream: the rows have left the staging buffer; the refit is complete
+    uint8_t *h_stage = nullptr;
+    hipEvent_t ev_staged = nullptr, ev_refit_done = nullptr;
+    uint64_t n_refits = 0, last_refit_allocs = 0, last_refit_launches = 0, last_refit_form = 0;
 };
 
 namespace {
@@ -1155,6 +1160,9 @@ void free_scene(RrtScene *s) {
     (void)hipFree(s->d_quad_mat);
     (void)hipFree(s->d_src_spheres);
     (void)hipFree(s->d_src_motion);
+    if (s->h_stage) (void)hipHostFree(s->h_stage);
+    if (s->ev_staged) (void)hipEventDestroy(s->ev_staged);
+    if (s->ev_refit_done) (void)hipEventDestroy(s->ev_refit_done);
     delete s->builder;
     delete s;
 }
@@ -2100,18 +2108,19 @@ int32_t rrt_scene_set_camera(RrtScene *scene, const RrtCamera *cam) {
     return RRT_OK;
 }
 
-int32_t rrt_scene_update_spheres(RrtScene *scene, const RrtSphere *spheres, uint32_t n_spheres, const float *motion,
-                                 void *stream) {
-    const std::string fn = "rrt_scene_update_spheres: ";
-    RrtScene *s = scene;
+namespace {
+
+// What rrt_scene_update_spheres and rrt_scene_refit_spheres refuse before any device call.
+int check_sphere_change(const RrtScene *s, const std::string &fn, const RrtSphere *spheres, uint32_t n_spheres,
+                        const float *motion, bool &has_motion) {
     if (!s) return fail(RRT_E_INVALID, fn + "null scene");
     if (n_spheres != s->n_spheres)
         return fail(RRT_E_INVALID, fn + "n_spheres is " + std::to_string(n_spheres) + ", the scene's is " +
                                        std::to_string(s->n_spheres) + " (the primitive count is fixed at creation)");
     if (n_spheres && !spheres) return fail(RRT_E_INVALID, fn + "null spheres");
     if (!s->device_bvh)
-        return fail(RRT_E_INVALID, fn + "the scene was not created with RRT_FLAG_DEVICE_BVH (the update rebuilds its "
-                                        "tree with the device builder)");
+        return fail(RRT_E_INVALID, fn + "the scene was not created with RRT_FLAG_DEVICE_BVH (its tree is rebuilt or "
+                                        "refitted by the device builder)");
     if (s->base.n_media)
         return fail(RRT_E_INVALID, fn + "scenes with constant media are not updated (which media are unbounded "
                                         "depends on every sphere)");
@@ -2122,7 +2131,7 @@ int32_t rrt_scene_update_spheres(RrtScene *scene, const RrtSphere *spheres, uint
     for (uint32_t i = 0; i < n_spheres; ++i)
         if (spheres[i].material_index >= s->n_materials)
             return fail(RRT_E_INVALID, fn + "sphere " + std::to_string(i) + " material_index out of range");
-    bool has_motion = false;
+    has_motion = false;
     if (motion)
         for (size_t i = 0; i < (size_t)n_spheres * 4 && !has_motion; ++i)
             has_motion = (i % 4 != 3) && motion[i] != 0.0f;
@@ -2131,16 +2140,15 @@ int32_t rrt_scene_update_spheres(RrtScene *scene, const RrtSphere *spheres, uint
                                         "class is fixed at creation)");
     if (has_motion && !(s->base.flags & RRT_FLAG_RAY_TIME))
         return fail(RRT_E_INVALID, fn + "moving spheres need RRT_FLAG_RAY_TIME (rays carry the camera's time draw)");
+    return RRT_OK;
+}
 
-    // ---- device work, on the default stream after `stream` has drained. The first update's
-    // allocations fail without touching the scene; a failure after them leaves it invalid (broke).
-    HIP_TRY(hipSetDevice(s->device), "hipSetDevice");
-    HIP_TRY(hipStreamSynchronize((hipStream_t)stream), "hipStreamSynchronize");
+// The first update or refit of a scene: the device staging of the rows, the node buffer at capacity,
+// the builder's reserve. A failure leaves the scene as it was. own_allocs counts the allocations.
+int ensure_change_buffers(RrtScene *s, const std::string &fn, uint64_t &own_allocs) {
     rrt::KParams &p = s->base;
-    const uint32_t n_prims = p.n_prims;
-    const uint64_t allocs_before = s->builder->allocations();
-    uint64_t own_allocs = 0;
-    if (!s->d_src_spheres) {  // the first update: staging, the node buffer at capacity, the builder's reserve
+    const uint32_t n_spheres = s->n_spheres;
+    if (!s->d_src_spheres) {
         ++own_allocs;
         HIP_TRY(hipMalloc((void **)&s->d_src_spheres, std::max<size_t>(n_spheres, 1) * sizeof(RrtSphere)), "hipMalloc spheres");
     }
@@ -2149,7 +2157,7 @@ int32_t rrt_scene_update_spheres(RrtScene *scene, const RrtSphere *spheres, uint
         HIP_TRY(hipMalloc((void **)&s->d_src_motion, std::max<size_t>(n_spheres, 1) * 4 * sizeof(float)), "hipMalloc motion");
     }
     if (!s->nodes_cap) {
-        const size_t cap = (size_t)(n_prims - 1u) * sizeof(rrt::GNode);  // a binary tree's internal nodes, 80-B form
+        const size_t cap = (size_t)(p.n_prims - 1u) * sizeof(rrt::GNode);  // a binary tree's internal nodes, 80-B form
         uint8_t *d = nullptr;
         ++own_allocs;
         HIP_TRY(hipMalloc((void **)&d, cap), "hipMalloc nodes");
@@ -2164,6 +2172,57 @@ int32_t rrt_scene_update_spheres(RrtScene *scene, const RrtSphere *spheres, uint
         s->nodes_cap = cap;
         if (s->builder->reserve() != hipSuccess) return fail(RRT_E_NOMEM, fn + "reserving the builder's workspace failed");
     }
+    return RRT_OK;
+}
+
+rrt::LeafTables leaf_tables_of(const RrtScene *s, const float *d_motion) {
+    rrt::LeafTables t{};
+    t.n_prims = s->base.n_prims, t.n_spheres = s->n_spheres, t.book2 = s->book2 ? 1u : 0u, t.f64 = s->f64 ? 1u : 0u;
+    t.order = s->builder->device_order();
+    t.spheres = s->d_src_spheres;
+    t.motion = d_motion;
+    t.mats = s->d_src_mats;
+    t.mat_diel = s->d_src_diel;
+    t.quad_rows = s->d_quad_rows;
+    t.quad_mat = s->d_quad_mat;
+    t.prim_cr = s->d_prim_cr;
+    t.prim_mtl = s->d_prim_mtl;
+    t.prim_motion = s->d_prim_motion;
+    t.prim_inv_r64 = s->d_prim_inv_r64;
+    t.prim_diel64 = s->d_prim_diel64;
+    return t;
+}
+
+// Scene creation's range check over the prim_cr rows of an f64 scene: (center, max(r, 0)) and the quads'.
+void sphere32_recheck(RrtScene *s, const RrtSphere *spheres, uint32_t n_spheres) {
+    bool in = s->quads_in_sphere32;
+    for (uint32_t i = 0; i < n_spheres && in; ++i) {
+        const float *c = spheres[i].center_radius;
+        in = row_in_sphere32(c[0], c[1], c[2], std::max(c[3], 0.0f));
+    }
+    s->base.sphere32 = sphere32_flag(in);
+}
+
+}  // namespace
+
+int32_t rrt_scene_update_spheres(RrtScene *scene, const RrtSphere *spheres, uint32_t n_spheres, const float *motion,
+                                 void *stream) {
+    const std::string fn = "rrt_scene_update_spheres: ";
+    RrtScene *s = scene;
+    bool has_motion = false;
+    if (int rc = check_sphere_change(s, fn, spheres, n_spheres, motion, has_motion)) return rc;
+
+    // ---- device work, on the default stream after `stream` (and a refit still in flight) has
+    // drained. The first update's allocations fail without touching the scene; a failure after them
+    // leaves it invalid (broke).
+    HIP_TRY(hipSetDevice(s->device), "hipSetDevice");
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream), "hipStreamSynchronize");
+    if (s->ev_refit_done) HIP_TRY(hipEventSynchronize(s->ev_refit_done), "hipEventSynchronize");
+    rrt::KParams &p = s->base;
+    const uint32_t n_prims = p.n_prims;
+    const uint64_t allocs_before = s->builder->allocations();
+    uint64_t own_allocs = 0;
+    if (int rc = ensure_change_buffers(s, fn, own_allocs)) return rc;
     auto broke = [&](int code, const std::string &msg) {
         s->failed_update = msg;
         return fail(code, fn + msg);
@@ -2184,29 +2243,8 @@ int32_t rrt_scene_update_spheres(RrtScene *scene, const RrtSphere *spheres, uint
     const size_t node_bytes = (size_t)fb.n_nodes * fb.stride;
     if (s->builder->emit_into(stride, s->d_nodes, s->nodes_cap, s->order.data()) != hipSuccess)
         return broke(RRT_E_HIP, "device BVH: emit failed");
-    rrt::LeafTables t{};
-    t.n_prims = n_prims, t.n_spheres = n_spheres, t.book2 = s->book2 ? 1u : 0u, t.f64 = s->f64 ? 1u : 0u;
-    t.order = s->builder->device_order();
-    t.spheres = s->d_src_spheres;
-    t.motion = d_motion;
-    t.mats = s->d_src_mats;
-    t.mat_diel = s->d_src_diel;
-    t.quad_rows = s->d_quad_rows;
-    t.quad_mat = s->d_quad_mat;
-    t.prim_cr = s->d_prim_cr;
-    t.prim_mtl = s->d_prim_mtl;
-    t.prim_motion = s->d_prim_motion;
-    t.prim_inv_r64 = s->d_prim_inv_r64;
-    t.prim_diel64 = s->d_prim_diel64;
-    if (rrt::launch_leaf_tables(t) != hipSuccess) return broke(RRT_E_HIP, "the leaf-table launch failed");
-    if (s->f64) {  // scene creation's range check over the prim_cr rows: (center, max(r, 0)) and the quads'
-        bool in = s->quads_in_sphere32;
-        for (uint32_t i = 0; i < n_spheres && in; ++i) {
-            const float *c = spheres[i].center_radius;
-            in = row_in_sphere32(c[0], c[1], c[2], std::max(c[3], 0.0f));
-        }
-        p.sphere32 = sphere32_flag(in);
-    }
+    if (rrt::launch_leaf_tables(leaf_tables_of(s, d_motion)) != hipSuccess) return broke(RRT_E_HIP, "the leaf-table launch failed");
+    if (s->f64) sphere32_recheck(s, spheres, n_spheres);
     tree_params(p, fb, node_bytes, s->book2);
     if (int rc = plan_check(p)) return broke(rc, g_err);
     bvh_info_tree(s->info, fb, node_bytes, leaf_param);
@@ -2233,6 +2271,130 @@ int32_t rrt_build_bvh_binned(const RrtSphere *spheres, uint32_t n_spheres, const
     const BinnedInput in = binned_input(spheres, n_spheres, ex);
     std::vector<uint32_t> order;
     const FlatBvh fb = flatten_binned(build_binned_host(in, max_leaf, node_cost), node_stride, in, order);
+    if (info) {
+        const bool book2 = ex.motion || ex.n_quads || ex.n_media;
+        *info = RrtBvhInfo{};
+        info->n_nodes = fb.n_nodes;
+        info->n_leaves = fb.n_leaves;
+        info->max_depth = fb.max_depth;
+        info->max_leaf_size = fb.max_leaf;
+        info->node_bytes = fb.bytes.size();
+        info->node_stride = fb.stride;
+        info->prim_bytes = (uint64_t)order.size() * (rrt::kPrimBytes + (book2 ? rrt::kMotionBytes : 0)) +
+                           ((uint64_t)ex.n_quads + ex.n_bquads) * sizeof(rrt::GQuad) +
+                           (uint64_t)ex.n_media * sizeof(rrt::GMedium);
+        info->width = 2;
+        info->max_leaf_param = max_leaf;
+        info->n_unbounded = fb.n_unbounded;
+    }
+    if (nodes_cap == 0) return RRT_OK;
+    if (!nodes_out || nodes_cap < fb.bytes.size() || (order.size() && !prim_order_out))
+        return fail(RRT_E_INVALID, "nodes buffer too small (need " + std::to_string(fb.bytes.size()) + " bytes)");
+    std::memcpy(nodes_out, fb.bytes.data(), fb.bytes.size());
+    if (order.size()) std::memcpy(prim_order_out, order.data(), order.size() * sizeof(uint32_t));
+    return RRT_OK;
+}
+
+// The refit: everything after the checks is enqueued on `stream`; no host read, no wait for the
+// device (but for the staging buffer of the refit before, which its copy has long left).
+int32_t rrt_scene_refit_spheres(RrtScene *scene, const RrtSphere *spheres, uint32_t n_spheres, const float *motion,
+                                void *stream) {
+    const std::string fn = "rrt_scene_refit_spheres: ";
+    RrtScene *s = scene;
+    bool has_motion = false;
+    if (int rc = check_sphere_change(s, fn, spheres, n_spheres, motion, has_motion)) return rc;
+    if (!s->failed_update.empty())
+        return fail(RRT_E_INVALID, fn + "the scene is invalid since rrt_scene_update_spheres failed (" + s->failed_update +
+                                       "); only an update that succeeds makes it valid again");
+    if (!s->builder->refit_form_ok())
+        return fail(RRT_E_INVALID, fn + "rrt_testing_refit_form(1): the single-workgroup form takes trees of at most " +
+                                       std::to_string(rrt::DeviceBvhBuilder::refit_small_max_nodes()) + " nodes");
+    HIP_TRY(hipSetDevice(s->device), "hipSetDevice");
+    hipStream_t st = (hipStream_t)stream;
+    const uint64_t allocs_before = s->builder->allocations();
+    uint64_t own_allocs = 0;
+    const size_t sphere_bytes = (size_t)n_spheres * sizeof(RrtSphere), motion_bytes = (size_t)n_spheres * 4 * sizeof(float);
+    if (!s->d_src_spheres || !s->nodes_cap || (s->book2 && !s->d_src_motion)) {
+        // the first change of this scene replaces its node array: what the stream still renders must be done
+        HIP_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
+        if (int rc = ensure_change_buffers(s, fn, own_allocs)) return rc;
+    }
+    if (!s->h_stage) {  // the first refit
+        ++own_allocs;
+        HIP_TRY(hipHostMalloc((void **)&s->h_stage, std::max<size_t>(sphere_bytes + motion_bytes, 16), hipHostMallocDefault),
+                "hipHostMalloc staging");
+    }
+    if (!s->ev_staged) HIP_TRY(hipEventCreateWithFlags(&s->ev_staged, hipEventDisableTiming), "hipEventCreate");
+    if (!s->ev_refit_done) HIP_TRY(hipEventCreateWithFlags(&s->ev_refit_done, hipEventDisableTiming), "hipEventCreate");
+    if (s->builder->reserve_refit() != hipSuccess) return fail(RRT_E_NOMEM, fn + "reserving the refit's workspace failed");
+    auto broke = [&](int code, const std::string &msg) {
+        s->failed_update = msg;
+        return fail(code, fn + msg);
+    };
+    if (s->n_refits && hipEventSynchronize(s->ev_staged) != hipSuccess) return broke(RRT_E_HIP, "waiting for the staging buffer failed");
+    if (sphere_bytes) std::memcpy(s->h_stage, spheres, sphere_bytes);
+    if (has_motion) std::memcpy(s->h_stage + sphere_bytes, motion, motion_bytes);
+    if (sphere_bytes && hipMemcpyAsync(s->d_src_spheres, s->h_stage, sphere_bytes, hipMemcpyHostToDevice, st) != hipSuccess)
+        return broke(RRT_E_HIP, "copying the spheres failed");
+    if (has_motion && hipMemcpyAsync(s->d_src_motion, s->h_stage + sphere_bytes, motion_bytes, hipMemcpyHostToDevice, st) != hipSuccess)
+        return broke(RRT_E_HIP, "copying the motion rows failed");
+    if (hipEventRecord(s->ev_staged, st) != hipSuccess) return broke(RRT_E_HIP, "hipEventRecord failed");
+    const float *d_motion = has_motion ? s->d_src_motion : nullptr;
+    if (rrt::launch_sphere_boxes(n_spheres, s->d_src_spheres, d_motion, s->builder->device_boxes(), st) != hipSuccess)
+        return broke(RRT_E_HIP, "the sphere-box launch failed");
+    if (s->builder->refit(st) != hipSuccess) return broke(RRT_E_HIP, "device BVH: refit failed");
+    if (s->builder->emit_refit(s->info.node_stride, s->d_nodes, s->nodes_cap, st) != hipSuccess)
+        return broke(RRT_E_HIP, "device BVH: emit failed");
+    if (rrt::launch_leaf_tables(leaf_tables_of(s, d_motion), st) != hipSuccess) return broke(RRT_E_HIP, "the leaf-table launch failed");
+    if (hipEventRecord(s->ev_refit_done, st) != hipSuccess) return broke(RRT_E_HIP, "hipEventRecord failed");
+    if (s->f64) sphere32_recheck(s, spheres, n_spheres);
+    s->n_refits++;
+    s->last_refit_allocs = own_allocs + (s->builder->allocations() - allocs_before);
+    s->last_refit_launches = (n_spheres ? 1u : 0u) + s->builder->refit_launches() + 2u;
+    s->last_refit_form = s->builder->refit_form();
+    return RRT_OK;
+}
+
+int32_t rrt_scene_tree_cost(RrtScene *scene, RrtTreeCost *out) {
+    const std::string fn = "rrt_scene_tree_cost: ";
+    if (!scene || !out) return fail(RRT_E_INVALID, fn + "null scene or out");
+    if (!scene->builder)
+        return fail(RRT_E_INVALID, fn + "the scene holds no device builder (RRT_FLAG_DEVICE_BVH and at least 2 primitives)");
+    HIP_TRY(hipSetDevice(scene->device), "hipSetDevice");
+    HIP_TRY(hipDeviceSynchronize(), "hipDeviceSynchronize");
+    if (scene->builder->tree_cost(&out->sah, &out->sah_at_build) != hipSuccess) return fail(RRT_E_HIP, fn + "the cost launch failed");
+    out->refits_since_build = scene->builder->refits_since_build();
+    return RRT_OK;
+}
+
+int32_t rrt_refit_bvh_binned(const RrtSphere *built_spheres, uint32_t n_spheres, const RrtSceneExt *built_ext,
+                             uint32_t max_leaf, double node_cost, uint32_t node_stride, const RrtSphere *new_spheres,
+                             const float *new_motion, void *nodes_out, size_t nodes_cap, uint32_t *prim_order_out,
+                             RrtBvhInfo *info, double *sah_out) {
+    if (n_spheres && (!built_spheres || !new_spheres)) return fail(RRT_E_INVALID, "null spheres");
+    const ExtView ex(built_ext);
+    for (uint32_t m = 0; m < ex.n_media; ++m)
+        if (ex.media[m].boundary_kind == RRT_BOUNDARY_QUADS &&
+            (ex.media[m].count == 0 || (uint64_t)ex.media[m].first + ex.media[m].count > ex.n_bquads))
+            return fail(RRT_E_INVALID, "medium " + std::to_string(m) + ": boundary quad range out of bounds");
+    if (max_leaf == 0 || max_leaf > rrt::kMaxLeafPrims || (node_stride != 80u && node_stride != 32u) || !(node_cost == node_cost))
+        return fail(RRT_E_INVALID, "max_leaf must be 1..7, node_stride 80 or 32");
+    if ((uint64_t)n_spheres + ex.n_quads + ex.n_media >= (1u << 24)) return fail(RRT_E_INVALID, ">= 2^24 primitives");
+    BinnedInput in = binned_input(built_spheres, n_spheres, ex);
+    BinnedTree bt = build_binned_host(in, max_leaf, node_cost);
+    for (uint32_t i = 0; i < n_spheres; ++i)
+        in.boxes[i] = rrt::sphere_box(new_spheres[i].center_radius, new_motion ? new_motion + 4 * (size_t)i : nullptr);
+    bvhb::refit_raw(bt.raw.data(), bt.sum.n_nodes, bt.objs.data(), in.boxes.data());
+    double root_box[6];
+    bvhb::root_box_of(bt.raw[0], root_box);
+    bt.slack = bvhb::slack_of(root_box);
+    if (sah_out) {
+        std::vector<double> terms(bt.raw.size());
+        for (size_t k = 0; k < bt.raw.size(); ++k) terms[k] = bvhb::sah_term(bt.raw[k], node_cost);
+        *sah_out = bvhb::sah_of_terms(terms.data(), bt.sum.n_nodes, bt.raw[0]);
+    }
+    std::vector<uint32_t> order;
+    const FlatBvh fb = flatten_binned(bt, node_stride, in, order);
     if (info) {
         const bool book2 = ex.motion || ex.n_quads || ex.n_media;
         *info = RrtBvhInfo{};
@@ -2444,6 +2606,22 @@ extern "C" int32_t rrt_testing_scene_update_stats(const RrtScene *scene, RrtScen
     out->updates = scene->n_updates;
     out->last_allocations = scene->last_update_allocs;
     out->last_levels = scene->last_update_levels;
+    return RRT_OK;
+}
+
+extern "C" int32_t rrt_testing_scene_refit_stats(const RrtScene *scene, RrtSceneRefitStats *out) {
+    if (!scene || !out) return fail(RRT_E_INVALID, "rrt_testing_scene_refit_stats: null scene or out");
+    out->refits = scene->n_refits;
+    out->last_allocations = scene->last_refit_allocs;
+    out->last_launches = scene->last_refit_launches;
+    out->last_form = scene->last_refit_form;
+    return RRT_OK;
+}
+
+// Test mode (rrt_testing_refit_form): the refit's per-level launches (0) or its single workgroup (1)
+// whatever the tree's size; -1 restores the automatic choice.
+extern "C" int32_t rrt_testing_refit_form(int32_t form) {
+    if (!rrt::set_refit_form(form)) return fail(RRT_E_INVALID, "rrt_testing_refit_form: the form is -1, 0 or 1");
     return RRT_OK;
 }
 

@@ -454,13 +454,33 @@ public:
     hipError_t reserve();
     hipError_t emit_into(uint32_t stride, uint8_t *d_nodes, size_t cap_bytes, uint32_t *order_out);
     uint64_t allocations() const;
+    // Refit (rrt_scene_refit_spheres): the boxes of the last build's tree recomputed bottom-up from
+    // device_boxes() (rrt_bvh_binned.h refit_raw), links and leaf order kept, then the root's slack,
+    // all enqueued on `stream` with no host synchronisation and no allocation: one launch per level,
+    // deepest first, or for a small tree one single-workgroup launch that loops over the levels.
+    // emit_refit() packs the refitted nodes on the same stream with the slack read on the device.
+    // refit_launches() / refit_form() (1: the single workgroup): the last refit's.
+    hipError_t refit(hipStream_t stream);
+    bool refit_form_ok() const;  // false: the single workgroup is forced (set_refit_form) on a tree over its bound
+    static uint32_t refit_small_max_nodes();
+    hipError_t emit_refit(uint32_t stride, uint8_t *d_nodes, size_t cap_bytes, hipStream_t stream);
+    uint32_t refit_launches() const;
+    uint32_t refit_form() const;
+    // The SAH cost (rrt_bvh_binned.h sah_term / sah_of_terms) of the tree held now and of the last
+    // build's tree, on the default stream, synchronous (the caller has synchronised the device). The
+    // first refit after a build sets the build's terms aside on its stream, so refit() needs
+    // reserve_refit() once beforehand (it allocates; reserve_cost() is tree_cost()'s own part).
+    hipError_t reserve_cost();
+    hipError_t reserve_refit();
+    hipError_t tree_cost(double *sah, double *sah_at_build);
+    uint64_t refits_since_build() const;
 
 private:
     struct Impl;
     Impl *impl_;
 };
 
-// The scene-update kernels (rrt_scene_update.hip), on the default stream:
+// The scene-update kernels (rrt_scene_update.hip), on `stream` (the default stream when null):
 //   launch_sphere_boxes  one lane per sphere: its padded f64 box (rrt_sphere_box.h) into boxes[i];
 //                        spheres = RrtSphere records, motion = n x 4 floats or null
 //   launch_leaf_tables   one lane per leaf position: the per-primitive tables scene creation forms
@@ -479,7 +499,11 @@ struct LeafTables {
     double *prim_inv_r64;      // f64
     double4 *prim_diel64;      // f64
 };
-hipError_t launch_sphere_boxes(uint32_t n, const void *d_spheres, const float *d_motion, void *d_boxes);
-hipError_t launch_leaf_tables(const LeafTables &t);
+hipError_t launch_sphere_boxes(uint32_t n, const void *d_spheres, const float *d_motion, void *d_boxes,
+                               hipStream_t stream = nullptr);
+hipError_t launch_leaf_tables(const LeafTables &t, hipStream_t stream = nullptr);
+// Test support (rrt_testing_refit_form): force the refit's per-level launches (0) or its single
+// workgroup (1); -1: the automatic choice. False for another value.
+bool set_refit_form(int form);
 
 }  // namespace rrt

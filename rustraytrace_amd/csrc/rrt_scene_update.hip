@@ -1,4 +1,4 @@
-// rrt_scene_update.hip — the device side of rrt_scene_update_spheres: the spheres' padded boxes for
+// rrt_scene_update.hip — the device side of rrt_scene_update_spheres and rrt_scene_refit_spheres: the spheres' padded boxes for
 // the builder (rrt_bvh_build.hip) and, after the build, the per-primitive tables in leaf order. Both
 // kernels restate what scene creation computes on the host (rrt_host.cpp prim_boxes and
 // prim_table_row) so that an updated scene holds the bytes of a freshly created one. One lane per
@@ -77,16 +77,16 @@ __global__ __launch_bounds__(kBlk) void k_leaf_tables(LeafTables t) {
 
 }  // namespace
 
-hipError_t launch_sphere_boxes(uint32_t n, const void *d_spheres, const float *d_motion, void *d_boxes) {
+hipError_t launch_sphere_boxes(uint32_t n, const void *d_spheres, const float *d_motion, void *d_boxes, hipStream_t stream) {
     if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_sphere_boxes, dim3((n + kBlk - 1) / kBlk), dim3(kBlk), 0, 0, n,
+    hipLaunchKernelGGL(k_sphere_boxes, dim3((n + kBlk - 1) / kBlk), dim3(kBlk), 0, stream, n,
                        reinterpret_cast<const RrtSphere *>(d_spheres), d_motion, reinterpret_cast<bvhb::Box6 *>(d_boxes));
     return hipGetLastError();
 }
 
-hipError_t launch_leaf_tables(const LeafTables &t) {
+hipError_t launch_leaf_tables(const LeafTables &t, hipStream_t stream) {
     if (t.n_prims == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_leaf_tables, dim3((t.n_prims + kBlk - 1) / kBlk), dim3(kBlk), 0, 0, t);
+    hipLaunchKernelGGL(k_leaf_tables, dim3((t.n_prims + kBlk - 1) / kBlk), dim3(kBlk), 0, stream, t);
     return hipGetLastError();
 }
 

@@ -332,6 +332,37 @@ def build_bvh_binned(scene: SceneData, max_leaf: int, node_cost: float, node_str
     return nodes, order[:n_prims], info.as_dict()
 
 
+def refit_bvh_binned(built_scene: SceneData, new_spheres, new_motion, max_leaf: int, node_cost: float, node_stride: int):
+    """rrt_refit_bvh_binned (host only): build_bvh_binned's tree of `built_scene` with its boxes
+    recomputed over new_spheres and new_motion (None = all zero), the specification of
+    DeviceScene.refit_spheres. Returns (node bytes, leaf order, info dict, sah)."""
+    lib = _lib.load()
+    info = _lib.RrtBvhInfo()
+    sah = ctypes.c_double(0.0)
+    n = len(built_scene.spheres)
+    sp = np.ascontiguousarray(new_spheres, dtype=_lib.SPHERE_DTYPE)
+    assert len(sp) == n, "a refit keeps the sphere count"
+    m = None
+    if new_motion is not None:
+        m = np.ascontiguousarray(new_motion, dtype=np.float32)
+        assert m.shape == (n, 4), "motion is (n_spheres, 4) float32"
+    ext, keep = scene_ext(built_scene)
+    n_prims = n + (0 if ext is None else ext.n_quads + ext.n_media)
+    extp = ctypes.byref(ext) if ext is not None else None
+
+    def refit(nodes_p, cap, order_p):
+        return lib.rrt_refit_bvh_binned(_lib.ptr(built_scene.spheres), n, extp, int(max_leaf), float(node_cost),
+                                        int(node_stride), _lib.ptr(sp), _lib.ptr(m), nodes_p, cap, order_p,
+                                        ctypes.byref(info), ctypes.byref(sah))
+
+    _lib.check(refit(None, 0, None))
+    nodes = np.zeros(info.node_bytes, dtype=np.uint8)
+    order = np.zeros(max(n_prims, 1), dtype=np.uint32)
+    _lib.check(refit(_lib.ptr(nodes), nodes.size, _lib.ptr(order)))
+    del keep
+    return nodes, order[:n_prims], info.as_dict(), float(sah.value)
+
+
 def decode_bvh2(nodes: np.ndarray, stride: int):
     """Decode build_bvh's width-2 node bytes (rrt_internal.h; stride = info["node_stride"]: 80 =
     GNode, sign-ordered lo/hi/lo planes, 32 = GNodeH, f16 planes): per node and child, box lo/hi (n, 2, 3),
@@ -451,6 +482,33 @@ class DeviceScene:
         _lib.check(self._lib.rrt_scene_update_spheres(self._h, _lib.ptr(sp), len(sp), _lib.ptr(m),
                                                       ctypes.c_void_p(stream_ptr)))
         self.scene = dataclasses.replace(self.scene, spheres=sp.copy(), motion=None if m is None else m.copy())
+
+    def refit_spheres(self, spheres, motion=None, stream_ptr: int = 0) -> None:
+        """rrt_scene_refit_spheres: replaces the spheres (and motion rows) like update_spheres but keeps
+        the tree's topology and leaf order and recomputes only its boxes; everything is enqueued on
+        the stream and the call does not wait for the device. tree_cost() tells when to rebuild."""
+        sp = np.ascontiguousarray(spheres, dtype=_lib.SPHERE_DTYPE)
+        m = None
+        if motion is not None:
+            m = np.ascontiguousarray(motion, dtype=np.float32)
+            assert m.shape == (len(sp), 4), "motion is (n_spheres, 4) float32"
+        _lib.check(self._lib.rrt_scene_refit_spheres(self._h, _lib.ptr(sp), len(sp), _lib.ptr(m),
+                                                     ctypes.c_void_p(stream_ptr)))
+        self.scene = dataclasses.replace(self.scene, spheres=sp.copy(), motion=None if m is None else m.copy())
+
+    def tree_cost(self) -> dict:
+        """rrt_scene_tree_cost: the SAH cost of the tree held now, of the last build's tree, and the
+        refits since that build. Synchronises the device."""
+        c = _lib.RrtTreeCost()
+        _lib.check(self._lib.rrt_scene_tree_cost(self._h, ctypes.byref(c)))
+        return {"sah": float(c.sah), "sah_at_build": float(c.sah_at_build), "refits_since_build": int(c.refits_since_build)}
+
+    def refit_stats(self) -> dict:
+        """rrt_testing_scene_refit_stats (test support): refits so far; the last one's device
+        allocations, kernel launches and form (1: the single workgroup, 0: one launch per level)."""
+        st = _lib.RrtSceneRefitStats()
+        _lib.check(self._lib.rrt_testing_scene_refit_stats(self._h, ctypes.byref(st)))
+        return {k: int(getattr(st, k)) for k, _ in st._fields_}
 
     def read_table(self, name: str) -> np.ndarray:
         """rrt_testing_scene_read_table (test support): one of the scene's device tables (a
