@@ -496,6 +496,65 @@ int32_t rrt_refit_bvh_binned(const RrtSphere *built_spheres, uint32_t n_spheres,
                              void *nodes_out, size_t nodes_cap, uint32_t *prim_order_out,
                              RrtBvhInfo *info, double *sah_out);
 
+/* ---- changing quads and book-3 lights too (additive; RRT_ABI_VERSION is unchanged) -------- */
+
+/* The geometry of a created scene, replaced as a whole. spheres / n_spheres / sphere_motion: as the
+ * arguments of rrt_scene_update_spheres (n_spheres must equal the scene's; motion NULL = all zero).
+ * quads: NULL keeps the scene's quads; else n_quads must equal the scene's, and each quad's q, u, v,
+ * and material_index replace the old. lights: for an RRT_FLAG_BOOK3 scene required, n_lights equal
+ * to the scene's and each entry's kind unchanged (the light list restates geometry: move a light
+ * with the quad or sphere it samples); for any other scene NULL / 0. Materials, textures and Perlin
+ * tables are kept. */
+typedef struct RrtSceneGeometry {
+    const RrtSphere *spheres;
+    uint32_t n_spheres;
+    const float *sphere_motion;
+    const RrtQuad *quads;
+    uint32_t n_quads;
+    const RrtLight *lights;
+    uint32_t n_lights;
+} RrtSceneGeometry;
+
+/* rrt_scene_update_spheres' contract extended to quads and lights: rebuilds the BVH on the device
+ * over the new sphere and quad boxes and re-forms there everything scene creation derives from the
+ * geometry, after which the scene holds, bit for bit, what rrt_scene_create_ex makes of the new
+ * inputs: the tree, the leaf order and RrtBvhInfo, every per-primitive table, the quad records (scene
+ * quads and light quads; the unrounded ones of an RRT_FLAG_F64_BOOK2 scene), the quads' table rows
+ * and material indices, the light records, every frame and its ray count. Waits for `stream` (and for
+ * a refit still in flight), then runs and returns synchronised. From the second geometry change of a
+ * scene on, no device memory is allocated or freed.
+ * Refused with RRT_E_INVALID, before any device call and with the scene untouched: everything
+ * rrt_scene_update_spheres refuses except RRT_FLAG_BOOK3 (a scene without RRT_FLAG_DEVICE_BVH, with
+ * media, of fewer than 2 primitives, ...); a scene with boundary quads; another n_quads or n_lights;
+ * a light whose kind differs from the scene's entry; lights missing on an RRT_FLAG_BOOK3 scene or
+ * given on any other; a quad material_index out of range or naming an image-textured material
+ * (scene creation's rule); a quad (or a quad light) whose q, u or v is not finite or whose u x v has
+ * a zero or non-finite squared length. The last is refused because a NaN formed on the host and one
+ * formed on the device need not agree in sign and payload, so the bit-for-bit contract cannot cover
+ * such quads (scene creation still accepts them).
+ * A failure after device work has begun leaves the scene invalid exactly as a failed
+ * rrt_scene_update_spheres does. */
+int32_t rrt_scene_update_geometry(RrtScene *scene, const RrtSceneGeometry *geometry, void *stream);
+
+/* rrt_scene_refit_spheres' contract extended to quads and lights, with rrt_scene_update_geometry's
+ * arguments and refusals: the tree keeps the topology and leaf order of the last build, its boxes
+ * are recomputed bottom-up from the new sphere and quad boxes (bit for bit rrt_refit_bvh_binned_ex),
+ * and every derived record and table is re-formed, in the kept leaf order. Everything is enqueued on
+ * `stream` with no host synchronisation; the pinned staging buffer holds the quad and light rows
+ * behind the spheres', sized once at the first geometry refit. Later geometry refits allocate and
+ * free nothing. Refits of both kinds compose with each other and with either update, and
+ * rrt_scene_tree_cost keeps working across them. */
+int32_t rrt_scene_refit_geometry(RrtScene *scene, const RrtSceneGeometry *geometry, void *stream);
+
+/* Host-only: rrt_refit_bvh_binned with new quads as well (new_quads: built_ext's n_quads records, or
+ * NULL = the built ones; media keep their boxes). The specification of rrt_scene_refit_geometry's
+ * tree, sah_out included. */
+int32_t rrt_refit_bvh_binned_ex(const RrtSphere *built_spheres, uint32_t n_spheres, const RrtSceneExt *built_ext,
+                                uint32_t max_leaf, double node_cost, uint32_t node_stride,
+                                const RrtSphere *new_spheres, const float *new_motion, const RrtQuad *new_quads,
+                                void *nodes_out, size_t nodes_cap, uint32_t *prim_order_out,
+                                RrtBvhInfo *info, double *sah_out);
+
 /* ---- host-side callers of the boundary ------------------------------------------------ */
 
 /* == gpu::build_in_one_weekend_scene (gpu/mod.rs:124-301): RTOW final scene from
@@ -744,7 +803,13 @@ typedef enum RrtSceneTable {
     RRT_TABLE_PRIM_MTL = 2,     /* 32-B material record */
     RRT_TABLE_PRIM_MOTION = 3,  /* float4, book-2 worlds */
     RRT_TABLE_PRIM_INV_R64 = 4, /* double, RRT_FLAG_F64 */
-    RRT_TABLE_PRIM_DIEL64 = 5   /* 4 doubles, RRT_FLAG_F64 */
+    RRT_TABLE_PRIM_DIEL64 = 5,  /* 4 doubles, RRT_FLAG_F64 */
+    /* the geometry tables (rrt_scene_update_geometry), in source order */
+    RRT_TABLE_GQUADS = 6,       /* 80-B quad records: the scene's quads, boundary quads, light quads */
+    RRT_TABLE_GQUADS64 = 7,     /* 128-B unrounded quad records, RRT_FLAG_F64_BOOK2 (instead of 6) */
+    RRT_TABLE_QUAD_ROWS = 8,    /* 2 float4 per quad: its prim_cr row, its prim_motion row (held by
+                                   a scene the device builder built, without media) */
+    RRT_TABLE_GLIGHTS = 9       /* 32-B light records, RRT_FLAG_BOOK3 */
 } RrtSceneTable;
 typedef struct RrtSceneUpdateStats {
     uint64_t updates;
@@ -754,6 +819,12 @@ typedef struct RrtSceneUpdateStats {
 int32_t rrt_testing_sphere_boxes(const RrtSphere *spheres, uint32_t n_spheres, const float *motion, double *out);
 int32_t rrt_testing_scene_read_table(RrtScene *scene, uint32_t what, void *out, size_t cap, size_t *bytes_out);
 int32_t rrt_testing_scene_update_stats(const RrtScene *scene, RrtSceneUpdateStats *out);
+/* Test support, not part of the drop-in: what a quad contributes to a scene, by the host compilation
+ * of the functions rrt_scene_update_geometry runs on the device (and scene creation on the host).
+ * Any output may be NULL. boxes6: n_quads x 6 doubles (min xyz, max xyz), the padded box; gquad:
+ * n_quads 80-B records (RRT_TABLE_GQUADS' layout); gquad64: n_quads 128-B records
+ * (RRT_TABLE_GQUADS64's: q, u, v, n, w as 3 doubles each, then D). */
+int32_t rrt_testing_quad_records(const RrtQuad *quads, uint32_t n_quads, double *boxes6, void *gquad, void *gquad64);
 
 /* Test support, not part of the drop-in. rrt_testing_scene_refit_stats: the scene's refits so far,
  * and of the last one the device allocations, the kernel launches and the form of the bottom-up

@@ -107,6 +107,10 @@ EXPORTED_SYMBOLS = (
     "rrt_refit_bvh_binned",
     "rrt_testing_scene_refit_stats",
     "rrt_testing_refit_form",
+    "rrt_scene_update_geometry",
+    "rrt_scene_refit_geometry",
+    "rrt_refit_bvh_binned_ex",
+    "rrt_testing_quad_records",
 )
 
 # == RrtSceneTable (include/rrt_hip.h, test support): table -> (code, row dtype)
@@ -114,6 +118,23 @@ SCENE_TABLES = {
     "boxes": (0, np.dtype("<f8")), "prim_cr": (1, np.dtype("<f4")), "prim_mtl": (2, np.dtype("<u4")),
     "prim_motion": (3, np.dtype("<f4")), "prim_inv_r64": (4, np.dtype("<f8")), "prim_diel64": (5, np.dtype("<f8")),
 }
+
+
+# The tables rrt_scene_update_geometry re-forms beyond SCENE_TABLES (RrtSceneTable 6-9), in source
+# order: table -> (code, row dtype). GQUAD_DTYPE / GQUAD64_DTYPE / GLIGHT_DTYPE give their records.
+SCENE_GEOMETRY_TABLES = {
+    "gquads": (6, np.dtype("<f4")), "gquads64": (7, np.dtype("<f8")), "quad_rows": (8, np.dtype("<f4")),
+    "glights": (9, np.dtype("<u4")),
+}
+GQUAD_DTYPE = np.dtype([("q", "<f4", 4), ("u", "<f4", 4), ("v", "<f4", 4), ("n", "<f4", 4), ("w", "<f4", 4)])  # q[3] = D
+GQUAD64_DTYPE = np.dtype([("q", "<f8", 3), ("u", "<f8", 3), ("v", "<f8", 3), ("n", "<f8", 3), ("w", "<f8", 3), ("D", "<f8")])
+GLIGHT_DTYPE = np.dtype([("sphere", "<f4", 4), ("kind", "<u4"), ("quad", "<u4"), ("area", "<f4"), ("_pad", "<u4")])
+assert GQUAD_DTYPE.itemsize == 80 and GQUAD64_DTYPE.itemsize == 128 and GLIGHT_DTYPE.itemsize == 32
+
+
+class RrtSceneGeometry(ctypes.Structure):  # include/rrt_hip.h
+    _fields_ = [("spheres", c_void_p), ("n_spheres", c_uint32), ("sphere_motion", c_void_p), ("quads", c_void_p),
+                ("n_quads", c_uint32), ("lights", c_void_p), ("n_lights", c_uint32)]
 
 
 class RrtSceneUpdateStats(ctypes.Structure):  # include/rrt_hip.h, test support
@@ -331,6 +352,17 @@ def sphere_boxes(spheres, motion=None) -> np.ndarray:
     return out
 
 
+def quad_records(quads):
+    """rrt_testing_quad_records (test support): what each quad contributes to a scene, by the host
+    compilation of the functions rrt_scene_update_geometry runs on the device: (boxes (n, 6) float64 as
+    min xyz, max xyz; GQUAD_DTYPE records; GQUAD64_DTYPE records)."""
+    q = np.ascontiguousarray(quads, dtype=QUAD_DTYPE)
+    boxes = np.zeros((len(q), 6), dtype=np.float64)
+    g32, g64 = np.zeros(len(q), dtype=GQUAD_DTYPE), np.zeros(len(q), dtype=GQUAD64_DTYPE)
+    check(load().rrt_testing_quad_records(ptr(q), len(q), ptr(boxes), ptr(g32), ptr(g64)))
+    return boxes, g32, g64
+
+
 def div_check(a_values) -> list:
     """rrt_testing_div_check (test support): the eight counters for the divisors a_values."""
     a = np.ascontiguousarray(a_values, dtype=np.float32).ravel()
@@ -439,6 +471,10 @@ def load() -> ctypes.CDLL:
         "rrt_refit_bvh_binned": (c_int32, [P, c_uint32, P, c_uint32, c_double, c_uint32, P, P, P, c_size_t, P, P, P]),
         "rrt_testing_scene_refit_stats": (c_int32, [P, P]),
         "rrt_testing_refit_form": (c_int32, [c_int32]),
+        "rrt_scene_update_geometry": (c_int32, [P, P, P]),
+        "rrt_scene_refit_geometry": (c_int32, [P, P, P]),
+        "rrt_refit_bvh_binned_ex": (c_int32, [P, c_uint32, P, c_uint32, c_double, c_uint32, P, P, P, P, c_size_t, P, P, P]),
+        "rrt_testing_quad_records": (c_int32, [P, c_uint32, P, P, P]),
     }
     experiment = "RRT_LIB_PATH" in os.environ  # A/B of older builds: tolerate symbols they lack
     for name, (res, args) in sig.items():

@@ -11,6 +11,7 @@
 #include "rrt_internal.h"
 #include "rrt_bvh_binned.h"
 #include "rrt_sphere_box.h"
+#include "rrt_quad_form.h"
 #include "../../include/rrt_hip.h"
 
 #include <algorithm>
@@ -674,16 +675,12 @@ void bvh_defaults(uint32_t &width, uint32_t &max_leaf) {
     if (width == 2) max_leaf = std::min(max_leaf, rrt::kMaxLeafPrims);
 }
 
-// Quad::set_bounding_box (quad.rs:43-47): the box of the four corners, padded.
+// Quad::set_bounding_box (quad.rs:43-47): the box of the four corners, padded (rrt_quad_form.h).
 static Aabb quad_box(const RrtQuad &qd) {
+    const rrt::bvhb::Box6 b6 = rrt::quad_box(qd.q, qd.u, qd.v);
     Aabb b;
-    for (int a = 0; a < 3; ++a) {
-        const double q = qd.q[a], u = qd.u[a], v = qd.v[a];
-        const double c[4] = {q, q + u + v, q + u, q + v};
-        b.ax[a] = Interval{std::min(std::min(c[0], c[1]), std::min(c[2], c[3])),
-                           std::max(std::max(c[0], c[1]), std::max(c[2], c[3]))};
-    }
-    return pad(b);
+    for (int a = 0; a < 3; ++a) b.ax[a] = Interval{b6.mn[a], b6.mx[a]};
+    return b;
 }
 
 // Book-2 extension arrays with null-safe counts.
@@ -1126,6 +1123,15 @@ struct RrtScene {
     uint8_t *h_stage = nullptr;
     hipEvent_t ev_staged = nullptr, ev_refit_done = nullptr;
     uint64_t n_refits = 0, last_refit_allocs = 0, last_refit_launches = 0, last_refit_form = 0;
+    size_t stage_cap = 0;                     // bytes of h_stage
+    // rrt_scene_update_geometry / rrt_scene_refit_geometry: what the refusals read on the host (the
+    // material kinds, the light kinds, the boundary quads' count), each light's GQuad index on the
+    // device (fixed: a light keeps its kind), and the device staging of the caller's quad and light rows
+    std::vector<uint32_t> mat_kinds, light_kinds;
+    uint32_t n_bquads = 0, n_gquads = 0;      // n_gquads: records of d_quads (scene, boundary and light quads)
+    uint32_t *d_light_quad = nullptr;
+    RrtQuad *d_src_quads = nullptr;
+    RrtLight *d_src_lights = nullptr;
 };
 
 namespace {
@@ -1160,6 +1166,9 @@ void free_scene(RrtScene *s) {
     (void)hipFree(s->d_quad_mat);
     (void)hipFree(s->d_src_spheres);
     (void)hipFree(s->d_src_motion);
+    (void)hipFree(s->d_light_quad);
+    (void)hipFree(s->d_src_quads);
+    (void)hipFree(s->d_src_lights);
     if (s->h_stage) (void)hipHostFree(s->h_stage);
     if (s->ev_staged) (void)hipEventDestroy(s->ev_staged);
     if (s->ev_refit_done) (void)hipEventDestroy(s->ev_refit_done);
@@ -1203,7 +1212,7 @@ int check_tile_shape(const RrtTile *t) {
 int check_tile(const RrtScene *s, const RrtTile *t) {
     if (!s) return fail(RRT_E_INVALID, "null scene");
     if (!s->failed_update.empty())
-        return fail(RRT_E_INVALID, "the scene is invalid since rrt_scene_update_spheres failed (" + s->failed_update +
+        return fail(RRT_E_INVALID, "the scene is invalid since a change of it failed (" + s->failed_update +
                                        "); a later update that succeeds makes it valid again");
     if (int rc = check_tile_shape(t)) return rc;
     const uint32_t sq = s->base.sqrt_spp;
@@ -1419,32 +1428,8 @@ int32_t rrt_device_count(int32_t *count) {
 // D = dot(normal, q), w = n * (1/dot(n, n)); Vec3 / f64 is `(1/rhs) * v`, vec3.rs:142-148), rounded
 // to the device record. Scene creation and rrt_testing_device_ops form their records here.
 // form_gquad64 keeps the f64 values unrounded (the f64 kernel's book-2 class, GQuad64).
-static rrt::GQuad64 form_gquad64(const RrtQuad &qd) {
-    const D3 q = d3(qd.q[0], qd.q[1], qd.q[2]), u = d3(qd.u[0], qd.u[1], qd.u[2]), v = d3(qd.v[0], qd.v[1], qd.v[2]);
-    const D3 n = cross(u, v);
-    const double nn = n.x * n.x + n.y * n.y + n.z * n.z;
-    const D3 normal = n * (1.0 / std::sqrt(nn));
-    const double dd = normal.x * q.x + normal.y * q.y + normal.z * q.z;
-    const D3 w = n * (1.0 / nn);
-    rrt::GQuad64 g;
-    const D3 *src[5] = {&q, &u, &v, &normal, &w};
-    double *dst[5] = {g.q, g.u, g.v, g.n, g.w};
-    for (int k = 0; k < 5; ++k) dst[k][0] = src[k]->x, dst[k][1] = src[k]->y, dst[k][2] = src[k]->z;
-    g.D = dd;
-    return g;
-}
-static rrt::GQuad form_gquad(const RrtQuad &qd) {
-    const rrt::GQuad64 g64 = form_gquad64(qd);
-    const D3 normal = d3(g64.n[0], g64.n[1], g64.n[2]), w = d3(g64.w[0], g64.w[1], g64.w[2]);
-    const double dd = g64.D;
-    rrt::GQuad g;
-    g.q = make_float4(qd.q[0], qd.q[1], qd.q[2], (float)dd);
-    g.u = make_float4(qd.u[0], qd.u[1], qd.u[2], 0.0f);
-    g.v = make_float4(qd.v[0], qd.v[1], qd.v[2], 0.0f);
-    g.n = make_float4((float)normal.x, (float)normal.y, (float)normal.z, 0.0f);
-    g.w = make_float4((float)w.x, (float)w.y, (float)w.z, 0.0f);
-    return g;
-}
+static rrt::GQuad64 form_gquad64(const RrtQuad &qd) { return rrt::quad_record64(qd.q, qd.u, qd.v); }
+static rrt::GQuad form_gquad(const RrtQuad &qd) { return rrt::quad_record32(qd.q, qd.u, qd.v); }
 
 // The book-3 light list as device records: a sphere as it is (radius max(r, 0)), a quad as its area
 // |u x v| (quad.rs:28, f64 rounded) and the index first_quad + k of its k-th entry in `light_quads`,
@@ -1455,15 +1440,10 @@ static std::vector<rrt::GLight> form_glights(const RrtLight *lights, uint32_t n_
     std::vector<rrt::GLight> glights(n_lights);
     for (uint32_t l = 0; l < glights.size(); ++l) {
         const RrtLight &L = lights[l];
-        rrt::GLight &g = glights[l];
-        g.kind = L.kind;
-        g.sphere = make_float4(L.a[0], L.a[1], L.a[2], std::max(L.a[3], 0.0f));
+        glights[l] = rrt::light_record(L, first_quad + (uint32_t)light_quads.size());
         if (L.kind == RRT_LIGHT_QUAD) {
             RrtQuad q{};
             for (int i = 0; i < 3; ++i) q.q[i] = L.a[i], q.u[i] = L.u[i], q.v[i] = L.v[i];
-            g.quad = first_quad + (uint32_t)light_quads.size();
-            const D3 n = cross(d3(L.u[0], L.u[1], L.u[2]), d3(L.v[0], L.v[1], L.v[2]));
-            g.area = (float)std::sqrt(n.x * n.x + n.y * n.y + n.z * n.z);  // quad.rs:28 area = |n|
             light_quads.push_back(q);
         }
     }
@@ -1879,6 +1859,12 @@ static int32_t scene_create(const RrtCamera *cam, const RrtSphere *spheres, uint
     s->n_spheres = n_spheres;
     s->n_materials = n_materials;
     s->max_leaf = max_leaf;
+    s->n_bquads = ex.n_bquads;
+    s->n_gquads = (uint32_t)gquads.size();
+    s->mat_kinds.resize(n_materials);
+    for (uint32_t i = 0; i < n_materials; ++i) s->mat_kinds[i] = materials[i].kind;
+    s->light_kinds.resize(glights.size());
+    for (uint32_t l = 0; l < glights.size(); ++l) s->light_kinds[l] = glights[l].kind;
     if (built_on_device) s->builder = builder.release();
     int rc = RRT_OK;
     do {
@@ -1898,8 +1884,14 @@ static int32_t scene_create(const RrtCamera *cam, const RrtSphere *spheres, uint
             for (uint32_t i = 0; i < n_prims; ++i) diel[i] = material_diel64(prim_mtl[i]);
             if ((rc = upload(&s->d_prim_diel64, diel.data(), diel.size(), "dielectric constants"))) break;
         }
-        // rrt_scene_update_spheres re-forms the tables above on the device, from these in source order
-        if (built_on_device && !n_media && !book3) {
+        // rrt_scene_update_spheres and rrt_scene_update_geometry re-form the tables above on the device,
+        // from these in source order
+        if (built_on_device && !n_media) {
+            if (!glights.empty()) {  // each light quad's GQuad, at its fixed index after the scene's quads
+                std::vector<uint32_t> light_quad(glights.size());
+                for (uint32_t l = 0; l < glights.size(); ++l) light_quad[l] = glights[l].quad;
+                if ((rc = upload(&s->d_light_quad, light_quad.data(), light_quad.size(), "light quad indices"))) break;
+            }
             if ((rc = upload(&s->d_src_mats, mats.data(), mats.size(), "material table"))) break;
             if (f64) {
                 std::vector<double4> mat_diel(n_materials);
@@ -2111,8 +2103,9 @@ int32_t rrt_scene_set_camera(RrtScene *scene, const RrtCamera *cam) {
 namespace {
 
 // What rrt_scene_update_spheres and rrt_scene_refit_spheres refuse before any device call.
+// geometry: the caller is a geometry entry, which brings a book-3 scene's lights along.
 int check_sphere_change(const RrtScene *s, const std::string &fn, const RrtSphere *spheres, uint32_t n_spheres,
-                        const float *motion, bool &has_motion) {
+                        const float *motion, bool &has_motion, bool geometry = false) {
     if (!s) return fail(RRT_E_INVALID, fn + "null scene");
     if (n_spheres != s->n_spheres)
         return fail(RRT_E_INVALID, fn + "n_spheres is " + std::to_string(n_spheres) + ", the scene's is " +
@@ -2124,7 +2117,7 @@ int check_sphere_change(const RrtScene *s, const std::string &fn, const RrtSpher
     if (s->base.n_media)
         return fail(RRT_E_INVALID, fn + "scenes with constant media are not updated (which media are unbounded "
                                         "depends on every sphere)");
-    if (s->base.flags & RRT_FLAG_BOOK3)
+    if (!geometry && (s->base.flags & RRT_FLAG_BOOK3))
         return fail(RRT_E_INVALID, fn + "RRT_FLAG_BOOK3 scenes are not updated (their light list restates geometry)");
     if (!s->builder)
         return fail(RRT_E_INVALID, fn + "a tree of fewer than 2 primitives is the root-leaf form the host builder writes");
@@ -2203,15 +2196,81 @@ void sphere32_recheck(RrtScene *s, const RrtSphere *spheres, uint32_t n_spheres)
     s->base.sphere32 = sphere32_flag(in);
 }
 
-}  // namespace
+// What a geometry entry (rrt_scene_update_geometry, rrt_scene_refit_geometry) changes beyond the
+// spheres; all null for the sphere entries. quads_in32: the new quads' prim_cr rows pass the sphere32
+// range check (scene creation's quads_in_sphere32, from the caller's rows through rrt_quad_form.h).
+struct GeometryChange {
+    const RrtQuad *quads = nullptr;
+    const RrtLight *lights = nullptr;
+    bool quads_in32 = true;
+};
 
-int32_t rrt_scene_update_spheres(RrtScene *scene, const RrtSphere *spheres, uint32_t n_spheres, const float *motion,
-                                 void *stream) {
-    const std::string fn = "rrt_scene_update_spheres: ";
-    RrtScene *s = scene;
-    bool has_motion = false;
-    if (int rc = check_sphere_change(s, fn, spheres, n_spheres, motion, has_motion)) return rc;
+// What the geometry entries refuse before any device call: check_sphere_change's list but for
+// RRT_FLAG_BOOK3, then the quads' and lights' own.
+int check_geometry_change(const RrtScene *s, const std::string &fn, const RrtSceneGeometry *g, bool &has_motion,
+                          GeometryChange &out) {
+    if (!s) return fail(RRT_E_INVALID, fn + "null scene");
+    if (!g) return fail(RRT_E_INVALID, fn + "null geometry");
+    if (int rc = check_sphere_change(s, fn, g->spheres, g->n_spheres, g->sphere_motion, has_motion, true)) return rc;
+    if (s->n_bquads)
+        return fail(RRT_E_INVALID, fn + "scenes with boundary quads are not updated (they bound constant media)");
+    const uint32_t n_quads = s->base.n_quads, n_lights = s->base.n_lights;
+    if (g->quads) {
+        if (g->n_quads != n_quads)
+            return fail(RRT_E_INVALID, fn + "n_quads is " + std::to_string(g->n_quads) + ", the scene's is " +
+                                           std::to_string(n_quads) + " (the primitive count is fixed at creation)");
+        for (uint32_t j = 0; j < n_quads; ++j) {
+            const RrtQuad &qd = g->quads[j];
+            const std::string what = fn + "quad " + std::to_string(j);
+            if (qd.material_index >= s->n_materials) return fail(RRT_E_INVALID, what + " material_index out of range");
+            if (s->mat_kinds[qd.material_index] == RRT_MAT_TEXTURED_LAMBERTIAN)
+                return fail(RRT_E_INVALID, what + ": image textures on quads are not supported");
+            if (!rrt::quad_is_regular(qd.q, qd.u, qd.v))
+                return fail(RRT_E_INVALID, what + " is degenerate: q, u and v must be finite and u x v must have a "
+                                                  "finite, non-zero length");
+            out.quads_in32 = out.quads_in32 && row_in_sphere32(qd.q[0], qd.q[1], qd.q[2], -(float)(j + 1));
+        }
+        out.quads = g->quads;
+    }
+    if (s->base.flags & RRT_FLAG_BOOK3) {
+        if (!g->lights)
+            return fail(RRT_E_INVALID, fn + "lights are missing: an RRT_FLAG_BOOK3 scene's light list restates geometry "
+                                            "and is given with it");
+        if (g->n_lights != n_lights)
+            return fail(RRT_E_INVALID, fn + "n_lights is " + std::to_string(g->n_lights) + ", the scene's is " +
+                                           std::to_string(n_lights) + " (the light count is fixed at creation)");
+        for (uint32_t l = 0; l < n_lights; ++l) {
+            const RrtLight &L = g->lights[l];
+            const std::string what = fn + "light " + std::to_string(l);
+            if (L.kind != s->light_kinds[l])
+                return fail(RRT_E_INVALID, what + ": kind " + std::to_string(L.kind) + " differs from the scene's entry (" +
+                                               std::to_string(s->light_kinds[l]) + ")");
+            if (L.kind == RRT_LIGHT_QUAD && !rrt::quad_is_regular(L.a, L.u, L.v))
+                return fail(RRT_E_INVALID, what + " is a degenerate quad: a, u and v must be finite and u x v must have "
+                                                  "a finite, non-zero length");
+        }
+        out.lights = g->lights;
+    } else if (g->lights || g->n_lights) {
+        return fail(RRT_E_INVALID, fn + "lights are given, but the scene was not created with RRT_FLAG_BOOK3");
+    }
+    return RRT_OK;
+}
 
+// The first geometry change that brings quads (lights): the device staging of those rows.
+int ensure_geometry_buffers(RrtScene *s, const GeometryChange &g, uint64_t &own_allocs) {
+    if (g.quads && s->base.n_quads && !s->d_src_quads) {
+        ++own_allocs;
+        HIP_TRY(hipMalloc((void **)&s->d_src_quads, (size_t)s->base.n_quads * sizeof(RrtQuad)), "hipMalloc quads");
+    }
+    if (g.lights && !s->d_src_lights) {
+        ++own_allocs;
+        HIP_TRY(hipMalloc((void **)&s->d_src_lights, (size_t)s->base.n_lights * sizeof(RrtLight)), "hipMalloc lights");
+    }
+    return RRT_OK;
+}
+
+int32_t update_scene(RrtScene *s, const std::string &fn, const RrtSphere *spheres, uint32_t n_spheres, const float *motion,
+                     bool has_motion, const GeometryChange &g, void *stream) {
     // ---- device work, on the default stream after `stream` (and a refit still in flight) has
     // drained. The first update's allocations fail without touching the scene; a failure after them
     // leaves it invalid (broke).
@@ -2223,17 +2282,25 @@ int32_t rrt_scene_update_spheres(RrtScene *scene, const RrtSphere *spheres, uint
     const uint64_t allocs_before = s->builder->allocations();
     uint64_t own_allocs = 0;
     if (int rc = ensure_change_buffers(s, fn, own_allocs)) return rc;
+    if (int rc = ensure_geometry_buffers(s, g, own_allocs)) return rc;
     auto broke = [&](int code, const std::string &msg) {
-        s->failed_update = msg;
+        s->failed_update = fn + msg;
         return fail(code, fn + msg);
     };
     if (n_spheres && hipMemcpy(s->d_src_spheres, spheres, (size_t)n_spheres * sizeof(RrtSphere), hipMemcpyHostToDevice) != hipSuccess)
         return broke(RRT_E_HIP, "copying the spheres failed");
     if (has_motion && hipMemcpy(s->d_src_motion, motion, (size_t)n_spheres * 4 * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
         return broke(RRT_E_HIP, "copying the motion rows failed");
+    const uint32_t n_quads = g.quads ? p.n_quads : 0u, n_lights = g.lights ? p.n_lights : 0u;
+    if (n_quads && hipMemcpy(s->d_src_quads, g.quads, (size_t)n_quads * sizeof(RrtQuad), hipMemcpyHostToDevice) != hipSuccess)
+        return broke(RRT_E_HIP, "copying the quads failed");
+    if (n_lights && hipMemcpy(s->d_src_lights, g.lights, (size_t)n_lights * sizeof(RrtLight), hipMemcpyHostToDevice) != hipSuccess)
+        return broke(RRT_E_HIP, "copying the lights failed");
     const float *d_motion = has_motion ? s->d_src_motion : nullptr;
     if (rrt::launch_sphere_boxes(n_spheres, s->d_src_spheres, d_motion, s->builder->device_boxes()) != hipSuccess)
         return broke(RRT_E_HIP, "the sphere-box launch failed");
+    if (rrt::launch_quad_boxes(n_quads, s->d_src_quads, s->builder->device_boxes() + n_spheres) != hipSuccess)
+        return broke(RRT_E_HIP, "the quad-box launch failed");
     bvhb::Summary sum{};
     uint32_t stride = 0, leaf_param = s->max_leaf, levels = 0;
     if (int rc = bvh_device_shape(*s->builder, n_prims, s->max_leaf, s->book2, s->f64, sum, stride, leaf_param, levels))
@@ -2243,7 +2310,14 @@ int32_t rrt_scene_update_spheres(RrtScene *scene, const RrtSphere *spheres, uint
     const size_t node_bytes = (size_t)fb.n_nodes * fb.stride;
     if (s->builder->emit_into(stride, s->d_nodes, s->nodes_cap, s->order.data()) != hipSuccess)
         return broke(RRT_E_HIP, "device BVH: emit failed");
+    // the quads' records, rows and material indices, then the lights with their GQuads; the leaf
+    // tables read the rows
+    if (rrt::launch_quad_records(n_quads, s->d_src_quads, s->d_quads, s->d_quads64, s->d_quad_rows, s->d_quad_mat) != hipSuccess)
+        return broke(RRT_E_HIP, "the quad-record launch failed");
+    if (rrt::launch_lights(n_lights, s->d_src_lights, s->d_light_quad, s->d_lights, s->d_quads) != hipSuccess)
+        return broke(RRT_E_HIP, "the light launch failed");
     if (rrt::launch_leaf_tables(leaf_tables_of(s, d_motion)) != hipSuccess) return broke(RRT_E_HIP, "the leaf-table launch failed");
+    if (s->f64 && g.quads) s->quads_in_sphere32 = g.quads_in32;  // the quads' part, from the caller's rows
     if (s->f64) sphere32_recheck(s, spheres, n_spheres);
     tree_params(p, fb, node_bytes, s->book2);
     if (int rc = plan_check(p)) return broke(rc, g_err);
@@ -2254,6 +2328,24 @@ int32_t rrt_scene_update_spheres(RrtScene *scene, const RrtSphere *spheres, uint
     s->last_update_allocs = own_allocs + (s->builder->allocations() - allocs_before);
     s->last_update_levels = levels;
     return RRT_OK;
+}
+
+}  // namespace
+
+int32_t rrt_scene_update_spheres(RrtScene *scene, const RrtSphere *spheres, uint32_t n_spheres, const float *motion,
+                                 void *stream) {
+    const std::string fn = "rrt_scene_update_spheres: ";
+    bool has_motion = false;
+    if (int rc = check_sphere_change(scene, fn, spheres, n_spheres, motion, has_motion)) return rc;
+    return update_scene(scene, fn, spheres, n_spheres, motion, has_motion, GeometryChange{}, stream);
+}
+
+int32_t rrt_scene_update_geometry(RrtScene *scene, const RrtSceneGeometry *geometry, void *stream) {
+    const std::string fn = "rrt_scene_update_geometry: ";
+    bool has_motion = false;
+    GeometryChange g;
+    if (int rc = check_geometry_change(scene, fn, geometry, has_motion, g)) return rc;
+    return update_scene(scene, fn, geometry->spheres, geometry->n_spheres, geometry->sphere_motion, has_motion, g, stream);
 }
 
 int32_t rrt_build_bvh_binned(const RrtSphere *spheres, uint32_t n_spheres, const RrtSceneExt *ext, uint32_t max_leaf,
@@ -2297,14 +2389,12 @@ int32_t rrt_build_bvh_binned(const RrtSphere *spheres, uint32_t n_spheres, const
 
 // The refit: everything after the checks is enqueued on `stream`; no host read, no wait for the
 // device (but for the staging buffer of the refit before, which its copy has long left).
-int32_t rrt_scene_refit_spheres(RrtScene *scene, const RrtSphere *spheres, uint32_t n_spheres, const float *motion,
-                                void *stream) {
-    const std::string fn = "rrt_scene_refit_spheres: ";
-    RrtScene *s = scene;
-    bool has_motion = false;
-    if (int rc = check_sphere_change(s, fn, spheres, n_spheres, motion, has_motion)) return rc;
+// A geometry refit stages the quad and light rows behind the spheres' and motion's; its staging
+// buffer is sized for all four at once, whichever of them the call brings.
+static int32_t refit_scene(RrtScene *s, const std::string &fn, const RrtSphere *spheres, uint32_t n_spheres, const float *motion,
+                           bool has_motion, const GeometryChange &g, bool geometry, void *stream) {
     if (!s->failed_update.empty())
-        return fail(RRT_E_INVALID, fn + "the scene is invalid since rrt_scene_update_spheres failed (" + s->failed_update +
+        return fail(RRT_E_INVALID, fn + "the scene is invalid since a change of it failed (" + s->failed_update +
                                        "); only an update that succeeds makes it valid again");
     if (!s->builder->refit_form_ok())
         return fail(RRT_E_INVALID, fn + "rrt_testing_refit_form(1): the single-workgroup form takes trees of at most " +
@@ -2319,16 +2409,28 @@ int32_t rrt_scene_refit_spheres(RrtScene *scene, const RrtSphere *spheres, uint3
         HIP_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
         if (int rc = ensure_change_buffers(s, fn, own_allocs)) return rc;
     }
-    if (!s->h_stage) {  // the first refit
+    if (int rc = ensure_geometry_buffers(s, g, own_allocs)) return rc;
+    const uint32_t n_quads = g.quads ? s->base.n_quads : 0u, n_lights = g.lights ? s->base.n_lights : 0u;
+    const size_t quad_bytes = (size_t)n_quads * sizeof(RrtQuad), light_bytes = (size_t)n_lights * sizeof(RrtLight);
+    const size_t quads_at = sphere_bytes + motion_bytes, lights_at = quads_at + (size_t)s->base.n_quads * sizeof(RrtQuad);
+    const size_t stage_need = std::max<size_t>(
+        geometry ? lights_at + (size_t)s->base.n_lights * sizeof(RrtLight) : sphere_bytes + motion_bytes, 16);
+    if (s->stage_cap < stage_need) {  // the first refit, or the first geometry refit after sphere refits
+        if (s->h_stage) {
+            if (s->n_refits) HIP_TRY(hipEventSynchronize(s->ev_staged), "hipEventSynchronize");
+            (void)hipHostFree(s->h_stage);
+            s->h_stage = nullptr;
+            s->stage_cap = 0;
+        }
         ++own_allocs;
-        HIP_TRY(hipHostMalloc((void **)&s->h_stage, std::max<size_t>(sphere_bytes + motion_bytes, 16), hipHostMallocDefault),
-                "hipHostMalloc staging");
+        HIP_TRY(hipHostMalloc((void **)&s->h_stage, stage_need, hipHostMallocDefault), "hipHostMalloc staging");
+        s->stage_cap = stage_need;
     }
     if (!s->ev_staged) HIP_TRY(hipEventCreateWithFlags(&s->ev_staged, hipEventDisableTiming), "hipEventCreate");
     if (!s->ev_refit_done) HIP_TRY(hipEventCreateWithFlags(&s->ev_refit_done, hipEventDisableTiming), "hipEventCreate");
     if (s->builder->reserve_refit() != hipSuccess) return fail(RRT_E_NOMEM, fn + "reserving the refit's workspace failed");
     auto broke = [&](int code, const std::string &msg) {
-        s->failed_update = msg;
+        s->failed_update = fn + msg;
         return fail(code, fn + msg);
     };
     if (s->n_refits && hipEventSynchronize(s->ev_staged) != hipSuccess) return broke(RRT_E_HIP, "waiting for the staging buffer failed");
@@ -2338,21 +2440,50 @@ int32_t rrt_scene_refit_spheres(RrtScene *scene, const RrtSphere *spheres, uint3
         return broke(RRT_E_HIP, "copying the spheres failed");
     if (has_motion && hipMemcpyAsync(s->d_src_motion, s->h_stage + sphere_bytes, motion_bytes, hipMemcpyHostToDevice, st) != hipSuccess)
         return broke(RRT_E_HIP, "copying the motion rows failed");
+    if (quad_bytes) std::memcpy(s->h_stage + quads_at, g.quads, quad_bytes);
+    if (light_bytes) std::memcpy(s->h_stage + lights_at, g.lights, light_bytes);
+    if (quad_bytes && hipMemcpyAsync(s->d_src_quads, s->h_stage + quads_at, quad_bytes, hipMemcpyHostToDevice, st) != hipSuccess)
+        return broke(RRT_E_HIP, "copying the quads failed");
+    if (light_bytes && hipMemcpyAsync(s->d_src_lights, s->h_stage + lights_at, light_bytes, hipMemcpyHostToDevice, st) != hipSuccess)
+        return broke(RRT_E_HIP, "copying the lights failed");
     if (hipEventRecord(s->ev_staged, st) != hipSuccess) return broke(RRT_E_HIP, "hipEventRecord failed");
     const float *d_motion = has_motion ? s->d_src_motion : nullptr;
     if (rrt::launch_sphere_boxes(n_spheres, s->d_src_spheres, d_motion, s->builder->device_boxes(), st) != hipSuccess)
         return broke(RRT_E_HIP, "the sphere-box launch failed");
+    if (rrt::launch_quad_boxes(n_quads, s->d_src_quads, s->builder->device_boxes() + n_spheres, st) != hipSuccess)
+        return broke(RRT_E_HIP, "the quad-box launch failed");
     if (s->builder->refit(st) != hipSuccess) return broke(RRT_E_HIP, "device BVH: refit failed");
     if (s->builder->emit_refit(s->info.node_stride, s->d_nodes, s->nodes_cap, st) != hipSuccess)
         return broke(RRT_E_HIP, "device BVH: emit failed");
+    if (rrt::launch_quad_records(n_quads, s->d_src_quads, s->d_quads, s->d_quads64, s->d_quad_rows, s->d_quad_mat, st) != hipSuccess)
+        return broke(RRT_E_HIP, "the quad-record launch failed");
+    if (rrt::launch_lights(n_lights, s->d_src_lights, s->d_light_quad, s->d_lights, s->d_quads, st) != hipSuccess)
+        return broke(RRT_E_HIP, "the light launch failed");
     if (rrt::launch_leaf_tables(leaf_tables_of(s, d_motion), st) != hipSuccess) return broke(RRT_E_HIP, "the leaf-table launch failed");
     if (hipEventRecord(s->ev_refit_done, st) != hipSuccess) return broke(RRT_E_HIP, "hipEventRecord failed");
+    if (s->f64 && g.quads) s->quads_in_sphere32 = g.quads_in32;  // the quads' part, from the caller's rows
     if (s->f64) sphere32_recheck(s, spheres, n_spheres);
     s->n_refits++;
     s->last_refit_allocs = own_allocs + (s->builder->allocations() - allocs_before);
-    s->last_refit_launches = (n_spheres ? 1u : 0u) + s->builder->refit_launches() + 2u;
+    s->last_refit_launches = (n_spheres ? 1u : 0u) + (n_quads ? 2u : 0u) + (n_lights ? 1u : 0u) + s->builder->refit_launches() + 2u;
     s->last_refit_form = s->builder->refit_form();
     return RRT_OK;
+}
+
+int32_t rrt_scene_refit_spheres(RrtScene *scene, const RrtSphere *spheres, uint32_t n_spheres, const float *motion,
+                                void *stream) {
+    const std::string fn = "rrt_scene_refit_spheres: ";
+    bool has_motion = false;
+    if (int rc = check_sphere_change(scene, fn, spheres, n_spheres, motion, has_motion)) return rc;
+    return refit_scene(scene, fn, spheres, n_spheres, motion, has_motion, GeometryChange{}, false, stream);
+}
+
+int32_t rrt_scene_refit_geometry(RrtScene *scene, const RrtSceneGeometry *geometry, void *stream) {
+    const std::string fn = "rrt_scene_refit_geometry: ";
+    bool has_motion = false;
+    GeometryChange g;
+    if (int rc = check_geometry_change(scene, fn, geometry, has_motion, g)) return rc;
+    return refit_scene(scene, fn, geometry->spheres, geometry->n_spheres, geometry->sphere_motion, has_motion, g, true, stream);
 }
 
 int32_t rrt_scene_tree_cost(RrtScene *scene, RrtTreeCost *out) {
@@ -2371,6 +2502,14 @@ int32_t rrt_refit_bvh_binned(const RrtSphere *built_spheres, uint32_t n_spheres,
                              uint32_t max_leaf, double node_cost, uint32_t node_stride, const RrtSphere *new_spheres,
                              const float *new_motion, void *nodes_out, size_t nodes_cap, uint32_t *prim_order_out,
                              RrtBvhInfo *info, double *sah_out) {
+    return rrt_refit_bvh_binned_ex(built_spheres, n_spheres, built_ext, max_leaf, node_cost, node_stride, new_spheres,
+                                   new_motion, nullptr, nodes_out, nodes_cap, prim_order_out, info, sah_out);
+}
+
+int32_t rrt_refit_bvh_binned_ex(const RrtSphere *built_spheres, uint32_t n_spheres, const RrtSceneExt *built_ext,
+                                uint32_t max_leaf, double node_cost, uint32_t node_stride, const RrtSphere *new_spheres,
+                                const float *new_motion, const RrtQuad *new_quads, void *nodes_out, size_t nodes_cap,
+                                uint32_t *prim_order_out, RrtBvhInfo *info, double *sah_out) {
     if (n_spheres && (!built_spheres || !new_spheres)) return fail(RRT_E_INVALID, "null spheres");
     const ExtView ex(built_ext);
     for (uint32_t m = 0; m < ex.n_media; ++m)
@@ -2384,6 +2523,8 @@ int32_t rrt_refit_bvh_binned(const RrtSphere *built_spheres, uint32_t n_spheres,
     BinnedTree bt = build_binned_host(in, max_leaf, node_cost);
     for (uint32_t i = 0; i < n_spheres; ++i)
         in.boxes[i] = rrt::sphere_box(new_spheres[i].center_radius, new_motion ? new_motion + 4 * (size_t)i : nullptr);
+    for (uint32_t j = 0; new_quads && j < ex.n_quads; ++j)
+        in.boxes[n_spheres + j] = rrt::quad_box(new_quads[j].q, new_quads[j].u, new_quads[j].v);
     bvhb::refit_raw(bt.raw.data(), bt.sum.n_nodes, bt.objs.data(), in.boxes.data());
     double root_box[6];
     bvhb::root_box_of(bt.raw[0], root_box);
@@ -2575,6 +2716,21 @@ extern "C" int32_t rrt_testing_sphere_boxes(const RrtSphere *spheres, uint32_t n
     return RRT_OK;
 }
 
+// Test support: the host compilation of rrt_quad_form.h (the device's: k_quad_boxes, k_quad_records).
+extern "C" int32_t rrt_testing_quad_records(const RrtQuad *quads, uint32_t n_quads, double *boxes6, void *gquad, void *gquad64) {
+    if (n_quads && !quads) return fail(RRT_E_INVALID, "rrt_testing_quad_records: null quads");
+    for (uint32_t j = 0; j < n_quads; ++j) {
+        const RrtQuad &qd = quads[j];
+        if (boxes6) {
+            const bvhb::Box6 b = rrt::quad_box(qd.q, qd.u, qd.v);
+            for (int a = 0; a < 3; ++a) boxes6[6 * (size_t)j + a] = b.mn[a], boxes6[6 * (size_t)j + 3 + a] = b.mx[a];
+        }
+        if (gquad) static_cast<rrt::GQuad *>(gquad)[j] = rrt::quad_record32(qd.q, qd.u, qd.v);
+        if (gquad64) static_cast<rrt::GQuad64 *>(gquad64)[j] = rrt::quad_record64(qd.q, qd.u, qd.v);
+    }
+    return RRT_OK;
+}
+
 // Test support: one of the scene's device tables, copied back.
 extern "C" int32_t rrt_testing_scene_read_table(RrtScene *scene, uint32_t what, void *out, size_t cap, size_t *bytes_out) {
     if (!scene || !bytes_out) return fail(RRT_E_INVALID, "rrt_testing_scene_read_table: null scene or bytes_out");
@@ -2590,6 +2746,10 @@ extern "C" int32_t rrt_testing_scene_read_table(RrtScene *scene, uint32_t what, 
     case RRT_TABLE_PRIM_MOTION: src = scene->d_prim_motion, bytes = n * sizeof(float4); break;
     case RRT_TABLE_PRIM_INV_R64: src = scene->d_prim_inv_r64, bytes = n * sizeof(double); break;
     case RRT_TABLE_PRIM_DIEL64: src = scene->d_prim_diel64, bytes = n * sizeof(double4); break;
+    case RRT_TABLE_GQUADS: src = scene->d_quads, bytes = (size_t)scene->n_gquads * sizeof(rrt::GQuad); break;
+    case RRT_TABLE_GQUADS64: src = scene->d_quads64, bytes = (size_t)scene->base.n_quads * sizeof(rrt::GQuad64); break;
+    case RRT_TABLE_QUAD_ROWS: src = scene->d_quad_rows, bytes = (size_t)scene->base.n_quads * 2 * sizeof(float4); break;
+    case RRT_TABLE_GLIGHTS: src = scene->d_lights, bytes = (size_t)scene->base.n_lights * sizeof(rrt::GLight); break;
     default: return fail(RRT_E_INVALID, "rrt_testing_scene_read_table: unknown table");
     }
     if (!src) bytes = 0;  // a table this scene does not hold

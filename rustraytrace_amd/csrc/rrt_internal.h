@@ -502,6 +502,19 @@ struct LeafTables {
 hipError_t launch_sphere_boxes(uint32_t n, const void *d_spheres, const float *d_motion, void *d_boxes,
                                hipStream_t stream = nullptr);
 hipError_t launch_leaf_tables(const LeafTables &t, hipStream_t stream = nullptr);
+// rrt_scene_update_geometry / rrt_scene_refit_geometry (rrt_quad_form.h on the device), one lane per row:
+//   launch_quad_boxes    quad j's padded f64 box into boxes[j] (the caller passes the builder's
+//                        boxes + n_spheres); quads = RrtQuad records
+//   launch_quad_records  quad j's GQuad into gquads[j] or GQuad64 into gquads64[j] (either may be
+//                        null), its two leaf-table rows into quad_rows[2j, 2j + 1] and its
+//                        material index into quad_mat[j]
+//   launch_lights        light l's GLight into glights[l] and, for a quad light, its GQuad into
+//                        gquads[light_quad[l]]; lights = RrtLight records
+hipError_t launch_quad_boxes(uint32_t n, const void *d_quads, void *d_boxes, hipStream_t stream = nullptr);
+hipError_t launch_quad_records(uint32_t n, const void *d_quads, GQuad *gquads, GQuad64 *gquads64, float4 *quad_rows,
+                               uint32_t *quad_mat, hipStream_t stream = nullptr);
+hipError_t launch_lights(uint32_t n, const void *d_lights, const uint32_t *light_quad, GLight *glights, GQuad *gquads,
+                         hipStream_t stream = nullptr);
 // Test support (rrt_testing_refit_form): force the refit's per-level launches (0) or its single
 // workgroup (1); -1: the automatic choice. False for another value.
 bool set_refit_form(int form);

@@ -3,8 +3,12 @@
 // kernels restate what scene creation computes on the host (rrt_host.cpp prim_boxes and
 // prim_table_row) so that an updated scene holds the bytes of a freshly created one. One lane per
 // row, plain vector stores; nothing here is worth tuning (a 10^5-sphere scene moves ~10 MB).
+// rrt_scene_update_geometry and rrt_scene_refit_geometry add the quads and the book-3 lights: their
+// boxes, GQuad / GQuad64 records, leaf-table rows and GLight records, all from rrt_quad_form.h, the
+// definition scene creation itself calls.
 #include "rrt_internal.h"
 #include "rrt_sphere_box.h"
+#include "rrt_quad_form.h"
 #include "../../include/rrt_hip.h"
 
 namespace rrt {
@@ -75,7 +79,73 @@ __global__ __launch_bounds__(kBlk) void k_leaf_tables(LeafTables t) {
     }
 }
 
+// ---- quads and book-3 lights (rrt_scene_update_geometry, rrt_scene_refit_geometry) ---------------
+static_assert(sizeof(RrtQuad) == 64 && sizeof(RrtLight) == 64, "RrtQuad and RrtLight are 64 B");
+
+// a row's q, u, v (or a light's a, u, v) by three 16-B loads from 16-B aligned records
+struct Quv {
+    float q[3], u[3], v[3];
+};
+__device__ __forceinline__ Quv load_quv(const float *q4) {
+    const float4 q = reinterpret_cast<const float4 *>(q4)[0], u = reinterpret_cast<const float4 *>(q4)[1],
+                 v = reinterpret_cast<const float4 *>(q4)[2];
+    return Quv{{q.x, q.y, q.z}, {u.x, u.y, u.z}, {v.x, v.y, v.z}};
+}
+
+__global__ __launch_bounds__(kBlk) void k_quad_boxes(uint32_t n, const RrtQuad *quads, bvhb::Box6 *boxes) {
+    const uint32_t j = blockIdx.x * kBlk + threadIdx.x;
+    if (j >= n) return;
+    const Quv r = load_quv(quads[j].q);
+    boxes[j] = quad_box(r.q, r.u, r.v);
+}
+
+__global__ __launch_bounds__(kBlk) void k_quad_records(uint32_t n, const RrtQuad *quads, GQuad *gquads, GQuad64 *gquads64,
+                                                       float4 *quad_rows, uint32_t *quad_mat) {
+    const uint32_t j = blockIdx.x * kBlk + threadIdx.x;
+    if (j >= n) return;
+    const Quv r = load_quv(quads[j].q);
+    const GQuad g = quad_record32(r.q, r.u, r.v);
+    if (gquads) gquads[j] = g;
+    if (gquads64) gquads64[j] = quad_record64(r.q, r.u, r.v);
+    quad_rows[2u * j] = quad_row_cr(g, j);
+    quad_rows[2u * j + 1u] = quad_row_plane(g);
+    quad_mat[j] = quads[j].material_index;
+}
+
+__global__ __launch_bounds__(kBlk) void k_lights(uint32_t n, const RrtLight *lights, const uint32_t *light_quad,
+                                                 GLight *glights, GQuad *gquads) {
+    const uint32_t l = blockIdx.x * kBlk + threadIdx.x;
+    if (l >= n) return;
+    const RrtLight L = lights[l];
+    const uint32_t at = light_quad[l];
+    glights[l] = light_record(L, at);
+    if (L.kind == RRT_LIGHT_QUAD) gquads[at] = quad_record32(L.a, L.u, L.v);
+}
+
 }  // namespace
+
+hipError_t launch_quad_boxes(uint32_t n, const void *d_quads, void *d_boxes, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_quad_boxes, dim3((n + kBlk - 1) / kBlk), dim3(kBlk), 0, stream, n,
+                       reinterpret_cast<const RrtQuad *>(d_quads), reinterpret_cast<bvhb::Box6 *>(d_boxes));
+    return hipGetLastError();
+}
+
+hipError_t launch_quad_records(uint32_t n, const void *d_quads, GQuad *gquads, GQuad64 *gquads64, float4 *quad_rows,
+                               uint32_t *quad_mat, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_quad_records, dim3((n + kBlk - 1) / kBlk), dim3(kBlk), 0, stream, n,
+                       reinterpret_cast<const RrtQuad *>(d_quads), gquads, gquads64, quad_rows, quad_mat);
+    return hipGetLastError();
+}
+
+hipError_t launch_lights(uint32_t n, const void *d_lights, const uint32_t *light_quad, GLight *glights, GQuad *gquads,
+                         hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_lights, dim3((n + kBlk - 1) / kBlk), dim3(kBlk), 0, stream, n,
+                       reinterpret_cast<const RrtLight *>(d_lights), light_quad, glights, gquads);
+    return hipGetLastError();
+}
 
 hipError_t launch_sphere_boxes(uint32_t n, const void *d_spheres, const float *d_motion, void *d_boxes, hipStream_t stream) {
     if (n == 0) return hipSuccess;

@@ -332,10 +332,12 @@ def build_bvh_binned(scene: SceneData, max_leaf: int, node_cost: float, node_str
     return nodes, order[:n_prims], info.as_dict()
 
 
-def refit_bvh_binned(built_scene: SceneData, new_spheres, new_motion, max_leaf: int, node_cost: float, node_stride: int):
-    """rrt_refit_bvh_binned (host only): build_bvh_binned's tree of `built_scene` with its boxes
-    recomputed over new_spheres and new_motion (None = all zero), the specification of
-    DeviceScene.refit_spheres. Returns (node bytes, leaf order, info dict, sah)."""
+def refit_bvh_binned(built_scene: SceneData, new_spheres, new_motion, max_leaf: int, node_cost: float, node_stride: int,
+                     new_quads=None):
+    """rrt_refit_bvh_binned_ex (host only): build_bvh_binned's tree of `built_scene` with its boxes
+    recomputed over new_spheres, new_motion (None = all zero) and new_quads (None = the built ones),
+    the specification of DeviceScene.refit_spheres and refit_geometry. Returns (node bytes, leaf
+    order, info dict, sah)."""
     lib = _lib.load()
     info = _lib.RrtBvhInfo()
     sah = ctypes.c_double(0.0)
@@ -349,11 +351,15 @@ def refit_bvh_binned(built_scene: SceneData, new_spheres, new_motion, max_leaf: 
     ext, keep = scene_ext(built_scene)
     n_prims = n + (0 if ext is None else ext.n_quads + ext.n_media)
     extp = ctypes.byref(ext) if ext is not None else None
+    q = None
+    if new_quads is not None:
+        q = np.ascontiguousarray(new_quads, dtype=_lib.QUAD_DTYPE)
+        assert len(q) == (0 if ext is None else ext.n_quads), "a refit keeps the quad count"
 
     def refit(nodes_p, cap, order_p):
-        return lib.rrt_refit_bvh_binned(_lib.ptr(built_scene.spheres), n, extp, int(max_leaf), float(node_cost),
-                                        int(node_stride), _lib.ptr(sp), _lib.ptr(m), nodes_p, cap, order_p,
-                                        ctypes.byref(info), ctypes.byref(sah))
+        return lib.rrt_refit_bvh_binned_ex(_lib.ptr(built_scene.spheres), n, extp, int(max_leaf), float(node_cost),
+                                           int(node_stride), _lib.ptr(sp), _lib.ptr(m), _lib.ptr(q), nodes_p, cap,
+                                           order_p, ctypes.byref(info), ctypes.byref(sah))
 
     _lib.check(refit(None, 0, None))
     nodes = np.zeros(info.node_bytes, dtype=np.uint8)
@@ -496,6 +502,47 @@ class DeviceScene:
                                                      ctypes.c_void_p(stream_ptr)))
         self.scene = dataclasses.replace(self.scene, spheres=sp.copy(), motion=None if m is None else m.copy())
 
+    def _geometry(self, spheres, motion, quads, lights):
+        """(RrtSceneGeometry, the replaced SceneData) of a geometry change; the struct borrows the
+        new scene's arrays."""
+        sc = self.scene
+        sp = np.ascontiguousarray(sc.spheres if spheres is None else spheres, dtype=_lib.SPHERE_DTYPE)
+        m = None
+        if motion is not None:
+            m = np.ascontiguousarray(motion, dtype=np.float32)
+            assert m.shape == (len(sp), 4), "motion is (n_spheres, 4) float32"
+        new = dataclasses.replace(sc, spheres=sp.copy(), motion=None if m is None else m.copy())
+        g = _lib.RrtSceneGeometry()
+        g.spheres, g.n_spheres = (new.spheres.ctypes.data if len(sp) else None), len(sp)
+        g.sphere_motion = new.motion.ctypes.data if m is not None and len(sp) else None
+        if quads is not None:
+            new = dataclasses.replace(new, quads=np.ascontiguousarray(quads, dtype=_lib.QUAD_DTYPE).copy())
+            g.quads, g.n_quads = new.quads.ctypes.data, len(new.quads)  # the address even of an empty array
+        if lights is None and sc.flags & _lib.FLAG_BOOK3:
+            lights = sc.lights
+        if lights is not None:
+            new = dataclasses.replace(new, lights=np.ascontiguousarray(lights, dtype=_lib.LIGHT_DTYPE).copy())
+            g.lights, g.n_lights = new.lights.ctypes.data, len(new.lights)
+        return g, new
+
+    def update_geometry(self, spheres=None, motion=None, quads=None, lights=None, stream_ptr: int = 0) -> None:
+        """rrt_scene_update_geometry: update_spheres extended to the quads (None = keep them) and, for a
+        book-3 scene, the light list (None = the current lights): the BVH is rebuilt on the device and
+        everything derived from the geometry re-formed there; the scene then equals one freshly created
+        from the new inputs. spheres=None passes the current spheres; motion=None is all zero. Waits
+        for the stream, returns synchronised."""
+        g, new = self._geometry(spheres, motion, quads, lights)
+        _lib.check(self._lib.rrt_scene_update_geometry(self._h, ctypes.byref(g), ctypes.c_void_p(stream_ptr)))
+        self.scene = new
+
+    def refit_geometry(self, spheres=None, motion=None, quads=None, lights=None, stream_ptr: int = 0) -> None:
+        """rrt_scene_refit_geometry: the same replacement as update_geometry, but the tree keeps its
+        topology and leaf order and only its boxes are recomputed; everything is enqueued on the stream
+        and the call does not wait for the device. tree_cost() tells when to rebuild."""
+        g, new = self._geometry(spheres, motion, quads, lights)
+        _lib.check(self._lib.rrt_scene_refit_geometry(self._h, ctypes.byref(g), ctypes.c_void_p(stream_ptr)))
+        self.scene = new
+
     def tree_cost(self) -> dict:
         """rrt_scene_tree_cost: the SAH cost of the tree held now, of the last build's tree, and the
         refits since that build. Synchronises the device."""
@@ -512,8 +559,9 @@ class DeviceScene:
 
     def read_table(self, name: str) -> np.ndarray:
         """rrt_testing_scene_read_table (test support): one of the scene's device tables (a
-        _lib.SCENE_TABLES name) as a flat array; empty when the scene does not hold it."""
-        code, dtype = _lib.SCENE_TABLES[name]
+        _lib.SCENE_TABLES or _lib.SCENE_GEOMETRY_TABLES name) as a flat array; empty when the scene does
+        not hold it."""
+        code, dtype = (_lib.SCENE_TABLES.get(name) or _lib.SCENE_GEOMETRY_TABLES[name])
         n = ctypes.c_size_t(0)
         _lib.check(self._lib.rrt_testing_scene_read_table(self._h, code, None, 0, ctypes.byref(n)))
         out = np.zeros(n.value // dtype.itemsize, dtype=dtype)
