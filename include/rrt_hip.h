@@ -555,6 +555,66 @@ int32_t rrt_refit_bvh_binned_ex(const RrtSphere *built_spheres, uint32_t n_spher
                                 void *nodes_out, size_t nodes_cap, uint32_t *prim_order_out,
                                 RrtBvhInfo *info, double *sah_out);
 
+/* ---- changing constant media and their boundaries too (additive; RRT_ABI_VERSION is unchanged) ---- */
+
+/* The media of a created scene, replaced as a whole. media: NULL keeps the scene's media; else
+ * n_media must equal the scene's and each entry's boundary_kind, first and count must equal the
+ * scene's entry (the structure is fixed at creation, as a light's kind is): its sphere row, density
+ * and material_index replace the old. boundary_quads: NULL keeps the scene's boundary quads; else
+ * n_boundary_quads must equal the scene's and each quad's q, u, v replace the old. */
+typedef struct RrtSceneMedia {
+    const RrtMedium *media;          /* NULL keeps the scene's media */
+    uint32_t n_media;
+    uint32_t n_boundary_quads;
+    const RrtQuad *boundary_quads;   /* NULL keeps the scene's boundary quads */
+} RrtSceneMedia;
+
+/* rrt_scene_update_geometry's contract extended to constant media: accepts every scene that entry
+ * accepts, and also scenes with media and / or boundary quads (f32 scenes: the f64 kernels refuse
+ * media at creation). media == NULL keeps the scene's media and boundary quads. Which media are
+ * tested outside the tree (RrtBvhInfo.n_unbounded) is decided again on the host from the new inputs,
+ * by scene creation's rule, and may change between updates, the tree's primitive count with it.
+ * Afterwards the scene holds, bit for bit, what rrt_scene_create_ex with RRT_FLAG_DEVICE_BVH makes of
+ * the new inputs: the classification and the tail of the leaf order, the tree over the remaining
+ * primitives, every per-primitive table, the quad records (scene quads, boundary quads, light
+ * quads), the medium records, the light records, every frame and its ray count. From the second
+ * change of a scene on, no device memory is allocated or freed, whichever way the classification
+ * flips.
+ * Refused with RRT_E_INVALID, before any device call and with the scene untouched: everything
+ * rrt_scene_update_geometry refuses except media and boundary quads; another n_media or
+ * n_boundary_quads; a medium whose boundary_kind, first or count differs from the scene's entry; a
+ * medium material_index out of range or naming no RRT_MAT_ISOTROPIC material, or a density that is
+ * not positive and finite (scene creation's rules); a sphere-bounded medium whose sphere row is not
+ * finite; a boundary quad whose q, u or v is not finite or whose u x v has a zero or non-finite
+ * squared length (rrt_scene_update_geometry's reason); a new classification that leaves fewer than 2
+ * primitives in the tree. */
+int32_t rrt_scene_update_world(RrtScene *scene, const RrtSceneGeometry *geometry,
+                               const RrtSceneMedia *media, void *stream);
+
+/* rrt_scene_refit_geometry's contract extended to constant media, with rrt_scene_update_world's
+ * arguments and refusals (but the last): topology, leaf order and the classification of the last
+ * build are kept — a medium tested after the walk stays correct wherever the geometry moves, a
+ * medium in the tree as long as its box is recomputed, which this does from its new boundary (bit
+ * for bit rrt_refit_bvh_binned_world). Everything is enqueued on `stream` with no host wait; the
+ * pinned staging buffer holds spheres | motion | quads | lights | media | boundary quads, sized
+ * once. Refits compose with each other, with the sphere and geometry refits where those apply, and
+ * with every update; rrt_scene_tree_cost keeps working across them. */
+int32_t rrt_scene_refit_world(RrtScene *scene, const RrtSceneGeometry *geometry,
+                              const RrtSceneMedia *media, void *stream);
+
+/* Host-only: rrt_refit_bvh_binned_ex with the new geometry taken from a second RrtSceneExt (its
+ * sphere_motion, NULL = all zero; its quads, media and boundary_quads, NULL = the built ones;
+ * new_ext == NULL = no motion, everything else as built). The counts, and
+ * each medium's boundary_kind, first and count, must equal built_ext's. The classification and the
+ * leaf order are the built tree's. The specification of rrt_scene_refit_world's tree, sah_out
+ * included. */
+int32_t rrt_refit_bvh_binned_world(const RrtSphere *built_spheres, uint32_t n_spheres,
+                                   const RrtSceneExt *built_ext, uint32_t max_leaf, double node_cost,
+                                   uint32_t node_stride, const RrtSphere *new_spheres,
+                                   const RrtSceneExt *new_ext,
+                                   void *nodes_out, size_t nodes_cap, uint32_t *prim_order_out,
+                                   RrtBvhInfo *info, double *sah_out);
+
 /* ---- host-side callers of the boundary ------------------------------------------------ */
 
 /* == gpu::build_in_one_weekend_scene (gpu/mod.rs:124-301): RTOW final scene from
@@ -808,8 +868,9 @@ typedef enum RrtSceneTable {
     RRT_TABLE_GQUADS = 6,       /* 80-B quad records: the scene's quads, boundary quads, light quads */
     RRT_TABLE_GQUADS64 = 7,     /* 128-B unrounded quad records, RRT_FLAG_F64_BOOK2 (instead of 6) */
     RRT_TABLE_QUAD_ROWS = 8,    /* 2 float4 per quad: its prim_cr row, its prim_motion row (held by
-                                   a scene the device builder built, without media) */
-    RRT_TABLE_GLIGHTS = 9       /* 32-B light records, RRT_FLAG_BOOK3 */
+                                   a scene the device builder built) */
+    RRT_TABLE_GLIGHTS = 9,      /* 32-B light records, RRT_FLAG_BOOK3 */
+    RRT_TABLE_GMEDIA = 10       /* 32-B medium records (rrt_scene_update_world), in source order */
 } RrtSceneTable;
 typedef struct RrtSceneUpdateStats {
     uint64_t updates;
@@ -825,6 +886,14 @@ int32_t rrt_testing_scene_update_stats(const RrtScene *scene, RrtSceneUpdateStat
  * n_quads 80-B records (RRT_TABLE_GQUADS' layout); gquad64: n_quads 128-B records
  * (RRT_TABLE_GQUADS64's: q, u, v, n, w as 3 doubles each, then D). */
 int32_t rrt_testing_quad_records(const RrtQuad *quads, uint32_t n_quads, double *boxes6, void *gquad, void *gquad64);
+/* Test support, not part of the drop-in: what a constant medium contributes to a scene, by the host
+ * compilation of the functions rrt_scene_update_world runs on the device (and scene creation on the
+ * host). Either output may be NULL. boxes6: n_media x 6 doubles (min xyz, max xyz), the medium's
+ * box; gmedium: n_media 32-B records (RRT_TABLE_GMEDIA's layout: the sphere, kind, first = n_quads +
+ * the medium's first, count, -1 / density). A quad boundary's range must lie within
+ * n_boundary_quads. */
+int32_t rrt_testing_medium_records(const RrtMedium *media, uint32_t n_media, const RrtQuad *boundary_quads,
+                                   uint32_t n_boundary_quads, uint32_t n_quads, double *boxes6, void *gmedium);
 
 /* Test support, not part of the drop-in. rrt_testing_scene_refit_stats: the scene's refits so far,
  * and of the last one the device allocations, the kernel launches and the form of the bottom-up

@@ -111,6 +111,10 @@ EXPORTED_SYMBOLS = (
     "rrt_scene_refit_geometry",
     "rrt_refit_bvh_binned_ex",
     "rrt_testing_quad_records",
+    "rrt_scene_update_world",
+    "rrt_scene_refit_world",
+    "rrt_refit_bvh_binned_world",
+    "rrt_testing_medium_records",
 )
 
 # == RrtSceneTable (include/rrt_hip.h, test support): table -> (code, row dtype)
@@ -130,6 +134,18 @@ GQUAD_DTYPE = np.dtype([("q", "<f4", 4), ("u", "<f4", 4), ("v", "<f4", 4), ("n",
 GQUAD64_DTYPE = np.dtype([("q", "<f8", 3), ("u", "<f8", 3), ("v", "<f8", 3), ("n", "<f8", 3), ("w", "<f8", 3), ("D", "<f8")])
 GLIGHT_DTYPE = np.dtype([("sphere", "<f4", 4), ("kind", "<u4"), ("quad", "<u4"), ("area", "<f4"), ("_pad", "<u4")])
 assert GQUAD_DTYPE.itemsize == 80 and GQUAD64_DTYPE.itemsize == 128 and GLIGHT_DTYPE.itemsize == 32
+
+
+# The table rrt_scene_update_world re-forms beyond those (RrtSceneTable 10), in source order.
+# GMEDIUM_DTYPE gives its records.
+SCENE_MEDIA_TABLES = {"gmedia": (10, np.dtype("<u4"))}
+GMEDIUM_DTYPE = np.dtype([("sphere", "<f4", 4), ("kind", "<u4"), ("first", "<u4"), ("count", "<u4"),
+                          ("neg_inv_density", "<f4")])
+assert GMEDIUM_DTYPE.itemsize == 32
+
+
+class RrtSceneMedia(ctypes.Structure):  # include/rrt_hip.h
+    _fields_ = [("media", c_void_p), ("n_media", c_uint32), ("n_boundary_quads", c_uint32), ("boundary_quads", c_void_p)]
 
 
 class RrtSceneGeometry(ctypes.Structure):  # include/rrt_hip.h
@@ -363,6 +379,19 @@ def quad_records(quads):
     return boxes, g32, g64
 
 
+def medium_records(media, boundary_quads=None, n_quads=0):
+    """rrt_testing_medium_records (test support): what each constant medium contributes to a scene, by the
+    host compilation of the functions rrt_scene_update_world runs on the device: (boxes (n, 6) float64 as
+    min xyz, max xyz; GMEDIUM_DTYPE records with first = n_quads + the medium's first)."""
+    md = np.ascontiguousarray(media, dtype=MEDIUM_DTYPE)
+    bq = None if boundary_quads is None else np.ascontiguousarray(boundary_quads, dtype=QUAD_DTYPE)
+    boxes = np.zeros((len(md), 6), dtype=np.float64)
+    g = np.zeros(len(md), dtype=GMEDIUM_DTYPE)
+    check(load().rrt_testing_medium_records(ptr(md), len(md), ptr(bq), 0 if bq is None else len(bq), int(n_quads),
+                                            ptr(boxes), ptr(g)))
+    return boxes, g
+
+
 def div_check(a_values) -> list:
     """rrt_testing_div_check (test support): the eight counters for the divisors a_values."""
     a = np.ascontiguousarray(a_values, dtype=np.float32).ravel()
@@ -475,6 +504,10 @@ def load() -> ctypes.CDLL:
         "rrt_scene_refit_geometry": (c_int32, [P, P, P]),
         "rrt_refit_bvh_binned_ex": (c_int32, [P, c_uint32, P, c_uint32, c_double, c_uint32, P, P, P, P, c_size_t, P, P, P]),
         "rrt_testing_quad_records": (c_int32, [P, c_uint32, P, P, P]),
+        "rrt_scene_update_world": (c_int32, [P, P, P, P]),
+        "rrt_scene_refit_world": (c_int32, [P, P, P, P]),
+        "rrt_refit_bvh_binned_world": (c_int32, [P, c_uint32, P, c_uint32, c_double, c_uint32, P, P, P, c_size_t, P, P, P]),
+        "rrt_testing_medium_records": (c_int32, [P, c_uint32, P, c_uint32, c_uint32, P, P]),
     }
     experiment = "RRT_LIB_PATH" in os.environ  # A/B of older builds: tolerate symbols they lack
     for name, (res, args) in sig.items():

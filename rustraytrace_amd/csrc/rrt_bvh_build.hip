@@ -402,6 +402,7 @@ hipError_t grow(T *&p, size_t &cap, size_t need, uint64_t &n_alloc) {
 
 struct DeviceBvhBuilder::Impl {
     uint32_t n_tree = 0;
+    uint32_t cap = 0;  // primitives every array is sized for (upload's n_boxes): n_tree <= cap
     Box6 *d_boxes = nullptr;
     uint32_t *d_order[2] = {nullptr, nullptr};
     int32_t *d_ptask[2] = {nullptr, nullptr};
@@ -427,7 +428,7 @@ struct DeviceBvhBuilder::Impl {
     // refit: the first node of every level that holds nodes, then n_nodes (host and device), the
     // kept build's node price, the slack on the device, and the SAH terms
     std::vector<uint32_t> level_base;
-    uint32_t *d_level_base = nullptr;  // n_tree + 1 entries
+    uint32_t *d_level_base = nullptr;  // cap + 1 entries
     double node_cost = 0.0;
     Slack *d_slack = nullptr;
     double *d_terms = nullptr;
@@ -489,35 +490,48 @@ DeviceBvhBuilder::~DeviceBvhBuilder() { delete impl_; }
 
 hipError_t DeviceBvhBuilder::upload(const Box6 *boxes, uint32_t n_boxes, const uint32_t *objs, uint32_t n_tree) {
     Impl &m = *impl_;
-    if (n_tree < 2u) return hipErrorInvalidValue;
+    if (n_tree < 2u || n_tree > n_boxes || m.cap) return hipErrorInvalidValue;
     for (uint32_t i = 0; i < n_tree; ++i)
         if (objs[i] >= n_boxes) return hipErrorInvalidValue;
     m.n_tree = n_tree;
-    const uint32_t nb = blocks_of(n_tree, kBlk);
-    BB_TRY(hipMalloc((void **)&m.d_boxes, (size_t)n_boxes * sizeof(Box6)));
-    BB_TRY(hipMemcpy(m.d_boxes, boxes, (size_t)n_boxes * sizeof(Box6), hipMemcpyHostToDevice));
-    BB_TRY(hipMalloc((void **)&m.d_order0, (size_t)n_tree * 4));
+    m.cap = n_boxes;
+    const size_t cap = n_boxes;  // n_tree may grow up to it (set_objects)
+    const uint32_t nb = blocks_of(n_boxes, kBlk);
+    BB_TRY(hipMalloc((void **)&m.d_boxes, cap * sizeof(Box6)));
+    BB_TRY(hipMemcpy(m.d_boxes, boxes, cap * sizeof(Box6), hipMemcpyHostToDevice));
+    BB_TRY(hipMalloc((void **)&m.d_order0, cap * 4));
     BB_TRY(hipMemcpy(m.d_order0, objs, (size_t)n_tree * 4, hipMemcpyHostToDevice));
     for (int k = 0; k < 2; ++k) {
-        BB_TRY(hipMalloc((void **)&m.d_order[k], (size_t)n_tree * 4));
-        BB_TRY(hipMalloc((void **)&m.d_ptask[k], (size_t)n_tree * 4));
+        BB_TRY(hipMalloc((void **)&m.d_order[k], cap * 4));
+        BB_TRY(hipMalloc((void **)&m.d_ptask[k], cap * 4));
     }
-    BB_TRY(hipMalloc((void **)&m.d_raw, (size_t)n_tree * sizeof(RawNode)));  // internal nodes <= n_tree - 1
-    BB_TRY(hipMalloc((void **)&m.d_flag, (size_t)n_tree));
+    BB_TRY(hipMalloc((void **)&m.d_raw, cap * sizeof(RawNode)));  // internal nodes <= n_tree - 1
+    BB_TRY(hipMalloc((void **)&m.d_flag, cap));
     BB_TRY(hipMalloc((void **)&m.d_block, (size_t)nb * 4));
     BB_TRY(hipMalloc((void **)&m.d_totals, 6 * 4));
     BB_TRY(hipMalloc((void **)&m.d_state, sizeof(LevelState)));
-    BB_TRY(hipMalloc((void **)&m.d_level_base, ((size_t)n_tree + 1) * 4));  // a level holds a node: <= n_tree - 1 levels
+    BB_TRY(hipMalloc((void **)&m.d_level_base, (cap + 1) * 4));  // a level holds a node: <= n_tree - 1 levels
     BB_TRY(hipMalloc((void **)&m.d_slack, sizeof(Slack)));
     m.n_alloc += 12;
     return hipSuccess;
 }
 
-// Tasks are disjoint ranges of span >= 2, so a level holds at most n_tree / 2 of them.
+hipError_t DeviceBvhBuilder::set_objects(const uint32_t *objs, uint32_t n_tree) {
+    Impl &m = *impl_;
+    if (!m.cap || !objs || n_tree < 2u || n_tree > m.cap) return hipErrorInvalidValue;
+    for (uint32_t i = 0; i < n_tree; ++i)
+        if (objs[i] >= m.cap) return hipErrorInvalidValue;
+    BB_TRY(hipMemcpy(m.d_order0, objs, (size_t)n_tree * 4, hipMemcpyHostToDevice));
+    m.n_tree = n_tree;
+    return hipSuccess;
+}
+uint32_t DeviceBvhBuilder::n_tree() const { return impl_->n_tree; }
+
+// Tasks are disjoint ranges of span >= 2, so a level holds at most n_tree / 2 <= cap / 2 of them.
 hipError_t DeviceBvhBuilder::reserve() {
     Impl &m = *impl_;
     if (m.n_tree < 2u) return hipErrorInvalidValue;
-    const size_t max_tasks = m.n_tree / 2u;
+    const size_t max_tasks = m.cap / 2u;
     for (int k = 0; k < 2; ++k) BB_TRY(grow(m.d_tasks[k], m.tasks_cap[k], max_tasks, m.n_alloc));
     BB_TRY(grow(m.d_dec, m.dec_cap, max_tasks, m.n_alloc));
     BB_TRY(grow(m.d_bins, m.bins_cap, max_tasks * (3 * kBins), m.n_alloc));
@@ -674,7 +688,7 @@ uint32_t DeviceBvhBuilder::refit_form() const { return impl_->last_refit_form; }
 
 hipError_t DeviceBvhBuilder::reserve_cost() {
     Impl &m = *impl_;
-    BB_TRY(grow(m.d_terms, m.terms_cap, (size_t)m.n_tree, m.n_alloc));
+    BB_TRY(grow(m.d_terms, m.terms_cap, (size_t)m.cap, m.n_alloc));
     if (!m.d_root_build) {
         ++m.n_alloc;
         BB_TRY(hipMalloc((void **)&m.d_root_build, 2 * sizeof(RawNode)));  // [0]: the build's root, [1]: the current one
@@ -684,7 +698,7 @@ hipError_t DeviceBvhBuilder::reserve_cost() {
 hipError_t DeviceBvhBuilder::reserve_refit() {
     Impl &m = *impl_;
     BB_TRY(reserve_cost());
-    return grow(m.d_terms_build, m.terms_build_cap, (size_t)m.n_tree, m.n_alloc);
+    return grow(m.d_terms_build, m.terms_build_cap, (size_t)m.cap, m.n_alloc);
 }
 uint64_t DeviceBvhBuilder::refits_since_build() const { return impl_->refits; }
 

@@ -12,6 +12,7 @@
 #include "rrt_bvh_binned.h"
 #include "rrt_sphere_box.h"
 #include "rrt_quad_form.h"
+#include "rrt_medium_form.h"
 #include "../../include/rrt_hip.h"
 
 #include <algorithm>
@@ -787,15 +788,9 @@ std::vector<Aabb> prim_boxes(const RrtSphere *spheres, uint32_t n_spheres, const
     }
     for (uint32_t j = 0; j < n_quads; ++j) boxes[n_spheres + j] = quad_box(ex.quads[j]);
     for (uint32_t m = 0; m < ex.n_media; ++m) {
-        const RrtMedium &md = ex.media[m];
-        Aabb b = aabb_empty();
-        if (md.boundary_kind == RRT_BOUNDARY_SPHERE) {
-            const double r = std::max((double)md.sphere[3], 0.0);
-            for (int a = 0; a < 3; ++a) b.ax[a] = Interval{md.sphere[a] - r, md.sphere[a] + r};
-            b = pad(b);
-        } else {
-            for (uint32_t k = 0; k < md.count; ++k) b = aabb_union(b, quad_box(ex.bquads[md.first + k]));
-        }
+        const rrt::bvhb::Box6 b6 = rrt::medium_box(ex.media[m], ex.bquads);  // rrt_medium_form.h
+        Aabb b;
+        for (int a = 0; a < 3; ++a) b.ax[a] = Interval{b6.mn[a], b6.mx[a]};
         boxes[n_spheres + n_quads + m] = b;
     }
     return boxes;
@@ -1132,6 +1127,15 @@ struct RrtScene {
     uint32_t *d_light_quad = nullptr;
     RrtQuad *d_src_quads = nullptr;
     RrtLight *d_src_lights = nullptr;
+    // rrt_scene_update_world / rrt_scene_refit_world, kept by a device-built scene with media or
+    // boundary quads: the rows the classification (unbounded_media) reads on the host and a kept
+    // array stands for (quads, media, boundary quads as last given), the unbounded media of the
+    // last build as primitive indices, and the device staging of the media and boundary-quad rows
+    std::vector<RrtQuad> h_quads, h_bquads;
+    std::vector<RrtMedium> h_media;
+    std::vector<uint32_t> unbounded;
+    RrtMedium *d_src_media = nullptr;
+    RrtQuad *d_src_bquads = nullptr;
 };
 
 namespace {
@@ -1169,6 +1173,8 @@ void free_scene(RrtScene *s) {
     (void)hipFree(s->d_light_quad);
     (void)hipFree(s->d_src_quads);
     (void)hipFree(s->d_src_lights);
+    (void)hipFree(s->d_src_media);
+    (void)hipFree(s->d_src_bquads);
     if (s->h_stage) (void)hipHostFree(s->h_stage);
     if (s->ev_staged) (void)hipEventDestroy(s->ev_staged);
     if (s->ev_refit_done) (void)hipEventDestroy(s->ev_refit_done);
@@ -1591,6 +1597,17 @@ static void bvh_info_tree(RrtBvhInfo &bi, const FlatBvh &fb, size_t node_bytes, 
     bi.n_unbounded = fb.n_unbounded;
 }
 
+// What scene creation and a world change (rrt_scene_update_world) alike refuse of a medium's phase
+// material and density. kind_of(k): material k's kind.
+template <class KindOf>
+static int32_t check_medium_phase(const RrtMedium &md, const std::string &what, uint32_t n_materials, KindOf kind_of) {
+    if (md.material_index >= n_materials || kind_of(md.material_index) != RRT_MAT_ISOTROPIC)
+        return fail(RRT_E_INVALID, what + ": material_index must name an RRT_MAT_ISOTROPIC material");
+    if (!(md.density > 0.0f) || !std::isfinite(md.density))
+        return fail(RRT_E_INVALID, what + ": density must be positive and finite");
+    return RRT_OK;
+}
+
 static int32_t scene_create(const RrtCamera *cam, const RrtSphere *spheres, uint32_t n_spheres,
                             const RrtMaterial *materials, uint32_t n_materials, const RrtTexture *textures,
                             uint32_t n_textures, const RrtSceneExt *ext, uint32_t flags, int32_t device,
@@ -1611,10 +1628,7 @@ static int32_t scene_create(const RrtCamera *cam, const RrtSphere *spheres, uint
     for (uint32_t m = 0; m < n_media; ++m) {
         const RrtMedium &md = ex.media[m];
         const std::string what = "medium " + std::to_string(m);
-        if (md.material_index >= n_materials || materials[md.material_index].kind != RRT_MAT_ISOTROPIC)
-            return fail(RRT_E_INVALID, what + ": material_index must name an RRT_MAT_ISOTROPIC material");
-        if (!(md.density > 0.0f) || !std::isfinite(md.density))
-            return fail(RRT_E_INVALID, what + ": density must be positive and finite");
+        if (int rc = check_medium_phase(md, what, n_materials, [&](uint32_t k) { return materials[k].kind; })) return rc;
         if (md.boundary_kind == RRT_BOUNDARY_QUADS) {
             if (md.count == 0 || (uint64_t)md.first + md.count > ex.n_bquads)
                 return fail(RRT_E_INVALID, what + ": boundary quad range out of bounds");
@@ -1824,13 +1838,7 @@ static int32_t scene_create(const RrtCamera *cam, const RrtSphere *spheres, uint
     // Media: boundary quads follow the scene's quads in the GQuad array.
     std::vector<rrt::GMedium> gmedia(n_media);
     for (uint32_t m = 0; m < n_media; ++m) {
-        const RrtMedium &md = ex.media[m];
-        rrt::GMedium &g = gmedia[m];
-        g.sphere = make_float4(md.sphere[0], md.sphere[1], md.sphere[2], std::max(md.sphere[3], 0.0f));
-        g.kind = md.boundary_kind;
-        g.first = n_quads + md.first;
-        g.count = md.count;
-        g.neg_inv_density = (float)(-1.0 / (double)md.density);  // constant_medium.rs:24
+        gmedia[m] = rrt::medium_record(ex.media[m], n_quads);  // rrt_medium_form.h
     }
     std::vector<rrt::GPerlin> perlin(n_perlin);
     for (uint32_t t = 0; t < n_perlin; ++t) {
@@ -1866,6 +1874,12 @@ static int32_t scene_create(const RrtCamera *cam, const RrtSphere *spheres, uint
     s->light_kinds.resize(glights.size());
     for (uint32_t l = 0; l < glights.size(); ++l) s->light_kinds[l] = glights[l].kind;
     if (built_on_device) s->builder = builder.release();
+    if (built_on_device && (n_media || ex.n_bquads)) {
+        if (n_quads) s->h_quads.assign(quads, quads + n_quads);
+        if (n_media) s->h_media.assign(ex.media, ex.media + n_media);
+        if (ex.n_bquads) s->h_bquads.assign(ex.bquads, ex.bquads + ex.n_bquads);
+        s->unbounded.assign(order.end() - fb.n_unbounded, order.end());
+    }
     int rc = RRT_OK;
     do {
         if (hipSetDevice(device) != hipSuccess) { rc = fail(RRT_E_HIP, "hipSetDevice failed"); break; }
@@ -1886,7 +1900,7 @@ static int32_t scene_create(const RrtCamera *cam, const RrtSphere *spheres, uint
         }
         // rrt_scene_update_spheres and rrt_scene_update_geometry re-form the tables above on the device,
         // from these in source order
-        if (built_on_device && !n_media) {
+        if (built_on_device) {
             if (!glights.empty()) {  // each light quad's GQuad, at its fixed index after the scene's quads
                 std::vector<uint32_t> light_quad(glights.size());
                 for (uint32_t l = 0; l < glights.size(); ++l) light_quad[l] = glights[l].quad;
@@ -1902,7 +1916,7 @@ static int32_t scene_create(const RrtCamera *cam, const RrtSphere *spheres, uint
                 std::vector<float4> rows(2 * (size_t)n_quads);
                 std::vector<uint32_t> quad_mat(n_quads);
                 for (uint32_t i = 0; i < n_prims; ++i) {
-                    if (order[i] < n_spheres) continue;
+                    if (order[i] < n_spheres || order[i] >= n_spheres + n_quads) continue;  // a sphere, a medium
                     const uint32_t j = order[i] - n_spheres;
                     rows[2 * (size_t)j] = prim_cr[i];
                     rows[2 * (size_t)j + 1] = prim_motion[i];
@@ -2103,9 +2117,10 @@ int32_t rrt_scene_set_camera(RrtScene *scene, const RrtCamera *cam) {
 namespace {
 
 // What rrt_scene_update_spheres and rrt_scene_refit_spheres refuse before any device call.
-// geometry: the caller is a geometry entry, which brings a book-3 scene's lights along.
+// geometry: the caller is a geometry entry, which brings a book-3 scene's lights along. world: a
+// world entry, which brings the media along too.
 int check_sphere_change(const RrtScene *s, const std::string &fn, const RrtSphere *spheres, uint32_t n_spheres,
-                        const float *motion, bool &has_motion, bool geometry = false) {
+                        const float *motion, bool &has_motion, bool geometry = false, bool world = false) {
     if (!s) return fail(RRT_E_INVALID, fn + "null scene");
     if (n_spheres != s->n_spheres)
         return fail(RRT_E_INVALID, fn + "n_spheres is " + std::to_string(n_spheres) + ", the scene's is " +
@@ -2114,7 +2129,7 @@ int check_sphere_change(const RrtScene *s, const std::string &fn, const RrtSpher
     if (!s->device_bvh)
         return fail(RRT_E_INVALID, fn + "the scene was not created with RRT_FLAG_DEVICE_BVH (its tree is rebuilt or "
                                         "refitted by the device builder)");
-    if (s->base.n_media)
+    if (s->base.n_media && !world)
         return fail(RRT_E_INVALID, fn + "scenes with constant media are not updated (which media are unbounded "
                                         "depends on every sphere)");
     if (!geometry && (s->base.flags & RRT_FLAG_BOOK3))
@@ -2172,6 +2187,9 @@ rrt::LeafTables leaf_tables_of(const RrtScene *s, const float *d_motion) {
     rrt::LeafTables t{};
     t.n_prims = s->base.n_prims, t.n_spheres = s->n_spheres, t.book2 = s->book2 ? 1u : 0u, t.f64 = s->f64 ? 1u : 0u;
     t.order = s->builder->device_order();
+    t.n_tree = s->builder->n_tree(), t.n_quads = s->base.n_quads;
+    for (size_t k = 0; k < s->unbounded.size() && k < rrt::kMaxUnbounded; ++k) t.unbounded[k] = s->unbounded[k];
+    t.media = s->d_src_media;
     t.spheres = s->d_src_spheres;
     t.motion = d_motion;
     t.mats = s->d_src_mats;
@@ -2203,16 +2221,81 @@ struct GeometryChange {
     const RrtQuad *quads = nullptr;
     const RrtLight *lights = nullptr;
     bool quads_in32 = true;
+    // a world entry (rrt_scene_update_world, rrt_scene_refit_world): the media and boundary quads it
+    // brings (null: kept), and for the update the new classification: the unbounded media and the
+    // tree's primitives in their original order
+    bool world = false;
+    const RrtMedium *media = nullptr;
+    const RrtQuad *bquads = nullptr;
+    std::vector<uint32_t> unbounded, objs;
 };
+
+int check_geometry_change(const RrtScene *s, const std::string &fn, const RrtSceneGeometry *g, bool &has_motion,
+                          GeometryChange &out, bool world);
+
+// What the world entries refuse beyond check_geometry_change's list (which they run without its
+// refusal of media and boundary quads), before any device call. update: the classification of the
+// new inputs is formed here (unbounded_media, scene creation's rule) and must leave a tree of 2.
+int check_world_change(const RrtScene *s, const std::string &fn, const RrtSceneGeometry *g, const RrtSceneMedia *wm,
+                       bool update, bool &has_motion, GeometryChange &out) {
+    if (int rc = check_geometry_change(s, fn, g, has_motion, out, true)) return rc;
+    out.world = true;
+    const uint32_t n_media = s->base.n_media, n_bquads = s->n_bquads;
+    if (wm && wm->media) {
+        if (wm->n_media != n_media)
+            return fail(RRT_E_INVALID, fn + "n_media is " + std::to_string(wm->n_media) + ", the scene's is " +
+                                           std::to_string(n_media) + " (the primitive count is fixed at creation)");
+        for (uint32_t m = 0; m < n_media; ++m) {
+            const RrtMedium &md = wm->media[m], &was = s->h_media[m];
+            const std::string what = fn + "medium " + std::to_string(m);
+            if (md.boundary_kind != was.boundary_kind || md.first != was.first || md.count != was.count)
+                return fail(RRT_E_INVALID, what + ": boundary_kind, first or count differs from the scene's entry (a "
+                                                  "medium's structure is fixed at creation)");
+            if (int rc = check_medium_phase(md, what, s->n_materials, [&](uint32_t k) { return s->mat_kinds[k]; })) return rc;
+            if (md.boundary_kind == RRT_BOUNDARY_SPHERE && !rrt::medium_sphere_is_finite(md))
+                return fail(RRT_E_INVALID, what + ": the sphere row must be finite");
+        }
+        out.media = wm->media;
+    }
+    if (wm && wm->boundary_quads) {
+        if (wm->n_boundary_quads != n_bquads)
+            return fail(RRT_E_INVALID, fn + "n_boundary_quads is " + std::to_string(wm->n_boundary_quads) + ", the scene's is " +
+                                           std::to_string(n_bquads) + " (the boundaries' structure is fixed at creation)");
+        for (uint32_t k = 0; k < n_bquads; ++k) {
+            const RrtQuad &qd = wm->boundary_quads[k];
+            if (!rrt::quad_is_regular(qd.q, qd.u, qd.v))
+                return fail(RRT_E_INVALID, fn + "boundary quad " + std::to_string(k) + " is degenerate: q, u and v must be "
+                                                "finite and u x v must have a finite, non-zero length");
+        }
+        out.bquads = wm->boundary_quads;
+    }
+    if (!update) return RRT_OK;
+    RrtSceneExt e{};
+    e.sphere_motion = has_motion ? g->sphere_motion : nullptr;
+    e.quads = out.quads ? out.quads : s->h_quads.data(), e.n_quads = s->base.n_quads;
+    e.media = out.media ? out.media : s->h_media.data(), e.n_media = n_media;
+    e.boundary_quads = out.bquads ? out.bquads : s->h_bquads.data(), e.n_boundary_quads = n_bquads;
+    const uint32_t first_medium = s->n_spheres + s->base.n_quads;
+    for (uint32_t m : unbounded_media(g->spheres, g->n_spheres, ExtView(&e))) out.unbounded.push_back(first_medium + m);
+    if (s->base.n_prims - (uint32_t)out.unbounded.size() < 2u)
+        return fail(RRT_E_INVALID, fn + "the new classification leaves fewer than 2 primitives in the tree (" +
+                                       std::to_string(out.unbounded.size()) + " media are unbounded)");
+    size_t u = 0;  // the unbounded media are in ascending order
+    for (uint32_t i = 0; i < s->base.n_prims; ++i) {
+        if (u < out.unbounded.size() && out.unbounded[u] == i) ++u;
+        else out.objs.push_back(i);
+    }
+    return RRT_OK;
+}
 
 // What the geometry entries refuse before any device call: check_sphere_change's list but for
 // RRT_FLAG_BOOK3, then the quads' and lights' own.
 int check_geometry_change(const RrtScene *s, const std::string &fn, const RrtSceneGeometry *g, bool &has_motion,
-                          GeometryChange &out) {
+                          GeometryChange &out, bool world = false) {
     if (!s) return fail(RRT_E_INVALID, fn + "null scene");
     if (!g) return fail(RRT_E_INVALID, fn + "null geometry");
-    if (int rc = check_sphere_change(s, fn, g->spheres, g->n_spheres, g->sphere_motion, has_motion, true)) return rc;
-    if (s->n_bquads)
+    if (int rc = check_sphere_change(s, fn, g->spheres, g->n_spheres, g->sphere_motion, has_motion, true, world)) return rc;
+    if (s->n_bquads && !world)
         return fail(RRT_E_INVALID, fn + "scenes with boundary quads are not updated (they bound constant media)");
     const uint32_t n_quads = s->base.n_quads, n_lights = s->base.n_lights;
     if (g->quads) {
@@ -2257,16 +2340,44 @@ int check_geometry_change(const RrtScene *s, const std::string &fn, const RrtSce
 }
 
 // The first geometry change that brings quads (lights): the device staging of those rows.
-int ensure_geometry_buffers(RrtScene *s, const GeometryChange &g, uint64_t &own_allocs) {
-    if (g.quads && s->base.n_quads && !s->d_src_quads) {
+int ensure_geometry_rows(RrtScene *s, bool quads, bool lights, uint64_t &own_allocs) {
+    if (quads && s->base.n_quads && !s->d_src_quads) {
         ++own_allocs;
         HIP_TRY(hipMalloc((void **)&s->d_src_quads, (size_t)s->base.n_quads * sizeof(RrtQuad)), "hipMalloc quads");
     }
-    if (g.lights && !s->d_src_lights) {
+    if (lights && s->base.n_lights && !s->d_src_lights) {
         ++own_allocs;
         HIP_TRY(hipMalloc((void **)&s->d_src_lights, (size_t)s->base.n_lights * sizeof(RrtLight)), "hipMalloc lights");
     }
     return RRT_OK;
+}
+int ensure_geometry_buffers(RrtScene *s, const GeometryChange &g, uint64_t &own_allocs) {
+    return ensure_geometry_rows(s, g.quads != nullptr, g.lights != nullptr, own_allocs);
+}
+
+// The first world change of a scene: the device staging of the media and boundary-quad rows, filled
+// with the scene's own (a later call may keep either array), and the quads' and lights' staging
+// whether or not this call brings them, so that no later world change allocates.
+int ensure_world_buffers(RrtScene *s, const GeometryChange &g, uint64_t &own_allocs) {
+    if (!g.world) return RRT_OK;
+    if (int rc = ensure_geometry_rows(s, true, true, own_allocs)) return rc;
+    if (!s->h_media.empty() && !s->d_src_media) {
+        ++own_allocs;
+        if (int rc = upload(&s->d_src_media, s->h_media.data(), s->h_media.size(), "media rows")) return rc;
+    }
+    if (!s->h_bquads.empty() && !s->d_src_bquads) {
+        ++own_allocs;
+        if (int rc = upload(&s->d_src_bquads, s->h_bquads.data(), s->h_bquads.size(), "boundary quad rows")) return rc;
+    }
+    return RRT_OK;
+}
+
+// After a world change: the rows a later call may keep.
+void keep_world_rows(RrtScene *s, const GeometryChange &g) {
+    if (!g.world || (s->h_media.empty() && s->h_bquads.empty())) return;
+    if (g.quads && s->base.n_quads) s->h_quads.assign(g.quads, g.quads + s->base.n_quads);
+    if (g.media && s->base.n_media) s->h_media.assign(g.media, g.media + s->base.n_media);
+    if (g.bquads && s->n_bquads) s->h_bquads.assign(g.bquads, g.bquads + s->n_bquads);
 }
 
 int32_t update_scene(RrtScene *s, const std::string &fn, const RrtSphere *spheres, uint32_t n_spheres, const float *motion,
@@ -2283,10 +2394,18 @@ int32_t update_scene(RrtScene *s, const std::string &fn, const RrtSphere *sphere
     uint64_t own_allocs = 0;
     if (int rc = ensure_change_buffers(s, fn, own_allocs)) return rc;
     if (int rc = ensure_geometry_buffers(s, g, own_allocs)) return rc;
+    if (int rc = ensure_world_buffers(s, g, own_allocs)) return rc;
     auto broke = [&](int code, const std::string &msg) {
         s->failed_update = fn + msg;
         return fail(code, fn + msg);
     };
+    // a world change: the rows it brings, then the boxes of all media (a quad boundary's box needs both)
+    const uint32_t n_media = g.media ? p.n_media : 0u, n_bquads = g.bquads ? s->n_bquads : 0u;
+    const uint32_t n_medium_boxes = (n_media || n_bquads) ? p.n_media : 0u;
+    if (n_media && hipMemcpy(s->d_src_media, g.media, (size_t)n_media * sizeof(RrtMedium), hipMemcpyHostToDevice) != hipSuccess)
+        return broke(RRT_E_HIP, "copying the media failed");
+    if (n_bquads && hipMemcpy(s->d_src_bquads, g.bquads, (size_t)n_bquads * sizeof(RrtQuad), hipMemcpyHostToDevice) != hipSuccess)
+        return broke(RRT_E_HIP, "copying the boundary quads failed");
     if (n_spheres && hipMemcpy(s->d_src_spheres, spheres, (size_t)n_spheres * sizeof(RrtSphere), hipMemcpyHostToDevice) != hipSuccess)
         return broke(RRT_E_HIP, "copying the spheres failed");
     if (has_motion && hipMemcpy(s->d_src_motion, motion, (size_t)n_spheres * 4 * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
@@ -2301,15 +2420,30 @@ int32_t update_scene(RrtScene *s, const std::string &fn, const RrtSphere *sphere
         return broke(RRT_E_HIP, "the sphere-box launch failed");
     if (rrt::launch_quad_boxes(n_quads, s->d_src_quads, s->builder->device_boxes() + n_spheres) != hipSuccess)
         return broke(RRT_E_HIP, "the quad-box launch failed");
+    if (rrt::launch_medium_boxes(n_medium_boxes, s->d_src_media, s->d_src_bquads, s->n_bquads,
+                                 s->builder->device_boxes() + n_spheres + p.n_quads) != hipSuccess)
+        return broke(RRT_E_HIP, "the medium-box launch failed");
+    // the classification the host formed: the tree's primitives to the builder, the unbounded media
+    // behind its leaf order
+    BinnedInput cls;
+    cls.unbounded = g.world ? g.unbounded : s->unbounded;
+    if (g.world && s->builder->set_objects(g.objs.data(), (uint32_t)g.objs.size()) != hipSuccess)
+        return broke(RRT_E_HIP, "device BVH: replacing the tree's primitives failed");
     bvhb::Summary sum{};
     uint32_t stride = 0, leaf_param = s->max_leaf, levels = 0;
     if (int rc = bvh_device_shape(*s->builder, n_prims, s->max_leaf, s->book2, s->f64, sum, stride, leaf_param, levels))
         return broke(rc, g_err);
-    const FlatBvh fb = flat_of_summary(sum, stride, BinnedInput{});
+    const FlatBvh fb = flat_of_summary(sum, stride, cls);
     if (int rc = tree_limits(fb, s->f64)) return broke(rc, g_err);
     const size_t node_bytes = (size_t)fb.n_nodes * fb.stride;
     if (s->builder->emit_into(stride, s->d_nodes, s->nodes_cap, s->order.data()) != hipSuccess)
         return broke(RRT_E_HIP, "device BVH: emit failed");
+    std::copy(cls.unbounded.begin(), cls.unbounded.end(), s->order.begin() + s->builder->n_tree());
+    s->unbounded = cls.unbounded;
+    if (rrt::launch_medium_records(n_media, s->d_src_media, p.n_quads, s->d_media) != hipSuccess)
+        return broke(RRT_E_HIP, "the medium-record launch failed");
+    if (rrt::launch_bquad_records(n_bquads, s->d_src_bquads, s->d_quads ? s->d_quads + p.n_quads : nullptr) != hipSuccess)
+        return broke(RRT_E_HIP, "the boundary-quad launch failed");
     // the quads' records, rows and material indices, then the lights with their GQuads; the leaf
     // tables read the rows
     if (rrt::launch_quad_records(n_quads, s->d_src_quads, s->d_quads, s->d_quads64, s->d_quad_rows, s->d_quad_mat) != hipSuccess)
@@ -2324,6 +2458,7 @@ int32_t update_scene(RrtScene *s, const std::string &fn, const RrtSphere *sphere
     bvh_info_tree(s->info, fb, node_bytes, leaf_param);
     if (hipDeviceSynchronize() != hipSuccess) return broke(RRT_E_HIP, "hipDeviceSynchronize failed");
     s->failed_update.clear();
+    keep_world_rows(s, g);
     s->n_updates++;
     s->last_update_allocs = own_allocs + (s->builder->allocations() - allocs_before);
     s->last_update_levels = levels;
@@ -2390,7 +2525,8 @@ int32_t rrt_build_bvh_binned(const RrtSphere *spheres, uint32_t n_spheres, const
 // The refit: everything after the checks is enqueued on `stream`; no host read, no wait for the
 // device (but for the staging buffer of the refit before, which its copy has long left).
 // A geometry refit stages the quad and light rows behind the spheres' and motion's; its staging
-// buffer is sized for all four at once, whichever of them the call brings.
+// buffer is sized for all four at once, whichever of them the call brings. A world refit stages the
+// media and the boundary quads behind those, its buffer sized for all six.
 static int32_t refit_scene(RrtScene *s, const std::string &fn, const RrtSphere *spheres, uint32_t n_spheres, const float *motion,
                            bool has_motion, const GeometryChange &g, bool geometry, void *stream) {
     if (!s->failed_update.empty())
@@ -2410,11 +2546,18 @@ static int32_t refit_scene(RrtScene *s, const std::string &fn, const RrtSphere *
         if (int rc = ensure_change_buffers(s, fn, own_allocs)) return rc;
     }
     if (int rc = ensure_geometry_buffers(s, g, own_allocs)) return rc;
+    // the first world change: blocking copies of the scene's own rows, which no launch in flight reads
+    if (int rc = ensure_world_buffers(s, g, own_allocs)) return rc;
     const uint32_t n_quads = g.quads ? s->base.n_quads : 0u, n_lights = g.lights ? s->base.n_lights : 0u;
     const size_t quad_bytes = (size_t)n_quads * sizeof(RrtQuad), light_bytes = (size_t)n_lights * sizeof(RrtLight);
     const size_t quads_at = sphere_bytes + motion_bytes, lights_at = quads_at + (size_t)s->base.n_quads * sizeof(RrtQuad);
+    const uint32_t n_media = g.media ? s->base.n_media : 0u, n_bquads = g.bquads ? s->n_bquads : 0u;
+    const uint32_t n_medium_boxes = (n_media || n_bquads) ? s->base.n_media : 0u;
+    const size_t media_bytes = (size_t)n_media * sizeof(RrtMedium), bquad_bytes = (size_t)n_bquads * sizeof(RrtQuad);
+    const size_t media_at = lights_at + (size_t)s->base.n_lights * sizeof(RrtLight);
+    const size_t bquads_at = media_at + (size_t)s->base.n_media * sizeof(RrtMedium);
     const size_t stage_need = std::max<size_t>(
-        geometry ? lights_at + (size_t)s->base.n_lights * sizeof(RrtLight) : sphere_bytes + motion_bytes, 16);
+        g.world ? bquads_at + (size_t)s->n_bquads * sizeof(RrtQuad) : geometry ? media_at : sphere_bytes + motion_bytes, 16);
     if (s->stage_cap < stage_need) {  // the first refit, or the first geometry refit after sphere refits
         if (s->h_stage) {
             if (s->n_refits) HIP_TRY(hipEventSynchronize(s->ev_staged), "hipEventSynchronize");
@@ -2446,12 +2589,21 @@ static int32_t refit_scene(RrtScene *s, const std::string &fn, const RrtSphere *
         return broke(RRT_E_HIP, "copying the quads failed");
     if (light_bytes && hipMemcpyAsync(s->d_src_lights, s->h_stage + lights_at, light_bytes, hipMemcpyHostToDevice, st) != hipSuccess)
         return broke(RRT_E_HIP, "copying the lights failed");
+    if (media_bytes) std::memcpy(s->h_stage + media_at, g.media, media_bytes);
+    if (bquad_bytes) std::memcpy(s->h_stage + bquads_at, g.bquads, bquad_bytes);
+    if (media_bytes && hipMemcpyAsync(s->d_src_media, s->h_stage + media_at, media_bytes, hipMemcpyHostToDevice, st) != hipSuccess)
+        return broke(RRT_E_HIP, "copying the media failed");
+    if (bquad_bytes && hipMemcpyAsync(s->d_src_bquads, s->h_stage + bquads_at, bquad_bytes, hipMemcpyHostToDevice, st) != hipSuccess)
+        return broke(RRT_E_HIP, "copying the boundary quads failed");
     if (hipEventRecord(s->ev_staged, st) != hipSuccess) return broke(RRT_E_HIP, "hipEventRecord failed");
     const float *d_motion = has_motion ? s->d_src_motion : nullptr;
     if (rrt::launch_sphere_boxes(n_spheres, s->d_src_spheres, d_motion, s->builder->device_boxes(), st) != hipSuccess)
         return broke(RRT_E_HIP, "the sphere-box launch failed");
     if (rrt::launch_quad_boxes(n_quads, s->d_src_quads, s->builder->device_boxes() + n_spheres, st) != hipSuccess)
         return broke(RRT_E_HIP, "the quad-box launch failed");
+    if (rrt::launch_medium_boxes(n_medium_boxes, s->d_src_media, s->d_src_bquads, s->n_bquads,
+                                 s->builder->device_boxes() + n_spheres + s->base.n_quads, st) != hipSuccess)
+        return broke(RRT_E_HIP, "the medium-box launch failed");
     if (s->builder->refit(st) != hipSuccess) return broke(RRT_E_HIP, "device BVH: refit failed");
     if (s->builder->emit_refit(s->info.node_stride, s->d_nodes, s->nodes_cap, st) != hipSuccess)
         return broke(RRT_E_HIP, "device BVH: emit failed");
@@ -2459,13 +2611,19 @@ static int32_t refit_scene(RrtScene *s, const std::string &fn, const RrtSphere *
         return broke(RRT_E_HIP, "the quad-record launch failed");
     if (rrt::launch_lights(n_lights, s->d_src_lights, s->d_light_quad, s->d_lights, s->d_quads, st) != hipSuccess)
         return broke(RRT_E_HIP, "the light launch failed");
+    if (rrt::launch_medium_records(n_media, s->d_src_media, s->base.n_quads, s->d_media, st) != hipSuccess)
+        return broke(RRT_E_HIP, "the medium-record launch failed");
+    if (rrt::launch_bquad_records(n_bquads, s->d_src_bquads, s->d_quads ? s->d_quads + s->base.n_quads : nullptr, st) != hipSuccess)
+        return broke(RRT_E_HIP, "the boundary-quad launch failed");
     if (rrt::launch_leaf_tables(leaf_tables_of(s, d_motion), st) != hipSuccess) return broke(RRT_E_HIP, "the leaf-table launch failed");
     if (hipEventRecord(s->ev_refit_done, st) != hipSuccess) return broke(RRT_E_HIP, "hipEventRecord failed");
     if (s->f64 && g.quads) s->quads_in_sphere32 = g.quads_in32;  // the quads' part, from the caller's rows
     if (s->f64) sphere32_recheck(s, spheres, n_spheres);
+    keep_world_rows(s, g);
     s->n_refits++;
     s->last_refit_allocs = own_allocs + (s->builder->allocations() - allocs_before);
-    s->last_refit_launches = (n_spheres ? 1u : 0u) + (n_quads ? 2u : 0u) + (n_lights ? 1u : 0u) + s->builder->refit_launches() + 2u;
+    s->last_refit_launches = (n_spheres ? 1u : 0u) + (n_quads ? 2u : 0u) + (n_lights ? 1u : 0u) + (n_medium_boxes ? 1u : 0u) +
+                             (n_media ? 1u : 0u) + (n_bquads ? 1u : 0u) + s->builder->refit_launches() + 2u;
     s->last_refit_form = s->builder->refit_form();
     return RRT_OK;
 }
@@ -2483,6 +2641,22 @@ int32_t rrt_scene_refit_geometry(RrtScene *scene, const RrtSceneGeometry *geomet
     bool has_motion = false;
     GeometryChange g;
     if (int rc = check_geometry_change(scene, fn, geometry, has_motion, g)) return rc;
+    return refit_scene(scene, fn, geometry->spheres, geometry->n_spheres, geometry->sphere_motion, has_motion, g, true, stream);
+}
+
+int32_t rrt_scene_update_world(RrtScene *scene, const RrtSceneGeometry *geometry, const RrtSceneMedia *media, void *stream) {
+    const std::string fn = "rrt_scene_update_world: ";
+    bool has_motion = false;
+    GeometryChange g;
+    if (int rc = check_world_change(scene, fn, geometry, media, true, has_motion, g)) return rc;
+    return update_scene(scene, fn, geometry->spheres, geometry->n_spheres, geometry->sphere_motion, has_motion, g, stream);
+}
+
+int32_t rrt_scene_refit_world(RrtScene *scene, const RrtSceneGeometry *geometry, const RrtSceneMedia *media, void *stream) {
+    const std::string fn = "rrt_scene_refit_world: ";
+    bool has_motion = false;
+    GeometryChange g;
+    if (int rc = check_world_change(scene, fn, geometry, media, false, has_motion, g)) return rc;
     return refit_scene(scene, fn, geometry->spheres, geometry->n_spheres, geometry->sphere_motion, has_motion, g, true, stream);
 }
 
@@ -2506,10 +2680,13 @@ int32_t rrt_refit_bvh_binned(const RrtSphere *built_spheres, uint32_t n_spheres,
                                    new_motion, nullptr, nodes_out, nodes_cap, prim_order_out, info, sah_out);
 }
 
-int32_t rrt_refit_bvh_binned_ex(const RrtSphere *built_spheres, uint32_t n_spheres, const RrtSceneExt *built_ext,
+// The refit twins' common body: the built tree with its boxes recomputed from the new rows (a null
+// array of new_quads, new_media or new_bquads: the built one; new_motion null: all zero).
+static int32_t refit_bvh_binned(const RrtSphere *built_spheres, uint32_t n_spheres, const RrtSceneExt *built_ext,
                                 uint32_t max_leaf, double node_cost, uint32_t node_stride, const RrtSphere *new_spheres,
-                                const float *new_motion, const RrtQuad *new_quads, void *nodes_out, size_t nodes_cap,
-                                uint32_t *prim_order_out, RrtBvhInfo *info, double *sah_out) {
+                                const float *new_motion, const RrtQuad *new_quads, const RrtMedium *new_media,
+                                const RrtQuad *new_bquads, void *nodes_out, size_t nodes_cap, uint32_t *prim_order_out,
+                                RrtBvhInfo *info, double *sah_out) {
     if (n_spheres && (!built_spheres || !new_spheres)) return fail(RRT_E_INVALID, "null spheres");
     const ExtView ex(built_ext);
     for (uint32_t m = 0; m < ex.n_media; ++m)
@@ -2525,6 +2702,13 @@ int32_t rrt_refit_bvh_binned_ex(const RrtSphere *built_spheres, uint32_t n_spher
         in.boxes[i] = rrt::sphere_box(new_spheres[i].center_radius, new_motion ? new_motion + 4 * (size_t)i : nullptr);
     for (uint32_t j = 0; new_quads && j < ex.n_quads; ++j)
         in.boxes[n_spheres + j] = rrt::quad_box(new_quads[j].q, new_quads[j].u, new_quads[j].v);
+    for (uint32_t m = 0; (new_media || new_bquads) && m < ex.n_media; ++m) {
+        const RrtMedium &was = ex.media[m], &md = new_media ? new_media[m] : was;
+        if (md.boundary_kind != was.boundary_kind || md.first != was.first || md.count != was.count)
+            return fail(RRT_E_INVALID, "medium " + std::to_string(m) + ": boundary_kind, first or count differs from the "
+                                       "built scene's entry");
+        in.boxes[n_spheres + ex.n_quads + m] = rrt::medium_box(md, new_bquads ? new_bquads : ex.bquads);
+    }
     bvhb::refit_raw(bt.raw.data(), bt.sum.n_nodes, bt.objs.data(), in.boxes.data());
     double root_box[6];
     bvhb::root_box_of(bt.raw[0], root_box);
@@ -2558,6 +2742,31 @@ int32_t rrt_refit_bvh_binned_ex(const RrtSphere *built_spheres, uint32_t n_spher
     std::memcpy(nodes_out, fb.bytes.data(), fb.bytes.size());
     if (order.size()) std::memcpy(prim_order_out, order.data(), order.size() * sizeof(uint32_t));
     return RRT_OK;
+}
+
+int32_t rrt_refit_bvh_binned_ex(const RrtSphere *built_spheres, uint32_t n_spheres, const RrtSceneExt *built_ext,
+                                uint32_t max_leaf, double node_cost, uint32_t node_stride, const RrtSphere *new_spheres,
+                                const float *new_motion, const RrtQuad *new_quads, void *nodes_out, size_t nodes_cap,
+                                uint32_t *prim_order_out, RrtBvhInfo *info, double *sah_out) {
+    return refit_bvh_binned(built_spheres, n_spheres, built_ext, max_leaf, node_cost, node_stride, new_spheres, new_motion,
+                            new_quads, nullptr, nullptr, nodes_out, nodes_cap, prim_order_out, info, sah_out);
+}
+
+int32_t rrt_refit_bvh_binned_world(const RrtSphere *built_spheres, uint32_t n_spheres, const RrtSceneExt *built_ext,
+                                   uint32_t max_leaf, double node_cost, uint32_t node_stride, const RrtSphere *new_spheres,
+                                   const RrtSceneExt *new_ext, void *nodes_out, size_t nodes_cap, uint32_t *prim_order_out,
+                                   RrtBvhInfo *info, double *sah_out) {
+    const std::string fn = "rrt_refit_bvh_binned_world: ";
+    const ExtView built(built_ext), ex(new_ext);
+    if (ex.quads && ex.n_quads != built.n_quads)
+        return fail(RRT_E_INVALID, fn + "n_quads is " + std::to_string(ex.n_quads) + ", the built scene's is " + std::to_string(built.n_quads));
+    if (ex.media && ex.n_media != built.n_media)
+        return fail(RRT_E_INVALID, fn + "n_media is " + std::to_string(ex.n_media) + ", the built scene's is " + std::to_string(built.n_media));
+    if (ex.bquads && ex.n_bquads != built.n_bquads)
+        return fail(RRT_E_INVALID, fn + "n_boundary_quads is " + std::to_string(ex.n_bquads) + ", the built scene's is " +
+                                       std::to_string(built.n_bquads));
+    return refit_bvh_binned(built_spheres, n_spheres, built_ext, max_leaf, node_cost, node_stride, new_spheres, ex.motion,
+                            ex.quads, ex.media, ex.bquads, nodes_out, nodes_cap, prim_order_out, info, sah_out);
 }
 
 int32_t rrt_tile_rows(uint32_t height, const RrtTile *tile, uint32_t *rows_out) {
@@ -2731,6 +2940,28 @@ extern "C" int32_t rrt_testing_quad_records(const RrtQuad *quads, uint32_t n_qua
     return RRT_OK;
 }
 
+// Test support: the host compilation of rrt_medium_form.h (the device's: k_medium_boxes, k_medium_records).
+extern "C" int32_t rrt_testing_medium_records(const RrtMedium *media, uint32_t n_media, const RrtQuad *boundary_quads,
+                                              uint32_t n_boundary_quads, uint32_t n_quads, double *boxes6, void *gmedium) {
+    const std::string fn = "rrt_testing_medium_records: ";
+    if (n_media && !media) return fail(RRT_E_INVALID, fn + "null media");
+    for (uint32_t m = 0; m < n_media; ++m) {
+        const RrtMedium &md = media[m];
+        if (md.boundary_kind == RRT_BOUNDARY_QUADS) {
+            if (md.count == 0 || (uint64_t)md.first + md.count > n_boundary_quads || !boundary_quads)
+                return fail(RRT_E_INVALID, fn + "medium " + std::to_string(m) + ": boundary quad range out of bounds");
+        } else if (md.boundary_kind != RRT_BOUNDARY_SPHERE) {
+            return fail(RRT_E_INVALID, fn + "medium " + std::to_string(m) + ": unknown boundary_kind");
+        }
+        if (boxes6) {
+            const bvhb::Box6 b = rrt::medium_box(md, boundary_quads);
+            for (int a = 0; a < 3; ++a) boxes6[6 * (size_t)m + a] = b.mn[a], boxes6[6 * (size_t)m + 3 + a] = b.mx[a];
+        }
+        if (gmedium) static_cast<rrt::GMedium *>(gmedium)[m] = rrt::medium_record(md, n_quads);
+    }
+    return RRT_OK;
+}
+
 // Test support: one of the scene's device tables, copied back.
 extern "C" int32_t rrt_testing_scene_read_table(RrtScene *scene, uint32_t what, void *out, size_t cap, size_t *bytes_out) {
     if (!scene || !bytes_out) return fail(RRT_E_INVALID, "rrt_testing_scene_read_table: null scene or bytes_out");
@@ -2750,6 +2981,7 @@ extern "C" int32_t rrt_testing_scene_read_table(RrtScene *scene, uint32_t what, 
     case RRT_TABLE_GQUADS64: src = scene->d_quads64, bytes = (size_t)scene->base.n_quads * sizeof(rrt::GQuad64); break;
     case RRT_TABLE_QUAD_ROWS: src = scene->d_quad_rows, bytes = (size_t)scene->base.n_quads * 2 * sizeof(float4); break;
     case RRT_TABLE_GLIGHTS: src = scene->d_lights, bytes = (size_t)scene->base.n_lights * sizeof(rrt::GLight); break;
+    case RRT_TABLE_GMEDIA: src = scene->d_media, bytes = (size_t)scene->base.n_media * sizeof(rrt::GMedium); break;
     default: return fail(RRT_E_INVALID, "rrt_testing_scene_read_table: unknown table");
     }
     if (!src) bytes = 0;  // a table this scene does not hold

@@ -427,7 +427,8 @@ constexpr uint32_t kFlagDeviceBvh = 0x10u;
 // (host pointers). build: the tree of one shape, kept on the device in raw f64 form; may be called
 // again for another shape. emit: the last build's nodes in the 80-B or 32-B format as a fresh
 // hipMalloc'd array the caller owns, and the leaf order (n_tree entries) to the host. Synchronous,
-// on the default stream.
+// on the default stream. Every array is sized for n_boxes primitives, the scene's count, so that
+// set_objects() can put any of them into the tree later.
 namespace bvhb {
 struct Box6;
 struct Summary;
@@ -439,6 +440,11 @@ public:
     DeviceBvhBuilder(const DeviceBvhBuilder &) = delete;
     DeviceBvhBuilder &operator=(const DeviceBvhBuilder &) = delete;
     hipError_t upload(const bvhb::Box6 *boxes, uint32_t n_boxes, const uint32_t *objs, uint32_t n_tree);
+    // Replaces the tree's primitives before a build (rrt_scene_update_world: a medium enters or
+    // leaves the tree): 2 <= n_tree <= n_boxes indices into the boxes, in their original order. One
+    // blocking copy, no allocation. The tree held stays the last build's until build() runs again.
+    hipError_t set_objects(const uint32_t *objs, uint32_t n_tree);
+    uint32_t n_tree() const;
     hipError_t build(uint32_t max_leaf, double node_cost, bvhb::Summary *out);
     hipError_t emit(uint32_t stride, uint8_t **d_nodes_out, uint32_t *order_out);
     uint32_t levels() const;  // of the last build: one blocking read each
@@ -446,8 +452,8 @@ public:
     // another upload: the caller rewrites device_boxes() in place (n_boxes rows, same primitives),
     // build() starts from the uploaded order again, and emit_into() packs the nodes into a buffer the
     // caller owns (cap_bytes >= n_nodes x stride, else hipErrorInvalidValue). reserve() sizes the
-    // per-level arrays for the widest level any tree of n_tree primitives can have (n_tree / 2
-    // tasks), after which build() allocates nothing. device_order(): the last build's leaf order on
+    // per-level arrays for the widest level any tree over the n_boxes primitives can have (n_boxes / 2
+    // tasks), after which build() allocates nothing, whatever set_objects() brings. device_order(): the last build's leaf order on
     // the device. allocations(): hipMalloc calls made by this builder so far.
     bvhb::Box6 *device_boxes();
     const uint32_t *device_order() const;
@@ -486,7 +492,12 @@ private:
 //   launch_leaf_tables   one lane per leaf position: the per-primitive tables scene creation forms
 struct LeafTables {
     uint32_t n_prims, n_spheres, book2, f64;
-    const uint32_t *order;     // leaf position -> primitive (spheres, then quads as n_spheres + j)
+    // leaf position -> primitive (spheres, then quads as n_spheres + j, then media as n_spheres +
+    // n_quads + m): the builder's n_tree entries, then the unbounded media, held here by value
+    const uint32_t *order;
+    uint32_t n_tree, n_quads;
+    uint32_t unbounded[kMaxUnbounded];
+    const void *media;         // RrtMedium[n_media], source order (their material indices)
     const void *spheres;       // RrtSphere[n_spheres], source order
     const float *motion;       // n_spheres x 4, or null (all zero)
     const GMaterial *mats;     // the material table, source order
@@ -515,6 +526,19 @@ hipError_t launch_quad_records(uint32_t n, const void *d_quads, GQuad *gquads, G
                                uint32_t *quad_mat, hipStream_t stream = nullptr);
 hipError_t launch_lights(uint32_t n, const void *d_lights, const uint32_t *light_quad, GLight *glights, GQuad *gquads,
                          hipStream_t stream = nullptr);
+// rrt_scene_update_world / rrt_scene_refit_world (rrt_medium_form.h on the device), one lane per row:
+//   launch_medium_boxes    medium m's box into boxes[m] (the caller passes the builder's boxes +
+//                          n_spheres + n_quads); media = RrtMedium records whose quad ranges lie
+//                          within the n_bquads RrtQuad records of bquads (a lane whose range does not
+//                          writes nothing)
+//   launch_medium_records  medium m's GMedium into gmedia[m]
+//   launch_bquad_records   boundary quad k's GQuad into gquads[k] (the caller passes the scene's
+//                          GQuad array + n_quads)
+hipError_t launch_medium_boxes(uint32_t n, const void *d_media, const void *d_bquads, uint32_t n_bquads, void *d_boxes,
+                               hipStream_t stream = nullptr);
+hipError_t launch_medium_records(uint32_t n, const void *d_media, uint32_t n_quads, GMedium *gmedia,
+                                 hipStream_t stream = nullptr);
+hipError_t launch_bquad_records(uint32_t n, const void *d_bquads, GQuad *gquads, hipStream_t stream = nullptr);
 // Test support (rrt_testing_refit_form): force the refit's per-level launches (0) or its single
 // workgroup (1); -1: the automatic choice. False for another value.
 bool set_refit_form(int form);

@@ -5,10 +5,13 @@
 // row, plain vector stores; nothing here is worth tuning (a 10^5-sphere scene moves ~10 MB).
 // rrt_scene_update_geometry and rrt_scene_refit_geometry add the quads and the book-3 lights: their
 // boxes, GQuad / GQuad64 records, leaf-table rows and GLight records, all from rrt_quad_form.h, the
-// definition scene creation itself calls.
+// definition scene creation itself calls. rrt_scene_update_world and rrt_scene_refit_world add the
+// constant media: their boxes and GMedium records from rrt_medium_form.h, their boundary quads' GQuad
+// records and their leaf-table rows.
 #include "rrt_internal.h"
 #include "rrt_sphere_box.h"
 #include "rrt_quad_form.h"
+#include "rrt_medium_form.h"
 #include "../../include/rrt_hip.h"
 
 namespace rrt {
@@ -42,11 +45,24 @@ __device__ __forceinline__ float recip_f32(float r) { return (float)(1.0 / (doub
 __global__ __launch_bounds__(kBlk) void k_leaf_tables(LeafTables t) {
     const uint32_t i = blockIdx.x * kBlk + threadIdx.x;
     if (i >= t.n_prims) return;
-    const uint32_t o = t.order[i];
+    // the builder's order holds the tree's primitives; the unbounded media follow them
+    // (selected by compares: a lane-indexed read of the by-value array would go through scratch)
+    uint32_t o;
+    if (i < t.n_tree) {
+        o = t.order[i];
+    } else {
+        const uint32_t k = i - t.n_tree;
+        o = k == 0u ? t.unbounded[0] : k == 1u ? t.unbounded[1] : k == 2u ? t.unbounded[2] : t.unbounded[3];
+    }
     float4 cr, mo = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     GMaterial mtl;
     uint32_t mat;
-    if (o >= t.n_spheres) {  // a quad: its stored plane, (q, tag) and (normal, D)
+    if (o >= t.n_spheres + t.n_quads) {  // a medium: its tag, no geometry, its phase material
+        const uint32_t m = o - t.n_spheres - t.n_quads;
+        cr = medium_row_cr(t.n_quads, m);
+        mat = reinterpret_cast<const RrtMedium *>(t.media)[m].material_index;
+        mtl = t.mats[mat];
+    } else if (o >= t.n_spheres) {  // a quad: its stored plane, (q, tag) and (normal, D)
         const uint32_t j = o - t.n_spheres;
         cr = t.quad_rows[2u * j];
         mo = t.quad_rows[2u * j + 1u];
@@ -122,7 +138,59 @@ __global__ __launch_bounds__(kBlk) void k_lights(uint32_t n, const RrtLight *lig
     if (L.kind == RRT_LIGHT_QUAD) gquads[at] = quad_record32(L.a, L.u, L.v);
 }
 
+// ---- constant media (rrt_scene_update_world, rrt_scene_refit_world) ------------------------------
+static_assert(sizeof(RrtMedium) == 48 && sizeof(GMedium) == 32, "RrtMedium is 48 B, GMedium 32 B");
+static_assert(kMaxUnbounded == 4u, "k_leaf_tables selects among four unbounded media");
+
+// A lane loops over its medium's boundary quads (a make_box has 6).
+__global__ __launch_bounds__(kBlk) void k_medium_boxes(uint32_t n, const RrtMedium *media, const RrtQuad *bquads,
+                                                       uint32_t n_bquads, bvhb::Box6 *boxes) {
+    const uint32_t m = blockIdx.x * kBlk + threadIdx.x;
+    if (m >= n) return;
+    const RrtMedium md = media[m];
+    if (md.boundary_kind != RRT_BOUNDARY_SPHERE && ((uint64_t)md.first + md.count > n_bquads)) return;
+    boxes[m] = medium_box(md, bquads);
+}
+
+__global__ __launch_bounds__(kBlk) void k_medium_records(uint32_t n, const RrtMedium *media, uint32_t n_quads,
+                                                         GMedium *gmedia) {
+    const uint32_t m = blockIdx.x * kBlk + threadIdx.x;
+    if (m >= n) return;
+    gmedia[m] = medium_record(media[m], n_quads);
+}
+
+// k_quad_records without the rows and the material: a boundary quad is no primitive of the scene.
+__global__ __launch_bounds__(kBlk) void k_bquad_records(uint32_t n, const RrtQuad *bquads, GQuad *gquads) {
+    const uint32_t k = blockIdx.x * kBlk + threadIdx.x;
+    if (k >= n) return;
+    const Quv r = load_quv(bquads[k].q);
+    gquads[k] = quad_record32(r.q, r.u, r.v);
+}
+
 }  // namespace
+
+hipError_t launch_medium_boxes(uint32_t n, const void *d_media, const void *d_bquads, uint32_t n_bquads, void *d_boxes,
+                               hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_medium_boxes, dim3((n + kBlk - 1) / kBlk), dim3(kBlk), 0, stream, n,
+                       reinterpret_cast<const RrtMedium *>(d_media), reinterpret_cast<const RrtQuad *>(d_bquads), n_bquads,
+                       reinterpret_cast<bvhb::Box6 *>(d_boxes));
+    return hipGetLastError();
+}
+
+hipError_t launch_medium_records(uint32_t n, const void *d_media, uint32_t n_quads, GMedium *gmedia, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_medium_records, dim3((n + kBlk - 1) / kBlk), dim3(kBlk), 0, stream, n,
+                       reinterpret_cast<const RrtMedium *>(d_media), n_quads, gmedia);
+    return hipGetLastError();
+}
+
+hipError_t launch_bquad_records(uint32_t n, const void *d_bquads, GQuad *gquads, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_bquad_records, dim3((n + kBlk - 1) / kBlk), dim3(kBlk), 0, stream, n,
+                       reinterpret_cast<const RrtQuad *>(d_bquads), gquads);
+    return hipGetLastError();
+}
 
 hipError_t launch_quad_boxes(uint32_t n, const void *d_quads, void *d_boxes, hipStream_t stream) {
     if (n == 0) return hipSuccess;

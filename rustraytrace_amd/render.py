@@ -369,6 +369,36 @@ def refit_bvh_binned(built_scene: SceneData, new_spheres, new_motion, max_leaf: 
     return nodes, order[:n_prims], info.as_dict(), float(sah.value)
 
 
+def refit_bvh_binned_world(built_scene: SceneData, new_scene: SceneData, max_leaf: int, node_cost: float, node_stride: int):
+    """rrt_refit_bvh_binned_world (host only): build_bvh_binned's tree of `built_scene` with its boxes
+    recomputed over new_scene's spheres, motion, quads, media and boundary quads (the same counts and
+    medium structure), the classification and leaf order kept: the specification of
+    DeviceScene.refit_world. Returns (node bytes, leaf order, info dict, sah)."""
+    lib = _lib.load()
+    info = _lib.RrtBvhInfo()
+    sah = ctypes.c_double(0.0)
+    n = len(built_scene.spheres)
+    sp = np.ascontiguousarray(new_scene.spheres, dtype=_lib.SPHERE_DTYPE)
+    assert len(sp) == n, "a refit keeps the sphere count"
+    ext, keep = scene_ext(built_scene)
+    new_ext, keep_new = scene_ext(new_scene)
+    n_prims = n + (0 if ext is None else ext.n_quads + ext.n_media)
+    extp = ctypes.byref(ext) if ext is not None else None
+    new_extp = ctypes.byref(new_ext) if new_ext is not None else None
+
+    def refit(nodes_p, cap, order_p):
+        return lib.rrt_refit_bvh_binned_world(_lib.ptr(built_scene.spheres), n, extp, int(max_leaf), float(node_cost),
+                                              int(node_stride), _lib.ptr(sp), new_extp, nodes_p, cap, order_p,
+                                              ctypes.byref(info), ctypes.byref(sah))
+
+    _lib.check(refit(None, 0, None))
+    nodes = np.zeros(info.node_bytes, dtype=np.uint8)
+    order = np.zeros(max(n_prims, 1), dtype=np.uint32)
+    _lib.check(refit(_lib.ptr(nodes), nodes.size, _lib.ptr(order)))
+    del keep, keep_new
+    return nodes, order[:n_prims], info.as_dict(), float(sah.value)
+
+
 def decode_bvh2(nodes: np.ndarray, stride: int):
     """Decode build_bvh's width-2 node bytes (rrt_internal.h; stride = info["node_stride"]: 80 =
     GNode, sign-ordered lo/hi/lo planes, 32 = GNodeH, f16 planes): per node and child, box lo/hi (n, 2, 3),
@@ -543,6 +573,45 @@ class DeviceScene:
         _lib.check(self._lib.rrt_scene_refit_geometry(self._h, ctypes.byref(g), ctypes.c_void_p(stream_ptr)))
         self.scene = new
 
+    def _media(self, new, media, boundary_quads):
+        """(RrtSceneMedia or None, the replaced SceneData) of a world change; the struct borrows the
+        new scene's arrays."""
+        if media is None and boundary_quads is None:
+            return None, new
+        wm = _lib.RrtSceneMedia()
+        if media is not None:
+            new = dataclasses.replace(new, media=np.ascontiguousarray(media, dtype=_lib.MEDIUM_DTYPE).copy())
+            wm.media, wm.n_media = new.media.ctypes.data, len(new.media)
+        if boundary_quads is not None:
+            new = dataclasses.replace(new, boundary_quads=np.ascontiguousarray(boundary_quads, dtype=_lib.QUAD_DTYPE).copy())
+            wm.boundary_quads, wm.n_boundary_quads = new.boundary_quads.ctypes.data, len(new.boundary_quads)
+        return wm, new
+
+    def update_world(self, spheres=None, motion=None, quads=None, lights=None, media=None, boundary_quads=None,
+                     stream_ptr: int = 0) -> None:
+        """rrt_scene_update_world: update_geometry extended to the constant media and their boundary quads
+        (None = keep them), on scenes with or without media: which media are tested outside the tree is
+        decided again from the new inputs, the BVH rebuilt on the device over the rest and everything
+        derived re-formed there; the scene then equals one freshly created from the new inputs. Waits
+        for the stream, returns synchronised."""
+        g, new = self._geometry(spheres, motion, quads, lights)
+        wm, new = self._media(new, media, boundary_quads)
+        _lib.check(self._lib.rrt_scene_update_world(self._h, ctypes.byref(g), None if wm is None else ctypes.byref(wm),
+                                                    ctypes.c_void_p(stream_ptr)))
+        self.scene = new
+
+    def refit_world(self, spheres=None, motion=None, quads=None, lights=None, media=None, boundary_quads=None,
+                    stream_ptr: int = 0) -> None:
+        """rrt_scene_refit_world: the same replacement as update_world, but the tree keeps its topology,
+        its leaf order and the last build's choice of the media tested outside it, and only its boxes
+        are recomputed; everything is enqueued on the stream and the call does not wait for the device.
+        tree_cost() tells when to rebuild."""
+        g, new = self._geometry(spheres, motion, quads, lights)
+        wm, new = self._media(new, media, boundary_quads)
+        _lib.check(self._lib.rrt_scene_refit_world(self._h, ctypes.byref(g), None if wm is None else ctypes.byref(wm),
+                                                   ctypes.c_void_p(stream_ptr)))
+        self.scene = new
+
     def tree_cost(self) -> dict:
         """rrt_scene_tree_cost: the SAH cost of the tree held now, of the last build's tree, and the
         refits since that build. Synchronises the device."""
@@ -559,9 +628,9 @@ class DeviceScene:
 
     def read_table(self, name: str) -> np.ndarray:
         """rrt_testing_scene_read_table (test support): one of the scene's device tables (a
-        _lib.SCENE_TABLES or _lib.SCENE_GEOMETRY_TABLES name) as a flat array; empty when the scene does
-        not hold it."""
-        code, dtype = (_lib.SCENE_TABLES.get(name) or _lib.SCENE_GEOMETRY_TABLES[name])
+        _lib.SCENE_TABLES, _lib.SCENE_GEOMETRY_TABLES or _lib.SCENE_MEDIA_TABLES name) as a flat array;
+        empty when the scene does not hold it."""
+        code, dtype = (_lib.SCENE_TABLES.get(name) or _lib.SCENE_GEOMETRY_TABLES.get(name) or _lib.SCENE_MEDIA_TABLES[name])
         n = ctypes.c_size_t(0)
         _lib.check(self._lib.rrt_testing_scene_read_table(self._h, code, None, 0, ctypes.byref(n)))
         out = np.zeros(n.value // dtype.itemsize, dtype=dtype)
