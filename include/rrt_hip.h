@@ -243,6 +243,22 @@ typedef struct RrtOverrides {
  * 65535 BVH nodes; the message names this flag and the item. A book-1 scene created with the flag
  * renders the bits RRT_FLAG_F64 alone renders. RRT_FLAG_F64 alone keeps refusing book-2 data. */
 #define RRT_FLAG_F64_BOOK2 0x20u
+/* The fast builder (additive; RRT_ABI_VERSION is unchanged): scene creation and every later
+ * rrt_scene_update_* build the tree on the device by an LBVH (rrt_bvh_lbvh.h: 30-bit Morton codes of
+ * the centroids, one sort, Karras' topology) instead of the binned SAH builder: a fixed number of
+ * launches whatever the tree's depth and one blocking read per build, against the binned builder's
+ * eight launches and one read per level. The tree traces slower (DESIGN.md section 5 has both numbers per
+ * scene); it is the choice for geometry that moves too much for a refit. Implies RRT_FLAG_DEVICE_BVH
+ * and is accepted wherever that flag is; RRT_BVH_WIDTH=4 is refused (RRT_E_INVALID), RRT_BVH_SPLIT,
+ * RRT_SAH_CT and RRT_F64_SAH_CT_LDS are ignored (no SAH decision is made), RRT_MAX_LEAF and
+ * RRT_MAX_LEAF_GLOBAL apply. The composition is the device flag's: the LDS shape (leaves of up to 3)
+ * kept if it fits, else the global shape (single-primitive leaves, 32-B nodes), else the host path's
+ * fallbacks; both shapes come out of one sorted order, so no shape is built twice. The bytes are
+ * those of rrt_build_bvh_lbvh for the kept shape, whose leaf size RrtBvhInfo.max_leaf_param reports.
+ * A tree of at most one primitive is written by the host builder. The refits keep the tree's
+ * topology and rrt_scene_tree_cost works, as for the binned builder; rrt_scene_set_builder switches
+ * between the two. Without the flag nothing changes. */
+#define RRT_FLAG_FAST_BVH 0x40u
 
 /* ---- error codes ------------------------------------------------------------------ */
 #define RRT_OK 0
@@ -419,6 +435,14 @@ int32_t rrt_build_bvh_ex(const RrtSphere *spheres, uint32_t n_spheres, const Rrt
 int32_t rrt_build_bvh_binned(const RrtSphere *spheres, uint32_t n_spheres, const RrtSceneExt *ext, uint32_t max_leaf,
                              double node_cost, uint32_t node_stride, void *nodes_out, size_t nodes_cap,
                              uint32_t *prim_order_out, RrtBvhInfo *info);
+
+/* Host-only: the tree RRT_FLAG_FAST_BVH builds for one shape and node format, by the sequential host
+ * twin of the device LBVH builder (rrt_bvh_lbvh.h on both sides, same bytes). Sizing protocol,
+ * primitive order, unbounded media and refusals are rrt_build_bvh_binned's; there is no node_cost
+ * because no SAH decision is made. RRT_BVH_WIDTH=4 is refused. */
+int32_t rrt_build_bvh_lbvh(const RrtSphere *spheres, uint32_t n_spheres, const RrtSceneExt *ext, uint32_t max_leaf,
+                           uint32_t node_stride, void *nodes_out, size_t nodes_cap, uint32_t *prim_order_out,
+                           RrtBvhInfo *info);
 
 /* The node array and leaf order the created scene holds, whichever builder made them: nodes_out of
  * at least rrt_scene_bvh_info's node_bytes, prim_order_out of n_spheres + n_quads + n_media entries
@@ -614,6 +638,24 @@ int32_t rrt_refit_bvh_binned_world(const RrtSphere *built_spheres, uint32_t n_sp
                                    const RrtSceneExt *new_ext,
                                    void *nodes_out, size_t nodes_cap, uint32_t *prim_order_out,
                                    RrtBvhInfo *info, double *sah_out);
+
+/* Host-only: rrt_refit_bvh_binned_world over the tree of rrt_build_bvh_lbvh: the specification of the
+ * three refits of a scene whose current tree the fast builder made. sah_out weighs a node child by 2
+ * (what rrt_scene_tree_cost uses for such an f32 scene; an f64 scene's LDS shape weighs it by 1.5). */
+int32_t rrt_refit_bvh_lbvh_world(const RrtSphere *built_spheres, uint32_t n_spheres,
+                                 const RrtSceneExt *built_ext, uint32_t max_leaf, uint32_t node_stride,
+                                 const RrtSphere *new_spheres, const RrtSceneExt *new_ext,
+                                 void *nodes_out, size_t nodes_cap, uint32_t *prim_order_out,
+                                 RrtBvhInfo *info, double *sah_out);
+
+/* Chooses the builder of the scene's next rrt_scene_update_*: RRT_BUILDER_BINNED (quality) or
+ * RRT_BUILDER_LBVH (speed). Host state only. Works on every scene the device builder built (either
+ * flag, at least 2 primitives in the tree; RRT_E_INVALID otherwise, and for another value). Meant for
+ * fast rebuilds while things move and one quality rebuild when they stop. The first update after a
+ * switch may allocate the other builder's workspace; later ones allocate nothing. Refits and
+ * rrt_scene_tree_cost follow whichever build is current. */
+enum { RRT_BUILDER_BINNED = 0, RRT_BUILDER_LBVH = 1 };
+int32_t rrt_scene_set_builder(RrtScene *scene, uint32_t builder);
 
 /* ---- host-side callers of the boundary ------------------------------------------------ */
 
@@ -910,6 +952,23 @@ typedef struct RrtSceneRefitStats {
 } RrtSceneRefitStats;
 int32_t rrt_testing_scene_refit_stats(const RrtScene *scene, RrtSceneRefitStats *out);
 int32_t rrt_testing_refit_form(int32_t form);
+
+/* Test support, not part of the drop-in. rrt_testing_scene_build_stats: of the scene's last device
+ * build (creation or update): the builder (RRT_BUILDER_*), the kernel launches the builder made (a
+ * library sort counts as one), its blocking reads of device memory, the form (1: the single-workgroup
+ * LBVH launch, 0 otherwise) and the shapes it built (binned: builds run; LBVH: finishing passes).
+ * rrt_testing_lbvh_form: forces the LBVH's launch-per-phase form (0) or its single workgroup (1); -1
+ * restores the automatic choice. With the single workgroup forced a build over its primitive bound
+ * fails. Both forms write the same bytes. Process-wide. */
+typedef struct RrtSceneBuildStats {
+    uint64_t builder;
+    uint64_t launches;
+    uint64_t blocking_reads;
+    uint64_t form;
+    uint64_t shape_attempts;
+} RrtSceneBuildStats;
+int32_t rrt_testing_scene_build_stats(const RrtScene *scene, RrtSceneBuildStats *out);
+int32_t rrt_testing_lbvh_form(int32_t form);
 
 /* Test support, not part of the drop-in (no reference counterpart; RRT_ABI_VERSION is unchanged and
  * the Rust shim does not bind it): the launch shape the library picks for a scene, computed on the

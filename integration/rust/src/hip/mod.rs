@@ -53,6 +53,8 @@ mod imp {
     /// Scene creation builds the BVH on the device (RRT_FLAG_DEVICE_BVH); same kernels, same output
     /// contract, another tree.
     pub const RRT_FLAG_DEVICE_BVH: u32 = 0x10;
+    /// The device builds the BVH by the LBVH builder (RRT_FLAG_FAST_BVH; implies the device flag).
+    pub const RRT_FLAG_FAST_BVH: u32 = 0x40;
     /// ABI this shim was written against (RRT_ABI_VERSION).
     pub const RRT_ABI_VERSION: u32 = 11;
 
@@ -121,7 +123,7 @@ mod imp {
     /// (rrt_hip_render_rgb8 + the library's P3 writer: identical bytes, 3 B/pixel over PCIe).
     /// RRT_BOOKS_F64=1 renders with the books path's f64 arithmetic (rrt_hip_render_f64) and
     /// prints the bytes color.rs's write_color gives for the f64 sums.
-    /// RRT_DEVICE_BVH=1 adds RRT_FLAG_DEVICE_BVH to whichever entry runs.
+    /// RRT_DEVICE_BVH=1 adds RRT_FLAG_DEVICE_BVH to whichever entry runs, RRT_FAST_BVH=1 RRT_FLAG_FAST_BVH.
     fn render(camera: CameraUniform, spheres: &[SphereGpu], materials: &[MaterialGpu]) -> Result<(), String> {
         let abi = unsafe { rrt_hip_abi_version() };
         if abi != RRT_ABI_VERSION {
@@ -132,7 +134,8 @@ mod imp {
         let total_spp = camera.params_f[3].max(1.0) as u32; // cuda/mod.rs:384
         let n_gpus = gpus()?;
         let pixels = width as usize * height as usize;
-        let bvh_flag = if std::env::var("RRT_DEVICE_BVH").map(|v| v == "1").unwrap_or(false) { RRT_FLAG_DEVICE_BVH } else { 0 };
+        let bvh_flag = if std::env::var("RRT_DEVICE_BVH").map(|v| v == "1").unwrap_or(false) { RRT_FLAG_DEVICE_BVH } else { 0 }
+            | if std::env::var("RRT_FAST_BVH").map(|v| v == "1").unwrap_or(false) { RRT_FLAG_FAST_BVH } else { 0 };
         if std::env::var("RRT_BOOKS_F64").map(|v| v == "1").unwrap_or(false) {
             let mut accum = vec![0.0f64; pixels * 4];
             check(unsafe {

@@ -40,6 +40,7 @@ FLAG_QUIET = 0x2
 FLAG_BOOK3 = 0x4
 FLAG_F64 = 0x8  # the books path's f64 arithmetic (include/rrt_hip.h RRT_FLAG_F64)
 FLAG_DEVICE_BVH = 0x10  # scene creation builds the BVH on the device (RRT_FLAG_DEVICE_BVH)
+FLAG_FAST_BVH = 0x40  # the device builds the BVH by the LBVH builder (RRT_FLAG_FAST_BVH; implies FLAG_DEVICE_BVH)
 FLAG_F64_BOOK2 = 0x20  # the f64 books path for moving spheres, quads, checker textures (RRT_FLAG_F64_BOOK2)
 
 # Every symbol include/rrt_hip.h declares (checked by tests/test_abi.py).
@@ -115,6 +116,11 @@ EXPORTED_SYMBOLS = (
     "rrt_scene_refit_world",
     "rrt_refit_bvh_binned_world",
     "rrt_testing_medium_records",
+    "rrt_build_bvh_lbvh",
+    "rrt_refit_bvh_lbvh_world",
+    "rrt_scene_set_builder",
+    "rrt_testing_scene_build_stats",
+    "rrt_testing_lbvh_form",
 )
 
 # == RrtSceneTable (include/rrt_hip.h, test support): table -> (code, row dtype)
@@ -161,6 +167,14 @@ class RrtSceneRefitStats(ctypes.Structure):  # include/rrt_hip.h, test support
     _fields_ = [("refits", c_uint64), ("last_allocations", c_uint64), ("last_launches", c_uint64), ("last_form", c_uint64)]
 
 
+class RrtSceneBuildStats(ctypes.Structure):  # include/rrt_hip.h, test support
+    _fields_ = [("builder", c_uint64), ("launches", c_uint64), ("blocking_reads", c_uint64), ("form", c_uint64),
+                ("shape_attempts", c_uint64)]
+
+
+BUILDERS = {"binned": 0, "lbvh": 1}  # RRT_BUILDER_*
+
+
 class RrtTreeCost(ctypes.Structure):  # include/rrt_hip.h
     _fields_ = [("sah", c_double), ("sah_at_build", c_double), ("refits_since_build", c_uint64)]
 
@@ -169,6 +183,11 @@ def refit_form(form: int) -> None:
     """rrt_testing_refit_form (test support): force the refit's per-level launches (0) or its single
     workgroup (1); -1 restores the automatic choice."""
     check(load().rrt_testing_refit_form(int(form)))
+
+def lbvh_form(form: int) -> None:
+    """rrt_testing_lbvh_form (test support): force the fast builder's launch-per-phase form (0) or its
+    single workgroup (1); -1 restores the automatic choice."""
+    check(load().rrt_testing_lbvh_form(int(form)))
 
 # == RrtDeviceOp (include/rrt_hip.h, test support): op -> (code, f32 columns in, 32-bit words out)
 DEVICE_OPS = {
@@ -507,6 +526,11 @@ def load() -> ctypes.CDLL:
         "rrt_scene_update_world": (c_int32, [P, P, P, P]),
         "rrt_scene_refit_world": (c_int32, [P, P, P, P]),
         "rrt_refit_bvh_binned_world": (c_int32, [P, c_uint32, P, c_uint32, c_double, c_uint32, P, P, P, c_size_t, P, P, P]),
+        "rrt_build_bvh_lbvh": (c_int32, [P, c_uint32, P, c_uint32, c_uint32, P, c_size_t, P, P]),
+        "rrt_refit_bvh_lbvh_world": (c_int32, [P, c_uint32, P, c_uint32, c_uint32, P, P, P, c_size_t, P, P, P]),
+        "rrt_scene_set_builder": (c_int32, [P, c_uint32]),
+        "rrt_testing_scene_build_stats": (c_int32, [P, P]),
+        "rrt_testing_lbvh_form": (c_int32, [c_int32]),
         "rrt_testing_medium_records": (c_int32, [P, c_uint32, P, c_uint32, c_uint32, P, P]),
     }
     experiment = "RRT_LIB_PATH" in os.environ  # A/B of older builds: tolerate symbols they lack

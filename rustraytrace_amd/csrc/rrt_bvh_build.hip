@@ -11,8 +11,15 @@
 // scatter. After the last level pack writes GNode / GNodeH records from the raw f64 nodes.
 // Tasks of a level are ordered left to right by position, so the flags' prefix at a task's start
 // is the exclusive scan of the tasks' left counts, and node ids come out breadth-first.
+//
+// The same builder object also holds the fast builder (RRT_FLAG_FAST_BVH): the LBVH of rrt_bvh_lbvh.h
+// over the same boxes and tree storage, in a launch count that does not depend on the depth and with
+// one blocking read per build (lbvh_build / lbvh_finish, further down).
 #include "rrt_bvh_binned.h"
+#include "rrt_bvh_lbvh.h"
 #include "rrt_internal.h"
+
+#include <rocprim/device/device_radix_sort.hpp>  // the fast builder's sort of 64-bit keys, nothing else
 
 #include <algorithm>
 #include <atomic>
@@ -383,6 +390,303 @@ __global__ __launch_bounds__(kBlk) void k_sah_terms(uint32_t n_nodes, const RawN
     if (k == 0) *root_out = raw[0];
 }
 
+// ---- the fast builder (RRT_FLAG_FAST_BVH): rrt_bvh_lbvh.h, one lane per primitive or per node ----
+// Phases: centroid bounds, keys, sort, Karras' nodes with parent links, levels and the per-level node
+// counts of both candidate shapes, a sort of the numbering keys, then (one blocking read later, for
+// the shape the host keeps) numbers, links and the level table, and the binned builder's level-ordered
+// refit for the boxes. Every phase is a device function taking one element, called by a kernel per
+// phase (any size; the sorts are rocPRIM's) or, for small trees, by one workgroup that loops over the
+// elements with __syncthreads() between phases and sorts in LDS. Out-of-range values set an error
+// bit instead of an address.
+using namespace lbvh;
+
+constexpr uint32_t kLbvhSmallMax = 2048;  // primitives the single workgroup takes (its LDS sort buffer)
+enum : uint32_t { kLbvhErrLevel = 1u, kLbvhErrChild = 2u, kLbvhErrId = 4u };
+
+struct LbvhState {  // read once per build
+    uint32_t error;
+    uint32_t finished;              // the shape the single workgroup finished in its launch
+    uint32_t max_leaf[2];           // per shape: the largest leaf
+    uint32_t hist[2][kMaxLevels];   // per shape: kept nodes per level
+    Bounds b;
+};
+
+struct LbvhArgs {
+    uint32_t n, cap;       // primitives of the tree; rows every array holds
+    uint32_t leaf[2];      // the two shapes' leaf sizes
+    const Box6 *boxes;
+    const uint32_t *objs;  // the tree's primitives, source order
+    uint64_t *keys[2];     // [0] unsorted, [1] sorted (n)
+    uint64_t *nkeys[2];    // numbering keys, [0] unsorted, [1] sorted (n - 1)
+    uint32_t *first, *last, *child, *parent, *ids, *scan;  // per Karras node (child: 2 each)
+    uint32_t *order;
+    RawNode *raw;
+    uint32_t *level_base;
+    LbvhState *st;
+};
+
+__device__ __forceinline__ void lbvh_state_init(LbvhState *st, uint32_t t) {  // t < 128
+    st->hist[t >> 6][t & 63u] = 0u;
+    if (t < 12) st->b.k[t] = key_is_min((int)t) ? kKeyPosInf : kKeyNegInf;
+    if (t == 0) st->error = 0u, st->finished = 0u;
+    if (t < 2) st->max_leaf[t] = 1u;
+}
+__device__ __forceinline__ void lbvh_key(const LbvhArgs &a, const Bounds &b, uint32_t usable, uint32_t i, uint64_t *keys) {
+    keys[i] = sort_key(morton_code(a.boxes[a.objs[i]], b, usable), i);
+}
+// Position i's primitive and, for i < n - 1, Karras node i over the sorted keys.
+__device__ __forceinline__ void lbvh_topology(const LbvhArgs &a, const uint64_t *keys, uint32_t i) {
+    a.order[i] = a.objs[(uint32_t)keys[i] < a.n ? (uint32_t)keys[i] : 0u];
+    if (i + 1u >= a.n) return;
+    const KNode k = karras_node(keys, a.n, i);
+    a.first[i] = k.first;
+    a.last[i] = k.last;
+    if (i == 0) a.parent[0] = kNoParent;
+    for (int c = 0; c < 2; ++c) {
+        uint32_t ch = k.child[c];
+        const uint32_t limit = (ch & kLeafChild) ? a.n : a.n - 1u;
+        if ((ch & ~kLeafChild) >= limit || ch == 0u) {  // never expected: keep every later index in range
+            atomicOr(&a.st->error, kLbvhErrChild);
+            ch = kLeafChild;
+        }
+        a.child[2u * i + (uint32_t)c] = ch;
+        if (!(ch & kLeafChild)) a.parent[ch] = i;
+    }
+}
+// Node i's level and numbering key; hist / max_leaf: the block's LDS counters ([2][kMaxLevels], [2]).
+__device__ __forceinline__ void lbvh_level(const LbvhArgs &a, uint32_t i, uint64_t *nkeys, uint32_t *hist, uint32_t *max_leaf) {
+    uint32_t level = 0;
+    for (uint32_t p = a.parent[i]; p != kNoParent && level < kMaxLevels; p = p < a.n - 1u ? a.parent[p] : kNoParent) ++level;
+    if (level >= kMaxLevels) {
+        atomicOr(&a.st->error, kLbvhErrLevel);
+        level = kMaxLevels - 1u;
+    }
+    nkeys[i] = number_key(level, a.first[i], i);
+    const uint32_t count = a.last[i] - a.first[i] + 1u;
+    for (int s = 0; s < 2; ++s) {
+        if (count <= a.leaf[s]) continue;
+        atomicAdd(&hist[s * kMaxLevels + level], 1u);
+        for (int c = 0; c < 2; ++c) {
+            const uint32_t lc = child_leaf_count(a.child[2u * i + (uint32_t)c], a.first, a.last, a.leaf[s]);
+            if (lc > 1u) atomicMax(&max_leaf[s], lc);
+        }
+    }
+}
+__device__ __forceinline__ bool lbvh_kept(const LbvhArgs &a, uint32_t m, uint32_t s, uint32_t &i) {
+    i = (uint32_t)a.nkeys[1][s] & kNumberIndexMask;
+    if (i >= a.n - 1u) {
+        i = 0;
+        return false;
+    }
+    return a.last[i] - a.first[i] + 1u > m;
+}
+// The node at sorted position s: its number (scan: the exclusive scan of the kept flags, or null when
+// every node is kept).
+__device__ __forceinline__ void lbvh_id(const LbvhArgs &a, uint32_t m, const uint32_t *scan, uint32_t s) {
+    uint32_t i;
+    if (lbvh_kept(a, m, s, i)) a.ids[i] = scan ? scan[s] : s;
+}
+__device__ __forceinline__ void lbvh_links(const LbvhArgs &a, uint32_t m, uint32_t s) {
+    uint32_t i;
+    if (!lbvh_kept(a, m, s, i)) return;
+    const uint32_t id = a.ids[i];
+    if (id >= a.cap) {
+        atomicOr(&a.st->error, kLbvhErrId);
+        return;
+    }
+    for (int c = 0; c < 2; ++c) a.raw[id].link[c] = child_link(a.child[2u * i + (uint32_t)c], a.first, a.last, a.ids, m);
+    a.raw[id]._pad[0] = a.raw[id]._pad[1] = 0u;
+}
+// One thread: the level table of shape `shape` (the first node of every level, then the node count)
+// and, for a root that fits a leaf, the root-leaf form. Returns the levels.
+__device__ __forceinline__ uint32_t lbvh_level_table(const LbvhArgs &a, int shape) {
+    if (a.n <= a.leaf[shape]) {
+        RawNode &r = a.raw[0];
+        never_hit(r.box[0]);
+        never_hit(r.box[1]);
+        r.link[0] = a.n << kLeafShift;
+        r.link[1] = 0u;
+        r._pad[0] = r._pad[1] = 0u;
+        a.level_base[0] = 0u;
+        a.level_base[1] = 1u;
+        return 1u;
+    }
+    uint32_t base = 0, l = 0;
+    for (; l < kMaxLevels && a.st->hist[shape][l] != 0u; ++l) {
+        a.level_base[l] = base;
+        base += a.st->hist[shape][l];
+    }
+    a.level_base[l] = base;
+    return l;
+}
+
+__global__ __launch_bounds__(128) void k_lbvh_init(LbvhState *st) { lbvh_state_init(st, threadIdx.x); }
+__global__ __launch_bounds__(kBlk) void k_lbvh_bounds(LbvhArgs a) {
+    __shared__ u64 s[12];
+    if (threadIdx.x < 12) s[threadIdx.x] = key_is_min((int)threadIdx.x) ? kKeyPosInf : kKeyNegInf;
+    __syncthreads();
+    const uint32_t i = blockIdx.x * kBlk + threadIdx.x;
+    if (i < a.n) {
+        const Bounds bo = bounds_of(a.boxes[a.objs[i]]);
+        for (int j = 6; j < 12; ++j) {
+            if (key_is_min(j)) atomicMin(&s[j], (u64)bo.k[j]);
+            else atomicMax(&s[j], (u64)bo.k[j]);
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x >= 6 && threadIdx.x < 12) {
+        u64 *dst = (u64 *)&a.st->b.k[threadIdx.x];
+        if (key_is_min((int)threadIdx.x)) atomicMin(dst, s[threadIdx.x]);
+        else atomicMax(dst, s[threadIdx.x]);
+    }
+}
+__global__ __launch_bounds__(kBlk) void k_lbvh_keys(LbvhArgs a) {
+    const uint32_t i = blockIdx.x * kBlk + threadIdx.x;
+    if (i >= a.n) return;
+    const Bounds b = a.st->b;
+    lbvh_key(a, b, usable_axes(b), i, a.keys[0]);
+}
+__global__ __launch_bounds__(kBlk) void k_lbvh_topology(LbvhArgs a) {
+    const uint32_t i = blockIdx.x * kBlk + threadIdx.x;
+    if (i < a.n) lbvh_topology(a, a.keys[1], i);
+}
+__global__ __launch_bounds__(kBlk) void k_lbvh_levels(LbvhArgs a) {
+    __shared__ uint32_t hist[2 * kMaxLevels], max_leaf[2];
+    if (threadIdx.x < 2 * kMaxLevels) hist[threadIdx.x] = 0u;
+    if (threadIdx.x < 2) max_leaf[threadIdx.x] = 1u;
+    __syncthreads();
+    const uint32_t i = blockIdx.x * kBlk + threadIdx.x;
+    if (i + 1u < a.n) lbvh_level(a, i, a.nkeys[0], hist, max_leaf);
+    __syncthreads();
+    if (threadIdx.x < 2 * kMaxLevels && hist[threadIdx.x]) atomicAdd(&a.st->hist[threadIdx.x >> 6][threadIdx.x & 63u], hist[threadIdx.x]);
+    if (threadIdx.x < 2 && max_leaf[threadIdx.x] > 1u) atomicMax(&a.st->max_leaf[threadIdx.x], max_leaf[threadIdx.x]);
+}
+__global__ __launch_bounds__(kBlk) void k_lbvh_flags(LbvhArgs a, uint32_t m) {
+    const uint32_t s = blockIdx.x * kBlk + threadIdx.x;
+    uint32_t i;
+    if (s + 1u < a.n) a.scan[s] = lbvh_kept(a, m, s, i) ? 1u : 0u;
+}
+__global__ __launch_bounds__(kBlk) void k_lbvh_ids(LbvhArgs a, uint32_t m, uint32_t scanned) {
+    const uint32_t s = blockIdx.x * kBlk + threadIdx.x;
+    if (s + 1u < a.n) lbvh_id(a, m, scanned ? a.scan : nullptr, s);
+}
+__global__ __launch_bounds__(kBlk) void k_lbvh_links(LbvhArgs a, int shape) {
+    const uint32_t s = blockIdx.x * kBlk + threadIdx.x;
+    if (s + 1u < a.n) lbvh_links(a, a.leaf[shape], s);
+    if (s == 0) (void)lbvh_level_table(a, shape);
+}
+
+// The single workgroup's sort: bitonic over p keys in LDS (p a power of two, padded with ~0).
+__device__ __forceinline__ void lbvh_lds_sort(uint64_t *s, uint32_t p) {
+    for (uint32_t k = 2; k <= p; k <<= 1)
+        for (uint32_t j = k >> 1; j > 0; j >>= 1) {
+            for (uint32_t t = threadIdx.x; t < p / 2u; t += kScanBlk) {
+                const uint32_t i = ((t & ~(j - 1u)) << 1) | (t & (j - 1u)), l = i | j;
+                const uint64_t x = s[i], y = s[l];
+                if ((x > y) == ((i & k) == 0u)) s[i] = y, s[l] = x;
+            }
+            __syncthreads();
+        }
+}
+// k_excl_scan's scan by the calling workgroup, in place over a[0, n).
+__device__ __forceinline__ void lbvh_block_scan(uint32_t n, uint32_t *a, uint32_t *s /* kScanBlk */) {
+    uint32_t carry = 0;
+    const uint32_t tid = threadIdx.x;
+    for (uint32_t base = 0; base < n; base += kScanBlk) {
+        const uint32_t i = base + tid;
+        const uint32_t own = i < n ? a[i] : 0u;
+        s[tid] = own;
+        __syncthreads();
+        for (uint32_t off = 1; off < (uint32_t)kScanBlk; off <<= 1) {
+            const uint32_t v = tid >= off ? s[tid - off] : 0u;
+            __syncthreads();
+            s[tid] += v;
+            __syncthreads();
+        }
+        if (i < n) a[i] = carry + s[tid] - own;
+        carry += s[kScanBlk - 1];
+        __syncthreads();
+    }
+}
+
+// The single-workgroup form, n <= kLbvhSmallMax. front: every phase up to the sorted numbering keys
+// and the state; then one shape is finished: numbers, links, level table, boxes (k_refit_small's
+// loop), slack. Which: shape 0 when its node count is at most fit_nodes (the host's prediction of its
+// own choice: the count up to which the LDS shape fits), else shape 1. front = 0 finishes `shape` of
+// the same build (the host kept the other one after all).
+__global__ __launch_bounds__(kScanBlk) void k_lbvh_small(LbvhArgs a, uint32_t front, int shape, uint32_t fit_nodes,
+                                                         uint32_t p /* pow2 >= n */, Slack *slack) {
+    __shared__ uint64_t s_keys[kLbvhSmallMax];
+    __shared__ u64 s_b[12];
+    __shared__ uint32_t s_hist[2 * kMaxLevels], s_max[2], s_scan[kScanBlk], s_levels;
+    const uint32_t tid = threadIdx.x, n = a.n, nk = a.n - 1u;
+    if (n < 2u || n > kLbvhSmallMax || p > kLbvhSmallMax || p < n) return;
+    if (front) {
+        if (tid < 128) lbvh_state_init(a.st, tid);
+        if (tid < 2 * kMaxLevels) s_hist[tid] = 0u;
+        if (tid < 2) s_max[tid] = 1u;
+        if (tid < 12) s_b[tid] = key_is_min((int)tid) ? kKeyPosInf : kKeyNegInf;
+        __syncthreads();
+        for (uint32_t i = tid; i < n; i += kScanBlk) {
+            const Bounds bo = bounds_of(a.boxes[a.objs[i]]);
+            for (int j = 6; j < 12; ++j) {
+                if (key_is_min(j)) atomicMin(&s_b[j], (u64)bo.k[j]);
+                else atomicMax(&s_b[j], (u64)bo.k[j]);
+            }
+        }
+        __syncthreads();
+        Bounds b;
+        for (int j = 0; j < 12; ++j) b.k[j] = s_b[j];
+        const uint32_t usable = usable_axes(b);
+        for (uint32_t i = tid; i < p; i += kScanBlk) {
+            if (i < n) lbvh_key(a, b, usable, i, s_keys);
+            else s_keys[i] = ~0ull;
+        }
+        __syncthreads();
+        lbvh_lds_sort(s_keys, p);
+        for (uint32_t i = tid; i < n; i += kScanBlk) lbvh_topology(a, s_keys, i);
+        __syncthreads();
+        for (uint32_t i = tid; i < p; i += kScanBlk) {
+            if (i < nk) lbvh_level(a, i, s_keys, s_hist, s_max);
+            else s_keys[i] = ~0ull;
+        }
+        __syncthreads();
+        lbvh_lds_sort(s_keys, p);
+        for (uint32_t i = tid; i < nk; i += kScanBlk) a.nkeys[1][i] = s_keys[i];
+        if (tid < 2 * kMaxLevels) a.st->hist[tid >> 6][tid & 63u] = s_hist[tid];
+        if (tid < 2) a.st->max_leaf[tid] = s_max[tid];
+        if (tid < 12) a.st->b.k[tid] = s_b[tid];
+        __syncthreads();
+        uint32_t nodes0 = 0;
+        for (uint32_t l = 0; l < kMaxLevels; ++l) nodes0 += s_hist[l];
+        if (n <= a.leaf[0]) nodes0 = 1u;
+        shape = nodes0 <= fit_nodes ? 0 : 1;
+        if (tid == 0) a.st->finished = (uint32_t)shape;
+    }
+    const uint32_t m = a.leaf[shape];
+    const bool scanned = m > 1u;
+    if (scanned) {
+        uint32_t i;
+        for (uint32_t s = tid; s < nk; s += kScanBlk) a.scan[s] = lbvh_kept(a, m, s, i) ? 1u : 0u;
+        __syncthreads();
+        lbvh_block_scan(nk, a.scan, s_scan);
+    }
+    for (uint32_t s = tid; s < nk; s += kScanBlk) lbvh_id(a, m, scanned ? a.scan : nullptr, s);
+    __syncthreads();
+    for (uint32_t s = tid; s < nk; s += kScanBlk) lbvh_links(a, m, s);
+    if (tid == 0) s_levels = lbvh_level_table(a, shape);
+    __syncthreads();
+    const uint32_t n_levels = s_levels, n_nodes = a.level_base[n_levels];
+    if (n_nodes > a.cap) return;
+    for (uint32_t l = n_levels; l-- > 0;) {
+        const uint32_t base = a.level_base[l], end = a.level_base[l + 1u];
+        for (uint32_t lane = tid; lane < 2u * (end - base); lane += kScanBlk)
+            refit_lane(a.raw, n_nodes, n, base + (lane >> 1), (int)(lane & 1u), a.order, a.boxes);
+        __syncthreads();
+    }
+    if (tid == 0) write_slack(a.raw, slack);
+}
+
 uint32_t blocks_of(uint32_t n, uint32_t b) { return (n + b - 1u) / b; }
 
 template <class T>
@@ -444,6 +748,21 @@ struct DeviceBvhBuilder::Impl {
     uint64_t refits = 0;  // since the last build
         uint32_t last_refit_launches = 0, last_refit_form = 0;
 
+    // the fast builder's workspace (lbvh_build), each sized for cap primitives, and the last read
+    uint64_t *d_lkeys[2] = {nullptr, nullptr}, *d_nkeys[2] = {nullptr, nullptr};
+    uint32_t *d_lnode = nullptr;  // 7 x cap: first, last, child (2), parent, ids, scan
+    LbvhState *d_lstate = nullptr;
+    void *d_sort_tmp = nullptr;
+    size_t lkeys_cap = 0, sort_tmp_bytes = 0;
+    LbvhState lstate{};
+    uint32_t lbvh_leaf[2] = {0u, 0u};
+    int lbvh_finished = -1;   // the shape the tree on the device is finished for
+    bool lbvh_small = false;  // the current build's form
+    bool slack_on_device = false;  // the held tree's slack is d_slack's (a fast build), not `slack`
+    // the last shape choice (stats_begin .. ): rrt_testing_scene_build_stats
+    BuildStats stats{};
+    LbvhArgs lbvh_args();
+
     hipError_t grow_scan(size_t n_tasks) {
         if (n_tasks <= scan_cap) return hipSuccess;
         (void)hipFree(d_scan);
@@ -476,6 +795,13 @@ struct DeviceBvhBuilder::Impl {
         (void)hipFree(d_terms);
         (void)hipFree(d_terms_build);
         (void)hipFree(d_root_build);
+        for (int k = 0; k < 2; ++k) {
+            (void)hipFree(d_lkeys[k]);
+            (void)hipFree(d_nkeys[k]);
+        }
+        (void)hipFree(d_lnode);
+        (void)hipFree(d_lstate);
+        (void)hipFree(d_sort_tmp);
     }
 };
 
@@ -548,6 +874,11 @@ hipError_t DeviceBvhBuilder::build(uint32_t max_leaf, double node_cost, Summary 
     if (n < 2u) return hipErrorInvalidValue;
     const uint32_t nb = blocks_of(n, kBlk);
     m.cur = 0;
+    m.slack_on_device = false;
+    m.lbvh_finished = -1;
+    m.stats.builder = 0, m.stats.form = 0;
+    m.stats.shape_attempts++;
+    m.stats.launches += 2, m.stats.blocking_reads += 1;  // the root's bounds
     BB_TRY(hipMemcpy(m.d_order[0], m.d_order0, (size_t)n * 4, hipMemcpyDeviceToDevice));
     BB_TRY(hipMemset(m.d_ptask[0], 0, (size_t)n * 4));  // every primitive in task 0, the root
     BB_TRY(hipMemset(m.d_state, 0, sizeof(LevelState)));
@@ -602,6 +933,7 @@ hipError_t DeviceBvhBuilder::build(uint32_t max_leaf, double node_cost, Summary 
                            s_child, s_left, m.d_flag, m.d_block, m.d_order[o], m.d_ptask[o], m.d_state);
         BB_TRY(hipGetLastError());
         BB_TRY(hipMemcpy(&st, m.d_state, sizeof(LevelState), hipMemcpyDeviceToHost));  // the per-level blocking read
+        m.stats.launches += 9, m.stats.blocking_reads += 1;
         if (st.error || st.n_next > next_cap) return hipErrorUnknown;
         if (st.n_split) {
             max_depth = level + 1;
@@ -751,12 +1083,204 @@ hipError_t DeviceBvhBuilder::emit_into(uint32_t stride, uint8_t *d_nodes, size_t
     if ((stride != 80u && stride != 32u) || m.sum.n_nodes == 0 || !d_nodes ||
         (size_t)m.sum.n_nodes * stride > cap_bytes)
         return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_pack, dim3(blocks_of(m.sum.n_nodes, kBlk)), dim3(kBlk), 0, 0, m.sum.n_nodes, m.d_raw, m.slack,
-                       stride, (uint32_t *)d_nodes);
+    if (m.slack_on_device)  // a fast build never brings the root box to the host
+        hipLaunchKernelGGL(k_pack_dev, dim3(blocks_of(m.sum.n_nodes, kBlk)), dim3(kBlk), 0, 0, m.sum.n_nodes, m.d_raw,
+                           m.d_slack, stride, (uint32_t *)d_nodes);
+    else
+        hipLaunchKernelGGL(k_pack, dim3(blocks_of(m.sum.n_nodes, kBlk)), dim3(kBlk), 0, 0, m.sum.n_nodes, m.d_raw, m.slack,
+                           stride, (uint32_t *)d_nodes);
     BB_TRY(hipGetLastError());
     return hipMemcpy(order_out, m.d_order[m.cur], (size_t)m.n_tree * 4, hipMemcpyDeviceToHost);
 }
 
 uint32_t DeviceBvhBuilder::levels() const { return impl_->levels; }
+
+// ---- the fast builder ----------------------------------------------------------------------------
+namespace {
+std::atomic<int> g_lbvh_form{-1};  // rrt_testing_lbvh_form
+}
+bool set_lbvh_form(int form) {
+    if (form < -1 || form > 1) return false;
+    g_lbvh_form.store(form);
+    return true;
+}
+uint32_t DeviceBvhBuilder::lbvh_small_max() { return kLbvhSmallMax; }
+void DeviceBvhBuilder::stats_begin() { impl_->stats = BuildStats{}; }
+BuildStats DeviceBvhBuilder::stats() const { return impl_->stats; }
+
+hipError_t DeviceBvhBuilder::reserve_lbvh() {
+    Impl &m = *impl_;
+    if (!m.cap) return hipErrorInvalidValue;
+    const size_t cap = m.cap;
+    if (m.lkeys_cap < cap) {
+        if (m.lkeys_cap) return hipErrorInvalidValue;  // cap is fixed by upload()
+        for (int k = 0; k < 2; ++k) {
+            BB_TRY(hipMalloc((void **)&m.d_lkeys[k], cap * 8));
+            BB_TRY(hipMalloc((void **)&m.d_nkeys[k], cap * 8));
+        }
+        BB_TRY(hipMalloc((void **)&m.d_lnode, cap * 7 * 4));
+        BB_TRY(hipMalloc((void **)&m.d_lstate, sizeof(LbvhState)));
+        size_t t0 = 0, t1 = 0;
+        BB_TRY(rocprim::radix_sort_keys(nullptr, t0, m.d_lkeys[0], m.d_lkeys[1], (uint32_t)cap, 0u, 62u, (hipStream_t)0));
+        BB_TRY(rocprim::radix_sort_keys(nullptr, t1, m.d_nkeys[0], m.d_nkeys[1], (uint32_t)cap, 28u, 62u, (hipStream_t)0));
+        m.sort_tmp_bytes = std::max<size_t>(std::max(t0, t1), 64);
+        BB_TRY(hipMalloc(&m.d_sort_tmp, m.sort_tmp_bytes));
+        m.n_alloc += 7;
+        m.lkeys_cap = cap;
+    }
+    return hipSuccess;
+}
+
+namespace {
+// rocPRIM's radix sort of bits [lo, hi) of n keys, its temporary storage the builder's.
+hipError_t lbvh_sort(void *tmp, size_t tmp_bytes, uint64_t *in, uint64_t *out, uint32_t n, unsigned lo, unsigned hi) {
+    size_t need = 0;
+    BB_TRY(rocprim::radix_sort_keys(nullptr, need, in, out, n, lo, hi, (hipStream_t)0));
+    if (need > tmp_bytes) return hipErrorOutOfMemory;  // sized for cap keys: never expected
+    return rocprim::radix_sort_keys(tmp, tmp_bytes, in, out, n, lo, hi, (hipStream_t)0);
+}
+}  // namespace
+
+LbvhArgs DeviceBvhBuilder::Impl::lbvh_args() {
+    Impl &m = *this;
+    LbvhArgs a{};
+    a.n = m.n_tree, a.cap = m.cap;
+    a.leaf[0] = m.lbvh_leaf[0], a.leaf[1] = m.lbvh_leaf[1];
+    a.boxes = m.d_boxes, a.objs = m.d_order0;
+    for (int k = 0; k < 2; ++k) a.keys[k] = m.d_lkeys[k], a.nkeys[k] = m.d_nkeys[k];
+    const size_t cap = m.cap;
+    a.first = m.d_lnode, a.last = m.d_lnode + cap, a.child = m.d_lnode + 2 * cap, a.parent = m.d_lnode + 4 * cap;
+    a.ids = m.d_lnode + 5 * cap, a.scan = m.d_lnode + 6 * cap;
+    a.order = m.d_order[0];
+    a.raw = m.d_raw, a.level_base = m.d_level_base, a.st = m.d_lstate;
+    return a;
+}
+
+namespace {
+uint32_t pow2_at_least(uint32_t n) {
+    uint32_t p = 2;
+    while (p < n) p <<= 1;
+    return p;
+}
+// What the state says of shape s.
+Summary lbvh_summary(const LbvhState &st, uint32_t n, uint32_t leaf, int s, std::vector<uint32_t> *level_base) {
+    Summary sum{};
+    if (level_base) level_base->clear();
+    if (n <= leaf) {
+        sum.n_nodes = 1, sum.n_leaves = 1, sum.max_depth = 1, sum.max_leaf = n;
+        if (level_base) level_base->push_back(0u), level_base->push_back(1u);
+        return sum;
+    }
+    uint32_t l = 0;
+    for (; l < kMaxLevels && st.hist[s][l] != 0u; ++l) {
+        if (level_base) level_base->push_back(sum.n_nodes);
+        sum.n_nodes += st.hist[s][l];
+    }
+    if (level_base) level_base->push_back(sum.n_nodes);
+    sum.max_depth = l;
+    sum.n_leaves = sum.n_nodes + 1u;
+    sum.max_leaf = st.max_leaf[s];
+    return sum;
+}
+}  // namespace
+
+// The phases up to the one blocking read. Launches of the per-phase form: init, bounds, keys, sort,
+// topology, levels, sort (7, a sort counted once); the single workgroup: 1, which also finishes the
+// shape fit_nodes predicts.
+hipError_t DeviceBvhBuilder::lbvh_build(uint32_t leaf_a, uint32_t leaf_b, uint32_t fit_nodes, Summary out[2]) {
+    Impl &m = *impl_;
+    const uint32_t n = m.n_tree;
+    if (n < 2u || leaf_a == 0 || leaf_b == 0) return hipErrorInvalidValue;
+    const int forced = g_lbvh_form.load();
+    if (forced == 1 && n > kLbvhSmallMax) return hipErrorInvalidValue;
+    BB_TRY(reserve_lbvh());
+    m.lbvh_small = forced < 0 ? n <= kLbvhSmallMax : forced == 1;
+    m.lbvh_leaf[0] = leaf_a, m.lbvh_leaf[1] = leaf_b;
+    m.lbvh_finished = -1;
+    m.cur = 0;
+    m.sum = Summary{};
+    m.level_base.clear();
+    m.build_captured = m.build_sah_known = false;
+    m.refits = 0;
+    m.levels = 0;
+    m.stats.builder = 1, m.stats.form = m.lbvh_small ? 1u : 0u;
+    const LbvhArgs a = m.lbvh_args();
+    const uint32_t nb = blocks_of(n, kBlk);
+    if (m.lbvh_small) {
+        hipLaunchKernelGGL(k_lbvh_small, dim3(1), dim3(kScanBlk), 0, 0, a, 1u, 0, fit_nodes, pow2_at_least(n), m.d_slack);
+        BB_TRY(hipGetLastError());
+        m.stats.launches += 1;
+        m.stats.shape_attempts += 1;
+    } else {
+        hipLaunchKernelGGL(k_lbvh_init, dim3(1), dim3(128), 0, 0, m.d_lstate);
+        hipLaunchKernelGGL(k_lbvh_bounds, dim3(nb), dim3(kBlk), 0, 0, a);
+        hipLaunchKernelGGL(k_lbvh_keys, dim3(nb), dim3(kBlk), 0, 0, a);
+        BB_TRY(hipGetLastError());
+        BB_TRY(lbvh_sort(m.d_sort_tmp, m.sort_tmp_bytes, m.d_lkeys[0], m.d_lkeys[1], n, 0u, 62u));
+        hipLaunchKernelGGL(k_lbvh_topology, dim3(nb), dim3(kBlk), 0, 0, a);
+        hipLaunchKernelGGL(k_lbvh_levels, dim3(nb), dim3(kBlk), 0, 0, a);
+        BB_TRY(hipGetLastError());
+        BB_TRY(lbvh_sort(m.d_sort_tmp, m.sort_tmp_bytes, m.d_nkeys[0], m.d_nkeys[1], n - 1u, 28u, 62u));
+        m.stats.launches += 7;
+    }
+    BB_TRY(hipMemcpy(&m.lstate, m.d_lstate, sizeof(LbvhState), hipMemcpyDeviceToHost));  // the build's one blocking read
+    m.stats.blocking_reads += 1;
+    if (m.lstate.error) return hipErrorUnknown;
+    for (int s = 0; s < 2; ++s) {
+        out[s] = lbvh_summary(m.lstate, n, m.lbvh_leaf[s], s, nullptr);
+        if (out[s].n_nodes == 0 || out[s].n_nodes >= n) return hipErrorUnknown;
+    }
+    if (m.lbvh_small) m.lbvh_finished = m.lstate.finished ? 1 : 0;
+    return hipSuccess;
+}
+
+// Shape `shape` of the last lbvh_build becomes the held tree: numbers, links, level table and boxes,
+// with no read. Launches of the per-phase form: flags and scan (leaves over 1 only), ids, links (4),
+// then the box pass: the refit's single workgroup (1), or one per level and the slack.
+hipError_t DeviceBvhBuilder::lbvh_finish(int shape, double node_cost, Summary *out) {
+    Impl &m = *impl_;
+    const uint32_t n = m.n_tree;
+    if (shape < 0 || shape > 1 || !m.lbvh_leaf[0]) return hipErrorInvalidValue;
+    m.sum = lbvh_summary(m.lstate, n, m.lbvh_leaf[shape], shape, &m.level_base);
+    m.levels = m.sum.max_depth;
+    m.node_cost = node_cost;
+    m.slack_on_device = true;
+    if (out) *out = m.sum;
+    if (m.lbvh_finished == shape) return hipSuccess;
+    const LbvhArgs a = m.lbvh_args();
+    m.stats.shape_attempts += 1;
+    if (m.lbvh_small) {
+        hipLaunchKernelGGL(k_lbvh_small, dim3(1), dim3(kScanBlk), 0, 0, a, 0u, shape, 0u, pow2_at_least(n), m.d_slack);
+        m.stats.launches += 1;
+    } else {
+        const uint32_t nkb = blocks_of(n - 1u, kBlk), leaf = m.lbvh_leaf[shape];
+        if (leaf > 1u) {
+            hipLaunchKernelGGL(k_lbvh_flags, dim3(nkb), dim3(kBlk), 0, 0, a, leaf);
+            hipLaunchKernelGGL(k_excl_scan, dim3(1), dim3(kScanBlk), 0, 0, n - 1u, a.scan, (uint32_t *)nullptr,
+                               (uint32_t *)nullptr, m.d_totals);
+            m.stats.launches += 2;
+        }
+        hipLaunchKernelGGL(k_lbvh_ids, dim3(nkb), dim3(kBlk), 0, 0, a, leaf, leaf > 1u ? 1u : 0u);
+        hipLaunchKernelGGL(k_lbvh_links, dim3(nkb), dim3(kBlk), 0, 0, a, shape);
+        m.stats.launches += 2;
+        const uint32_t n_nodes = m.sum.n_nodes, n_levels = (uint32_t)m.level_base.size() - 1u;
+        if (n_nodes <= kRefitSmallMaxNodes) {
+            hipLaunchKernelGGL(k_refit_small, dim3(1), dim3(kScanBlk), 0, 0, n_levels, m.d_level_base, m.d_raw, n_nodes, n,
+                               m.d_order[0], m.d_boxes, m.d_slack);
+            m.stats.launches += 1;
+        } else {
+            for (uint32_t l = n_levels; l-- > 0;) {
+                const uint32_t base = m.level_base[l], end = m.level_base[l + 1];
+                hipLaunchKernelGGL(k_refit_level, dim3(blocks_of(2u * (end - base), kBlk)), dim3(kBlk), 0, 0, base, end, m.d_raw,
+                                   n_nodes, n, m.d_order[0], m.d_boxes);
+            }
+            hipLaunchKernelGGL(k_refit_slack, dim3(1), dim3(1), 0, 0, m.d_raw, m.d_slack);
+            m.stats.launches += n_levels + 1u;
+        }
+    }
+    BB_TRY(hipGetLastError());
+    m.lbvh_finished = shape;
+    return hipSuccess;
+}
 
 }  // namespace rrt

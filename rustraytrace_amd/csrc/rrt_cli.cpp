@@ -111,6 +111,8 @@ static void usage() {
                  "  --books-f64-book2  --books-f64 that also takes the_next_week 1, 2, 5 and 7 (RRT_FLAG_F64_BOOK2:\n"
                  "                   moving spheres, quads, checker textures); other scenes are refused\n"
                  "  --device-bvh     build the scene's BVH on the device (RRT_FLAG_DEVICE_BVH) instead of the host\n"
+                 "  --fast-bvh       build it on the device by the LBVH builder (RRT_FLAG_FAST_BVH): a cheaper build,\n"
+                 "                   a slower tree; implies --device-bvh\n"
                  "books: in_one_weekend, the_next_week [1-9, other = final_scene(400, 250, 4)], "
                  "the_rest_of_your_life\n");
 }
@@ -148,7 +150,7 @@ int main(int argc, char **argv) {
     uint64_t seed = 0x5EED1234ull;
     int grid_half = 11;
     std::string out = "-";
-    bool p6 = false, host_quantise = false, seed_set = false, books_f64 = false, books_f64_book2 = false, device_bvh = false;
+    bool p6 = false, host_quantise = false, seed_set = false, books_f64 = false, books_f64_book2 = false, device_bvh = false, fast_bvh = false;
 
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
@@ -183,6 +185,7 @@ int main(int argc, char **argv) {
         else if (a == "--books-f64") books_f64 = true;
         else if (a == "--books-f64-book2") books_f64 = books_f64_book2 = true;
         else if (a == "--device-bvh") device_bvh = true;
+        else if (a == "--fast-bvh") fast_bvh = true;
         else if (a == "-h" || a == "--help") { usage(); return 0; }
         else positional.push_back(a);
     }
@@ -293,6 +296,7 @@ int main(int argc, char **argv) {
     ext.lights = lights.empty() ? nullptr : lights.data();
     ext.n_lights = (uint32_t)lights.size();
     if (device_bvh) flags |= RRT_FLAG_DEVICE_BVH;
+    if (fast_bvh) flags |= RRT_FLAG_FAST_BVH;
     const uint32_t w = (uint32_t)cam.params_f[1], h = (uint32_t)cam.params_f[2];
     const uint32_t spp = (uint32_t)(cam.params_f[3] < 1.0f ? 1.0f : cam.params_f[3]);
     const auto t0 = std::chrono::steady_clock::now();

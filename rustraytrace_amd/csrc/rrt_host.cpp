@@ -10,6 +10,7 @@
 // without a HIP device every render entry fails with RRT_E_NODEV.
 #include "rrt_internal.h"
 #include "rrt_bvh_binned.h"
+#include "rrt_bvh_lbvh.h"
 #include "rrt_sphere_box.h"
 #include "rrt_quad_form.h"
 #include "rrt_medium_form.h"
@@ -978,6 +979,76 @@ BinnedTree build_binned_host(const BinnedInput &in, uint32_t max_leaf, double no
     return bt;
 }
 
+// The host twin of the fast builder (rrt_bvh_lbvh.h), sequential: keys, a sort, Karras' nodes, their
+// levels, the breadth-first numbers of the kept ones, links, then the binned header's refit for the
+// boxes. The device builder (rrt_bvh_build.hip build_lbvh) must produce these bytes.
+BinnedTree build_lbvh_host(const BinnedInput &in, uint32_t max_leaf) {
+    using namespace rrt::lbvh;
+    BinnedTree bt;
+    const uint32_t n = (uint32_t)in.objs.size();
+    bt.objs = in.objs;
+    auto root_leaf = [&]() {
+        RawNode r{};
+        never_hit(r.box[0]);
+        never_hit(r.box[1]);
+        r.link[0] = n << kLeafShift;
+        bt.raw.push_back(r);
+        bt.sum.n_nodes = 1, bt.sum.n_leaves = 1, bt.sum.max_depth = 1, bt.sum.max_leaf = n;
+    };
+    if (n >= 2) {
+        Bounds b = bounds_empty();
+        for (uint32_t i = 0; i < n; ++i) bounds_merge(b, bounds_of(in.boxes[in.objs[i]]));
+        const uint32_t usable = usable_axes(b);
+        std::vector<uint64_t> keys(n);
+        for (uint32_t i = 0; i < n; ++i) keys[i] = sort_key(morton_code(in.boxes[in.objs[i]], b, usable), i);
+        std::sort(keys.begin(), keys.end());
+        for (uint32_t i = 0; i < n; ++i) bt.objs[i] = in.objs[(uint32_t)keys[i]];
+        if (n <= max_leaf) {
+            root_leaf();
+        } else {
+            const uint32_t nk = n - 1u;
+            std::vector<uint32_t> first(nk), last(nk), parent(nk, kNoParent), ids(nk, 0u);
+            std::vector<KNode> kn(nk);
+            for (uint32_t i = 0; i < nk; ++i) {
+                kn[i] = karras_node(keys.data(), n, i);
+                first[i] = kn[i].first, last[i] = kn[i].last;
+                for (int c = 0; c < 2; ++c)
+                    if (!(kn[i].child[c] & kLeafChild)) parent[kn[i].child[c]] = i;
+            }
+            std::vector<uint64_t> nkeys;
+            uint32_t depth = 0;
+            for (uint32_t i = 0; i < nk; ++i) {
+                if (last[i] - first[i] + 1u <= max_leaf) continue;
+                uint32_t level = 0;
+                for (uint32_t p = parent[i]; p != kNoParent; p = parent[p]) ++level;
+                depth = std::max(depth, level + 1u);
+                nkeys.push_back(number_key(level, first[i], i));
+            }
+            std::sort(nkeys.begin(), nkeys.end());
+            for (uint32_t s = 0; s < (uint32_t)nkeys.size(); ++s) ids[(uint32_t)nkeys[s] & kNumberIndexMask] = s;
+            bt.raw.assign(nkeys.size(), RawNode{});
+            for (uint32_t s = 0; s < (uint32_t)nkeys.size(); ++s) {
+                const uint32_t i = (uint32_t)nkeys[s] & kNumberIndexMask;
+                for (int c = 0; c < 2; ++c) {
+                    bt.raw[s].link[c] = child_link(kn[i].child[c], first.data(), last.data(), ids.data(), max_leaf);
+                    bt.sum.max_leaf = std::max(bt.sum.max_leaf, child_leaf_count(kn[i].child[c], first.data(), last.data(), max_leaf));
+                }
+            }
+            bt.sum.n_nodes = (uint32_t)nkeys.size();
+            bt.sum.n_leaves = bt.sum.n_nodes + 1u;
+            bt.sum.max_depth = depth;
+        }
+    } else {
+        root_leaf();
+    }
+    refit_raw(bt.raw.data(), bt.sum.n_nodes, bt.objs.data(), in.boxes.data());
+    double root_box[6];
+    root_box_of(bt.raw[0], root_box);
+    if (n == 0) never_hit(root_box);
+    bt.slack = slack_of(root_box);
+    return bt;
+}
+
 // The twin's FlatBvh in the 80-B or 32-B node format (the header's roundings).
 FlatBvh flat_of_summary(const bvhb::Summary &sum, uint32_t stride, const BinnedInput &in) {
     FlatBvh f;
@@ -1007,7 +1078,9 @@ FlatBvh flatten_binned(const BinnedTree &bt, uint32_t stride, const BinnedInput 
 // caller's leaf size. sum / stride / leaf_param describe the shape that was kept (leaf_param: its
 // leaf size) and the builder holds its tree. Scene creation and rrt_scene_update_spheres both choose
 // here.
-int bvh_device_shape(rrt::DeviceBvhBuilder &bld, size_t n_prims_all, uint32_t max_leaf, bool book2, bool f64,
+// lbvh: the fast builder (RRT_FLAG_FAST_BVH). One build yields the summaries of both candidate shapes
+// by one read; the same composition then picks one, which lbvh_finish makes the held tree.
+int bvh_device_shape(rrt::DeviceBvhBuilder &bld, bool lbvh, size_t n_prims_all, uint32_t max_leaf, bool book2, bool f64,
                      bvhb::Summary &sum, uint32_t &stride, uint32_t &leaf_param, uint32_t &levels) {
     auto cost = [](double c) {
         if (const char *e = std::getenv("RRT_SAH_CT")) return std::atof(e);
@@ -1023,6 +1096,39 @@ int bvh_device_shape(rrt::DeviceBvhBuilder &bld, size_t n_prims_all, uint32_t ma
     stride = 0;
     bvhb::Summary none{};
     none.n_nodes = 1, none.max_depth = 1;
+    bld.stats_begin();
+    if (lbvh) {
+        const bool try_lds = fits(none);
+        const uint32_t leaf_global = std::min(max_leaf, max_leaf_global());
+        // the node count up to which the LDS shape fits, for the single workgroup to finish the shape
+        // this function will keep (f64: the fit also reads the depth, so the LDS shape is predicted)
+        uint32_t fit_nodes = 0;
+        if (try_lds && f64) fit_nodes = 0xffffffffu;
+        else if (try_lds) {
+            uint32_t lo = 1, hi = bld.n_tree();  // fits(lo) holds
+            while (lo < hi) {
+                bvhb::Summary mid{};
+                mid.n_nodes = lo + (hi - lo + 1) / 2, mid.max_depth = 1;
+                if (fits(mid)) lo = mid.n_nodes;
+                else hi = mid.n_nodes - 1;
+            }
+            fit_nodes = lo;
+        }
+        bvhb::Summary both[2];
+        if (bld.lbvh_build(max_leaf, leaf_global, fit_nodes, both) != hipSuccess)
+            return fail(RRT_E_HIP, "device BVH: the fast build failed");
+        int shape = 1;
+        stride = (uint32_t)sizeof(rrt::GNodeH), leaf_param = leaf_global;
+        if (try_lds && fits(both[0])) {
+            shape = 0, stride = (uint32_t)sizeof(rrt::GNode), leaf_param = max_leaf;
+        } else if ((f64 && both[1].n_nodes > 65535u) || both[1].max_depth + 1 > (uint32_t)rrt::kMaxStackDepth) {
+            shape = 0, leaf_param = max_leaf;
+        }
+        const double price = (shape == 0 && stride == sizeof(rrt::GNode) && f64) ? f64_node_cost_lds() : kNodeCost;
+        if (bld.lbvh_finish(shape, price, &sum) != hipSuccess) return fail(RRT_E_HIP, "device BVH: the fast build failed");
+        levels = bld.levels();
+        return RRT_OK;
+    }
     if (fits(none)) {  // the primitive records leave room for a node
         if (bld.build(max_leaf, cost(f64 ? f64_node_cost_lds() : kNodeCost), &sum) != hipSuccess)
             return fail(RRT_E_HIP, "device BVH: build failed");
@@ -1045,14 +1151,14 @@ int bvh_device_shape(rrt::DeviceBvhBuilder &bld, size_t n_prims_all, uint32_t ma
 
 // Scene creation's device build: upload, the shape choice, and the nodes emitted to a fresh device
 // array (d_nodes, owned by the caller); the order and the summary come back. n_tree >= 2.
-int scene_bvh_device(rrt::DeviceBvhBuilder &bld, const BinnedInput &in, size_t n_prims_all, uint32_t max_leaf, bool book2,
+int scene_bvh_device(rrt::DeviceBvhBuilder &bld, bool lbvh, const BinnedInput &in, size_t n_prims_all, uint32_t max_leaf, bool book2,
                      bool f64, FlatBvh &fb, uint8_t **d_nodes, std::vector<uint32_t> &order, uint32_t &leaf_param,
                      uint32_t &levels) {
     if (bld.upload(in.boxes.data(), (uint32_t)in.boxes.size(), in.objs.data(), (uint32_t)in.objs.size()) != hipSuccess)
         return fail(RRT_E_HIP, "device BVH: upload failed");
     bvhb::Summary sum{};
     uint32_t stride = 0;
-    if (int rc = bvh_device_shape(bld, n_prims_all, max_leaf, book2, f64, sum, stride, leaf_param, levels)) return rc;
+    if (int rc = bvh_device_shape(bld, lbvh, n_prims_all, max_leaf, book2, f64, sum, stride, leaf_param, levels)) return rc;
     fb = flat_of_summary(sum, stride, in);
     order.assign(in.objs.size(), 0u);
     if (bld.emit(stride, d_nodes, order.data()) != hipSuccess) return fail(RRT_E_HIP, "device BVH: emit failed");
@@ -1102,6 +1208,7 @@ struct RrtScene {
     // tables below are what the leaf-order tables are re-formed from.
     bool device_bvh = false;                  // created with RRT_FLAG_DEVICE_BVH
     rrt::DeviceBvhBuilder *builder = nullptr; // kept when it built the tree (>= 2 primitives)
+    bool fast_bvh = false;                    // the next update's builder is the LBVH (RRT_FLAG_FAST_BVH, rrt_scene_set_builder)
     uint32_t n_spheres = 0, n_materials = 0, max_leaf = 0;
     bool quads_in_sphere32 = true;            // the quads' prim_cr rows pass the sphere32 range check
     rrt::GMaterial *d_src_mats = nullptr;     // the GMaterial table
@@ -1680,12 +1787,16 @@ static int32_t scene_create(const RrtCamera *cam, const RrtSphere *spheres, uint
     static_assert(RRT_FLAG_F64 == rrt::kFlagF64, "RRT_FLAG_F64");
     static_assert(RRT_FLAG_DEVICE_BVH == rrt::kFlagDeviceBvh, "RRT_FLAG_DEVICE_BVH");
     const bool f64 = (flags & RRT_FLAG_F64) != 0;
-    const bool device_bvh = (flags & RRT_FLAG_DEVICE_BVH) != 0;
-    flags &= ~RRT_FLAG_DEVICE_BVH;  // a choice of scene creation: the kernels never see it
+    static_assert(RRT_FLAG_FAST_BVH == rrt::kFlagFastBvh, "RRT_FLAG_FAST_BVH");
+    const bool fast_bvh = (flags & RRT_FLAG_FAST_BVH) != 0;  // implies the device flag
+    const bool device_bvh = (flags & RRT_FLAG_DEVICE_BVH) != 0 || fast_bvh;
+    flags &= ~(RRT_FLAG_DEVICE_BVH | RRT_FLAG_FAST_BVH);  // choices of scene creation: the kernels never see them
     if (device_bvh) {
         uint32_t w, l;
         bvh_defaults(w, l);
-        if (w != 2) return fail(RRT_E_INVALID, "RRT_FLAG_DEVICE_BVH builds binary trees only (RRT_BVH_WIDTH=4 is set)");
+        if (w != 2)
+            return fail(RRT_E_INVALID, std::string(fast_bvh ? "RRT_FLAG_FAST_BVH" : "RRT_FLAG_DEVICE_BVH") +
+                                           " builds binary trees only (RRT_BVH_WIDTH=4 is set)");
     }
     // the f64 kernel's book-2 class runs the scenes that have book-2 data; a book-1 scene created with
     // RRT_FLAG_F64_BOOK2 is an RRT_FLAG_F64 scene (same tree, same kernel class, same bits)
@@ -1741,7 +1852,7 @@ static int32_t scene_create(const RrtCamera *cam, const RrtSphere *spheres, uint
             if (hipSetDevice(device) != hipSuccess) return fail(RRT_E_HIP, "hipSetDevice failed");
             uint32_t levels = 0;
             builder.reset(new rrt::DeviceBvhBuilder);
-            if (int rc = scene_bvh_device(*builder, in, (size_t)n_spheres + n_quads + n_media, max_leaf, book2, f64, fb,
+            if (int rc = scene_bvh_device(*builder, fast_bvh, in, (size_t)n_spheres + n_quads + n_media, max_leaf, book2, f64, fb,
                                           &dev_nodes.p, order, leaf_param, levels))
                 return rc;
             built_on_device = true;
@@ -1874,6 +1985,7 @@ static int32_t scene_create(const RrtCamera *cam, const RrtSphere *spheres, uint
     s->light_kinds.resize(glights.size());
     for (uint32_t l = 0; l < glights.size(); ++l) s->light_kinds[l] = glights[l].kind;
     if (built_on_device) s->builder = builder.release();
+    s->fast_bvh = fast_bvh;
     if (built_on_device && (n_media || ex.n_bquads)) {
         if (n_quads) s->h_quads.assign(quads, quads + n_quads);
         if (n_media) s->h_media.assign(ex.media, ex.media + n_media);
@@ -2178,7 +2290,8 @@ int ensure_change_buffers(RrtScene *s, const std::string &fn, uint64_t &own_allo
         s->d_nodes = d;
         p.nodes = d;
         s->nodes_cap = cap;
-        if (s->builder->reserve() != hipSuccess) return fail(RRT_E_NOMEM, fn + "reserving the builder's workspace failed");
+        if (!s->fast_bvh && s->builder->reserve() != hipSuccess)
+            return fail(RRT_E_NOMEM, fn + "reserving the builder's workspace failed");
     }
     return RRT_OK;
 }
@@ -2431,7 +2544,9 @@ int32_t update_scene(RrtScene *s, const std::string &fn, const RrtSphere *sphere
         return broke(RRT_E_HIP, "device BVH: replacing the tree's primitives failed");
     bvhb::Summary sum{};
     uint32_t stride = 0, leaf_param = s->max_leaf, levels = 0;
-    if (int rc = bvh_device_shape(*s->builder, n_prims, s->max_leaf, s->book2, s->f64, sum, stride, leaf_param, levels))
+    if (!s->fast_bvh && s->builder->reserve() != hipSuccess)  // allocates after a switch from the fast builder only
+        return broke(RRT_E_NOMEM, "reserving the builder's workspace failed");
+    if (int rc = bvh_device_shape(*s->builder, s->fast_bvh, n_prims, s->max_leaf, s->book2, s->f64, sum, stride, leaf_param, levels))
         return broke(rc, g_err);
     const FlatBvh fb = flat_of_summary(sum, stride, cls);
     if (int rc = tree_limits(fb, s->f64)) return broke(rc, g_err);
@@ -2483,9 +2598,10 @@ int32_t rrt_scene_update_geometry(RrtScene *scene, const RrtSceneGeometry *geome
     return update_scene(scene, fn, geometry->spheres, geometry->n_spheres, geometry->sphere_motion, has_motion, g, stream);
 }
 
-int32_t rrt_build_bvh_binned(const RrtSphere *spheres, uint32_t n_spheres, const RrtSceneExt *ext, uint32_t max_leaf,
-                             double node_cost, uint32_t node_stride, void *nodes_out, size_t nodes_cap,
-                             uint32_t *prim_order_out, RrtBvhInfo *info) {
+// The build twins' common body (lbvh: rrt_bvh_lbvh.h's builder, which takes no node_cost).
+static int32_t build_bvh_twin(bool lbvh, const RrtSphere *spheres, uint32_t n_spheres, const RrtSceneExt *ext, uint32_t max_leaf,
+                              double node_cost, uint32_t node_stride, void *nodes_out, size_t nodes_cap,
+                              uint32_t *prim_order_out, RrtBvhInfo *info) {
     if (n_spheres && !spheres) return fail(RRT_E_INVALID, "null spheres");
     const ExtView ex(ext);
     for (uint32_t m = 0; m < ex.n_media; ++m)
@@ -2497,7 +2613,7 @@ int32_t rrt_build_bvh_binned(const RrtSphere *spheres, uint32_t n_spheres, const
     if ((uint64_t)n_spheres + ex.n_quads + ex.n_media >= (1u << 24)) return fail(RRT_E_INVALID, ">= 2^24 primitives");
     const BinnedInput in = binned_input(spheres, n_spheres, ex);
     std::vector<uint32_t> order;
-    const FlatBvh fb = flatten_binned(build_binned_host(in, max_leaf, node_cost), node_stride, in, order);
+    const FlatBvh fb = flatten_binned(lbvh ? build_lbvh_host(in, max_leaf) : build_binned_host(in, max_leaf, node_cost), node_stride, in, order);
     if (info) {
         const bool book2 = ex.motion || ex.n_quads || ex.n_media;
         *info = RrtBvhInfo{};
@@ -2520,6 +2636,20 @@ int32_t rrt_build_bvh_binned(const RrtSphere *spheres, uint32_t n_spheres, const
     std::memcpy(nodes_out, fb.bytes.data(), fb.bytes.size());
     if (order.size()) std::memcpy(prim_order_out, order.data(), order.size() * sizeof(uint32_t));
     return RRT_OK;
+}
+
+int32_t rrt_build_bvh_binned(const RrtSphere *spheres, uint32_t n_spheres, const RrtSceneExt *ext, uint32_t max_leaf,
+                             double node_cost, uint32_t node_stride, void *nodes_out, size_t nodes_cap,
+                             uint32_t *prim_order_out, RrtBvhInfo *info) {
+    return build_bvh_twin(false, spheres, n_spheres, ext, max_leaf, node_cost, node_stride, nodes_out, nodes_cap, prim_order_out, info);
+}
+
+int32_t rrt_build_bvh_lbvh(const RrtSphere *spheres, uint32_t n_spheres, const RrtSceneExt *ext, uint32_t max_leaf,
+                           uint32_t node_stride, void *nodes_out, size_t nodes_cap, uint32_t *prim_order_out, RrtBvhInfo *info) {
+    uint32_t w, l;
+    bvh_defaults(w, l);
+    if (w != 2) return fail(RRT_E_INVALID, "rrt_build_bvh_lbvh builds binary trees only (RRT_BVH_WIDTH=4 is set)");
+    return build_bvh_twin(true, spheres, n_spheres, ext, max_leaf, 0.0, node_stride, nodes_out, nodes_cap, prim_order_out, info);
 }
 
 // The refit: everything after the checks is enqueued on `stream`; no host read, no wait for the
@@ -2660,6 +2790,18 @@ int32_t rrt_scene_refit_world(RrtScene *scene, const RrtSceneGeometry *geometry,
     return refit_scene(scene, fn, geometry->spheres, geometry->n_spheres, geometry->sphere_motion, has_motion, g, true, stream);
 }
 
+int32_t rrt_scene_set_builder(RrtScene *scene, uint32_t builder) {
+    const std::string fn = "rrt_scene_set_builder: ";
+    if (!scene) return fail(RRT_E_INVALID, fn + "null scene");
+    if (builder != RRT_BUILDER_BINNED && builder != RRT_BUILDER_LBVH)
+        return fail(RRT_E_INVALID, fn + "the builder is RRT_BUILDER_BINNED (0) or RRT_BUILDER_LBVH (1)");
+    if (!scene->builder)
+        return fail(RRT_E_INVALID, fn + "the scene holds no device builder (RRT_FLAG_DEVICE_BVH or RRT_FLAG_FAST_BVH and at "
+                                        "least 2 primitives)");
+    scene->fast_bvh = builder == RRT_BUILDER_LBVH;
+    return RRT_OK;
+}
+
 int32_t rrt_scene_tree_cost(RrtScene *scene, RrtTreeCost *out) {
     const std::string fn = "rrt_scene_tree_cost: ";
     if (!scene || !out) return fail(RRT_E_INVALID, fn + "null scene or out");
@@ -2682,7 +2824,7 @@ int32_t rrt_refit_bvh_binned(const RrtSphere *built_spheres, uint32_t n_spheres,
 
 // The refit twins' common body: the built tree with its boxes recomputed from the new rows (a null
 // array of new_quads, new_media or new_bquads: the built one; new_motion null: all zero).
-static int32_t refit_bvh_binned(const RrtSphere *built_spheres, uint32_t n_spheres, const RrtSceneExt *built_ext,
+static int32_t refit_bvh_binned(bool lbvh, const RrtSphere *built_spheres, uint32_t n_spheres, const RrtSceneExt *built_ext,
                                 uint32_t max_leaf, double node_cost, uint32_t node_stride, const RrtSphere *new_spheres,
                                 const float *new_motion, const RrtQuad *new_quads, const RrtMedium *new_media,
                                 const RrtQuad *new_bquads, void *nodes_out, size_t nodes_cap, uint32_t *prim_order_out,
@@ -2697,7 +2839,7 @@ static int32_t refit_bvh_binned(const RrtSphere *built_spheres, uint32_t n_spher
         return fail(RRT_E_INVALID, "max_leaf must be 1..7, node_stride 80 or 32");
     if ((uint64_t)n_spheres + ex.n_quads + ex.n_media >= (1u << 24)) return fail(RRT_E_INVALID, ">= 2^24 primitives");
     BinnedInput in = binned_input(built_spheres, n_spheres, ex);
-    BinnedTree bt = build_binned_host(in, max_leaf, node_cost);
+    BinnedTree bt = lbvh ? build_lbvh_host(in, max_leaf) : build_binned_host(in, max_leaf, node_cost);
     for (uint32_t i = 0; i < n_spheres; ++i)
         in.boxes[i] = rrt::sphere_box(new_spheres[i].center_radius, new_motion ? new_motion + 4 * (size_t)i : nullptr);
     for (uint32_t j = 0; new_quads && j < ex.n_quads; ++j)
@@ -2748,15 +2890,14 @@ int32_t rrt_refit_bvh_binned_ex(const RrtSphere *built_spheres, uint32_t n_spher
                                 uint32_t max_leaf, double node_cost, uint32_t node_stride, const RrtSphere *new_spheres,
                                 const float *new_motion, const RrtQuad *new_quads, void *nodes_out, size_t nodes_cap,
                                 uint32_t *prim_order_out, RrtBvhInfo *info, double *sah_out) {
-    return refit_bvh_binned(built_spheres, n_spheres, built_ext, max_leaf, node_cost, node_stride, new_spheres, new_motion,
+    return refit_bvh_binned(false, built_spheres, n_spheres, built_ext, max_leaf, node_cost, node_stride, new_spheres, new_motion,
                             new_quads, nullptr, nullptr, nodes_out, nodes_cap, prim_order_out, info, sah_out);
 }
 
-int32_t rrt_refit_bvh_binned_world(const RrtSphere *built_spheres, uint32_t n_spheres, const RrtSceneExt *built_ext,
-                                   uint32_t max_leaf, double node_cost, uint32_t node_stride, const RrtSphere *new_spheres,
-                                   const RrtSceneExt *new_ext, void *nodes_out, size_t nodes_cap, uint32_t *prim_order_out,
-                                   RrtBvhInfo *info, double *sah_out) {
-    const std::string fn = "rrt_refit_bvh_binned_world: ";
+static int32_t refit_bvh_world(bool lbvh, const std::string &fn, const RrtSphere *built_spheres, uint32_t n_spheres,
+                               const RrtSceneExt *built_ext, uint32_t max_leaf, double node_cost, uint32_t node_stride,
+                               const RrtSphere *new_spheres, const RrtSceneExt *new_ext, void *nodes_out, size_t nodes_cap,
+                               uint32_t *prim_order_out, RrtBvhInfo *info, double *sah_out) {
     const ExtView built(built_ext), ex(new_ext);
     if (ex.quads && ex.n_quads != built.n_quads)
         return fail(RRT_E_INVALID, fn + "n_quads is " + std::to_string(ex.n_quads) + ", the built scene's is " + std::to_string(built.n_quads));
@@ -2765,8 +2906,29 @@ int32_t rrt_refit_bvh_binned_world(const RrtSphere *built_spheres, uint32_t n_sp
     if (ex.bquads && ex.n_bquads != built.n_bquads)
         return fail(RRT_E_INVALID, fn + "n_boundary_quads is " + std::to_string(ex.n_bquads) + ", the built scene's is " +
                                        std::to_string(built.n_bquads));
-    return refit_bvh_binned(built_spheres, n_spheres, built_ext, max_leaf, node_cost, node_stride, new_spheres, ex.motion,
+    return refit_bvh_binned(lbvh, built_spheres, n_spheres, built_ext, max_leaf, node_cost, node_stride, new_spheres, ex.motion,
                             ex.quads, ex.media, ex.bquads, nodes_out, nodes_cap, prim_order_out, info, sah_out);
+}
+
+int32_t rrt_refit_bvh_binned_world(const RrtSphere *built_spheres, uint32_t n_spheres, const RrtSceneExt *built_ext,
+                                   uint32_t max_leaf, double node_cost, uint32_t node_stride, const RrtSphere *new_spheres,
+                                   const RrtSceneExt *new_ext, void *nodes_out, size_t nodes_cap, uint32_t *prim_order_out,
+                                   RrtBvhInfo *info, double *sah_out) {
+    return refit_bvh_world(false, "rrt_refit_bvh_binned_world: ", built_spheres, n_spheres, built_ext, max_leaf, node_cost,
+                           node_stride, new_spheres, new_ext, nodes_out, nodes_cap, prim_order_out, info, sah_out);
+}
+
+// sah_out weighs a node child by 2, the price rrt_scene_tree_cost uses for a fast-built f32 scene
+// (an f64 scene's LDS shape is weighed by RRT_F64_SAH_CT_LDS's 1.5 on the device).
+int32_t rrt_refit_bvh_lbvh_world(const RrtSphere *built_spheres, uint32_t n_spheres, const RrtSceneExt *built_ext,
+                                 uint32_t max_leaf, uint32_t node_stride, const RrtSphere *new_spheres,
+                                 const RrtSceneExt *new_ext, void *nodes_out, size_t nodes_cap, uint32_t *prim_order_out,
+                                 RrtBvhInfo *info, double *sah_out) {
+    uint32_t w, l;
+    bvh_defaults(w, l);
+    if (w != 2) return fail(RRT_E_INVALID, "rrt_refit_bvh_lbvh_world builds binary trees only (RRT_BVH_WIDTH=4 is set)");
+    return refit_bvh_world(true, "rrt_refit_bvh_lbvh_world: ", built_spheres, n_spheres, built_ext, max_leaf, kNodeCost,
+                           node_stride, new_spheres, new_ext, nodes_out, nodes_cap, prim_order_out, info, sah_out);
 }
 
 int32_t rrt_tile_rows(uint32_t height, const RrtTile *tile, uint32_t *rows_out) {
@@ -3012,6 +3174,20 @@ extern "C" int32_t rrt_testing_scene_refit_stats(const RrtScene *scene, RrtScene
 
 // Test mode (rrt_testing_refit_form): the refit's per-level launches (0) or its single workgroup (1)
 // whatever the tree's size; -1 restores the automatic choice.
+extern "C" int32_t rrt_testing_lbvh_form(int32_t form) {
+    if (!rrt::set_lbvh_form(form)) return fail(RRT_E_INVALID, "rrt_testing_lbvh_form: the form is -1, 0 or 1");
+    return RRT_OK;
+}
+extern "C" int32_t rrt_testing_scene_build_stats(const RrtScene *scene, RrtSceneBuildStats *out) {
+    if (!scene || !out) return fail(RRT_E_INVALID, "rrt_testing_scene_build_stats: null scene or out");
+    if (!scene->builder)
+        return fail(RRT_E_INVALID, "rrt_testing_scene_build_stats: the scene holds no device builder (RRT_FLAG_DEVICE_BVH or "
+                                   "RRT_FLAG_FAST_BVH and at least 2 primitives)");
+    const rrt::BuildStats b = scene->builder->stats();
+    out->builder = b.builder, out->launches = b.launches, out->blocking_reads = b.blocking_reads;
+    out->form = b.form, out->shape_attempts = b.shape_attempts;
+    return RRT_OK;
+}
 extern "C" int32_t rrt_testing_refit_form(int32_t form) {
     if (!rrt::set_refit_form(form)) return fail(RRT_E_INVALID, "rrt_testing_refit_form: the form is -1, 0 or 1");
     return RRT_OK;

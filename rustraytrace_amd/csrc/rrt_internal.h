@@ -433,6 +433,10 @@ namespace bvhb {
 struct Box6;
 struct Summary;
 }  // namespace bvhb
+// Of one shape choice (stats_begin() .. ): rrt_testing_scene_build_stats.
+struct BuildStats {
+    uint64_t builder, launches, blocking_reads, form, shape_attempts;
+};
 class DeviceBvhBuilder {
 public:
     DeviceBvhBuilder();
@@ -480,6 +484,20 @@ public:
     hipError_t reserve_refit();
     hipError_t tree_cost(double *sah, double *sah_at_build);
     uint64_t refits_since_build() const;
+    // The fast builder (rrt_bvh_lbvh.h) over the same boxes, objects and tree storage, so that emit,
+    // emit_into, refit, emit_refit and tree_cost serve its tree as they serve build()'s. lbvh_build:
+    // the sorted order and topology, and by the build's one blocking read the summaries of two shapes
+    // (leaves of up to leaf_a, leaf_b); the small form also finishes one in its launch: shape 0 when
+    // its node count is at most fit_nodes, else shape 1 (the caller's prediction of its own choice).
+    // lbvh_finish: shape 0 or 1 becomes the held tree (numbers, links, boxes; no read), node_cost the
+    // price tree_cost() weighs its node children by. The workspace is allocated by the first
+    // lbvh_build (reserve_lbvh), sized for n_boxes; later ones allocate nothing.
+    hipError_t reserve_lbvh();
+    hipError_t lbvh_build(uint32_t leaf_a, uint32_t leaf_b, uint32_t fit_nodes, bvhb::Summary out[2]);
+    hipError_t lbvh_finish(int shape, double node_cost, bvhb::Summary *out);
+    static uint32_t lbvh_small_max();
+    void stats_begin();
+    BuildStats stats() const;
 
 private:
     struct Impl;
@@ -542,5 +560,8 @@ hipError_t launch_bquad_records(uint32_t n, const void *d_bquads, GQuad *gquads,
 // Test support (rrt_testing_refit_form): force the refit's per-level launches (0) or its single
 // workgroup (1); -1: the automatic choice. False for another value.
 bool set_refit_form(int form);
+// rrt_testing_lbvh_form: the fast builder's launch-per-phase form (0) or its single workgroup (1).
+bool set_lbvh_form(int form);
+constexpr uint32_t kFlagFastBvh = 0x40u;
 
 }  // namespace rrt

@@ -49,6 +49,8 @@ def parse(argv=None):
                          "quantiser (color.rs), bit-identical to the 1-GPU f64 frame")
     ap.add_argument("--device-bvh", action="store_true",
                     help="each rank builds its scene's BVH on its device (RRT_FLAG_DEVICE_BVH) instead of the host")
+    ap.add_argument("--fast-bvh", action="store_true",
+                    help="each rank builds its BVH on its device by the LBVH builder (RRT_FLAG_FAST_BVH; implies --device-bvh)")
     ap.add_argument("--gather", choices=("accum", "rgb8"), default="accum",
                     help="what the ranks gather: their accum tiles (16 B/pixel, 32 with --f64), or rgb8: each rank "
                          "quantises its tile on the device (the books quantiser with --f64, render_io's without) and "
@@ -96,7 +98,7 @@ def main(argv=None) -> int:
     scene = rrt.config_scene(args.config, **over)
     W, H, S = scene.width, scene.height, scene.spp
 
-    ds = rrt.DeviceScene(scene, device=device, f64=args.f64, device_bvh=args.device_bvh)
+    ds = rrt.DeviceScene(scene, device=device, f64=args.f64, device_bvh=args.device_bvh, fast_bvh=args.fast_bvh)
     if args.band <= 0:
         args.band = balanced_band(H, world)
     tile = ds.tile(band_rows=args.band, rank=rank, n_ranks=world, sample_begin=0, sample_end=S)

@@ -74,13 +74,13 @@ def scene_ext(scene: SceneData):
 
 
 def render(scene: SceneData, spp: Optional[int] = None, n_gpus: int = 1, quiet: bool = True,
-           device_bvh: bool = False) -> np.ndarray:
+           device_bvh: bool = False, fast_bvh: bool = False) -> np.ndarray:
     """Render `scene` on `n_gpus` GPUs; returns the RGBA float32 accum (H, W, 4), w = sample count."""
     lib = _lib.load()
     accum = np.zeros((scene.height, scene.width, 4), dtype=np.float32)
     tex, ntex, keep = _textures(scene)
     ext, keep_ext = scene_ext(scene)
-    flags = scene.flags | (_lib.FLAG_QUIET if quiet else 0) | (_lib.FLAG_DEVICE_BVH if device_bvh else 0)
+    flags = scene.flags | (_lib.FLAG_QUIET if quiet else 0) | (_lib.FLAG_DEVICE_BVH if device_bvh else 0) | (_lib.FLAG_FAST_BVH if fast_bvh else 0)
     _lib.check(lib.rrt_hip_render_ex(_lib.ptr(scene.camera), _lib.ptr(scene.spheres), len(scene.spheres),
                                      _lib.ptr(scene.materials), len(scene.materials),
                                      ctypes.cast(tex, ctypes.c_void_p) if tex is not None else None, ntex,
@@ -90,12 +90,12 @@ def render(scene: SceneData, spp: Optional[int] = None, n_gpus: int = 1, quiet: 
     return accum
 
 
-def _f64_ex_args(scene: SceneData, spp, n_gpus, quiet, device_bvh, out):
+def _f64_ex_args(scene: SceneData, spp, n_gpus, quiet, device_bvh, out, fast_bvh=False):
     """The argument list of the f64 _ex one-shots (RrtSceneExt passed, both f64 flags implied) and what
     must stay alive during the call."""
     tex, ntex, keep = _textures(scene)
     ext, keep_ext = scene_ext(scene)
-    flags = scene.flags | (_lib.FLAG_QUIET if quiet else 0) | (_lib.FLAG_DEVICE_BVH if device_bvh else 0)
+    flags = scene.flags | (_lib.FLAG_QUIET if quiet else 0) | (_lib.FLAG_DEVICE_BVH if device_bvh else 0) | (_lib.FLAG_FAST_BVH if fast_bvh else 0)
     args = (_lib.ptr(scene.camera), _lib.ptr(scene.spheres), len(scene.spheres), _lib.ptr(scene.materials),
             len(scene.materials), ctypes.cast(tex, ctypes.c_void_p) if tex is not None else None, ntex,
             ctypes.byref(ext) if ext is not None else None, int(spp or 0), int(n_gpus), flags, _lib.ptr(out))
@@ -103,7 +103,7 @@ def _f64_ex_args(scene: SceneData, spp, n_gpus, quiet, device_bvh, out):
 
 
 def render_f64(scene: SceneData, spp: Optional[int] = None, n_gpus: int = 1, quiet: bool = True,
-               device_bvh: bool = False, book2: bool = False) -> np.ndarray:
+               device_bvh: bool = False, book2: bool = False, fast_bvh: bool = False) -> np.ndarray:
     """rrt_hip_render_f64: the books path's own f64 arithmetic (RRT_FLAG_F64, book-1 scenes);
     returns the RGBA float64 accum (H, W, 4) of f64 sums, w = sample count. book2=True:
     rrt_hip_render_f64_ex with the scene's RrtSceneExt (RRT_FLAG_F64_BOOK2: moving spheres, quads,
@@ -111,7 +111,7 @@ def render_f64(scene: SceneData, spp: Optional[int] = None, n_gpus: int = 1, qui
     lib = _lib.load()
     if book2:
         accum = np.zeros((scene.height, scene.width, 4), dtype=np.float64)
-        args, keep = _f64_ex_args(scene, spp, n_gpus, quiet, device_bvh, accum)
+        args, keep = _f64_ex_args(scene, spp, n_gpus, quiet, device_bvh, accum, fast_bvh)
         _lib.check(lib.rrt_hip_render_f64_ex(*args))
         del keep
         return accum
@@ -119,7 +119,7 @@ def render_f64(scene: SceneData, spp: Optional[int] = None, n_gpus: int = 1, qui
         raise ValueError("render_f64: book-1 scenes only (RRT_FLAG_F64)")
     accum = np.zeros((scene.height, scene.width, 4), dtype=np.float64)
     tex, ntex, keep = _textures(scene)
-    flags = scene.flags | _lib.FLAG_F64 | (_lib.FLAG_QUIET if quiet else 0) | (_lib.FLAG_DEVICE_BVH if device_bvh else 0)
+    flags = scene.flags | _lib.FLAG_F64 | (_lib.FLAG_QUIET if quiet else 0) | (_lib.FLAG_DEVICE_BVH if device_bvh else 0) | (_lib.FLAG_FAST_BVH if fast_bvh else 0)
     _lib.check(lib.rrt_hip_render_f64(_lib.ptr(scene.camera), _lib.ptr(scene.spheres), len(scene.spheres),
                                       _lib.ptr(scene.materials), len(scene.materials),
                                       ctypes.cast(tex, ctypes.c_void_p) if tex is not None else None, ntex,
@@ -129,7 +129,7 @@ def render_f64(scene: SceneData, spp: Optional[int] = None, n_gpus: int = 1, qui
 
 
 def render_rgb8(scene: SceneData, spp: Optional[int] = None, n_gpus: int = 1, quiet: bool = True,
-                device_bvh: bool = False) -> np.ndarray:
+                device_bvh: bool = False, fast_bvh: bool = False) -> np.ndarray:
     """rrt_hip_render_rgb8_ex: render and quantise on the device (render_io.rs quantiser);
     returns (H, W, 3) uint8, identical to quantize_accum(render(scene)) at the same spp, for
     every book (the scene's RrtSceneExt — motion, Perlin tables, quads, media, lights — is passed)."""
@@ -137,7 +137,7 @@ def render_rgb8(scene: SceneData, spp: Optional[int] = None, n_gpus: int = 1, qu
     out = np.zeros((scene.height, scene.width, 3), dtype=np.uint8)
     tex, ntex, keep = _textures(scene)
     ext, keep_ext = scene_ext(scene)
-    flags = scene.flags | (_lib.FLAG_QUIET if quiet else 0) | (_lib.FLAG_DEVICE_BVH if device_bvh else 0)
+    flags = scene.flags | (_lib.FLAG_QUIET if quiet else 0) | (_lib.FLAG_DEVICE_BVH if device_bvh else 0) | (_lib.FLAG_FAST_BVH if fast_bvh else 0)
     _lib.check(lib.rrt_hip_render_rgb8_ex(_lib.ptr(scene.camera), _lib.ptr(scene.spheres), len(scene.spheres),
                                           _lib.ptr(scene.materials), len(scene.materials),
                                           ctypes.cast(tex, ctypes.c_void_p) if tex is not None else None, ntex,
@@ -155,7 +155,7 @@ def quantize_accum_async(n_pixels: int, d_accum_ptr: int, samples_per_pixel: int
 
 
 def render_f64_rgb8(scene: SceneData, spp: Optional[int] = None, n_gpus: int = 1, quiet: bool = True,
-                    device_bvh: bool = False, book2: bool = False) -> np.ndarray:
+                    device_bvh: bool = False, book2: bool = False, fast_bvh: bool = False) -> np.ndarray:
     """rrt_hip_render_f64_rgb8: the f64 books kernel (RRT_FLAG_F64, book-1 scenes), then the books
     path's quantiser (color.rs) on the device; returns (H, W, 3) uint8, identical to
     quantize_accum_books_f64(render_f64(scene)) at the same spp. book2=True: rrt_hip_render_f64_rgb8_ex
@@ -163,7 +163,7 @@ def render_f64_rgb8(scene: SceneData, spp: Optional[int] = None, n_gpus: int = 1
     lib = _lib.load()
     if book2:
         out = np.zeros((scene.height, scene.width, 3), dtype=np.uint8)
-        args, keep = _f64_ex_args(scene, spp, n_gpus, quiet, device_bvh, out)
+        args, keep = _f64_ex_args(scene, spp, n_gpus, quiet, device_bvh, out, fast_bvh)
         _lib.check(lib.rrt_hip_render_f64_rgb8_ex(*args))
         del keep
         return out
@@ -171,7 +171,7 @@ def render_f64_rgb8(scene: SceneData, spp: Optional[int] = None, n_gpus: int = 1
         raise ValueError("render_f64_rgb8: book-1 scenes only (RRT_FLAG_F64)")
     out = np.zeros((scene.height, scene.width, 3), dtype=np.uint8)
     tex, ntex, keep = _textures(scene)
-    flags = scene.flags | _lib.FLAG_F64 | (_lib.FLAG_QUIET if quiet else 0) | (_lib.FLAG_DEVICE_BVH if device_bvh else 0)
+    flags = scene.flags | _lib.FLAG_F64 | (_lib.FLAG_QUIET if quiet else 0) | (_lib.FLAG_DEVICE_BVH if device_bvh else 0) | (_lib.FLAG_FAST_BVH if fast_bvh else 0)
     _lib.check(lib.rrt_hip_render_f64_rgb8(_lib.ptr(scene.camera), _lib.ptr(scene.spheres), len(scene.spheres),
                                            _lib.ptr(scene.materials), len(scene.materials),
                                            ctypes.cast(tex, ctypes.c_void_p) if tex is not None else None, ntex,
@@ -332,6 +332,58 @@ def build_bvh_binned(scene: SceneData, max_leaf: int, node_cost: float, node_str
     return nodes, order[:n_prims], info.as_dict()
 
 
+def build_bvh_lbvh(scene: SceneData, max_leaf: int, node_stride: int):
+    """rrt_build_bvh_lbvh (host only): the tree RRT_FLAG_FAST_BVH builds for one shape (max_leaf) and node
+    format (node_stride 80 or 32), by the LBVH builder's sequential host twin. Returns (node bytes uint8,
+    leaf-order permutation uint32, info dict) like build_bvh."""
+    lib = _lib.load()
+    info = _lib.RrtBvhInfo()
+    n = len(scene.spheres)
+    ext, keep = scene_ext(scene)
+    n_prims = n + (0 if ext is None else ext.n_quads + ext.n_media)
+    extp = ctypes.byref(ext) if ext is not None else None
+
+    def build(nodes_p, cap, order_p):
+        return lib.rrt_build_bvh_lbvh(_lib.ptr(scene.spheres), n, extp, int(max_leaf), int(node_stride), nodes_p, cap,
+                                      order_p, ctypes.byref(info))
+
+    _lib.check(build(None, 0, None))
+    nodes = np.zeros(info.node_bytes, dtype=np.uint8)
+    order = np.zeros(max(n_prims, 1), dtype=np.uint32)
+    _lib.check(build(_lib.ptr(nodes), nodes.size, _lib.ptr(order)))
+    del keep
+    return nodes, order[:n_prims], info.as_dict()
+
+
+def refit_bvh_lbvh_world(built_scene: SceneData, new_scene: SceneData, max_leaf: int, node_stride: int):
+    """rrt_refit_bvh_lbvh_world (host only): build_bvh_lbvh's tree of `built_scene` with its boxes
+    recomputed over new_scene's spheres, motion, quads, media and boundary quads: the specification of
+    the refits of a scene the LBVH builder built. Returns (node bytes, leaf order, info dict, sah)."""
+    lib = _lib.load()
+    info = _lib.RrtBvhInfo()
+    sah = ctypes.c_double(0.0)
+    n = len(built_scene.spheres)
+    sp = np.ascontiguousarray(new_scene.spheres, dtype=_lib.SPHERE_DTYPE)
+    assert len(sp) == n, "a refit keeps the sphere count"
+    ext, keep = scene_ext(built_scene)
+    new_ext, keep_new = scene_ext(new_scene)
+    n_prims = n + (0 if ext is None else ext.n_quads + ext.n_media)
+    extp = ctypes.byref(ext) if ext is not None else None
+    new_extp = ctypes.byref(new_ext) if new_ext is not None else None
+
+    def refit(nodes_p, cap, order_p):
+        return lib.rrt_refit_bvh_lbvh_world(_lib.ptr(built_scene.spheres), n, extp, int(max_leaf), int(node_stride),
+                                            _lib.ptr(sp), new_extp, nodes_p, cap, order_p, ctypes.byref(info),
+                                            ctypes.byref(sah))
+
+    _lib.check(refit(None, 0, None))
+    nodes = np.zeros(info.node_bytes, dtype=np.uint8)
+    order = np.zeros(max(n_prims, 1), dtype=np.uint32)
+    _lib.check(refit(_lib.ptr(nodes), nodes.size, _lib.ptr(order)))
+    del keep, keep_new
+    return nodes, order[:n_prims], info.as_dict(), float(sah.value)
+
+
 def refit_bvh_binned(built_scene: SceneData, new_spheres, new_motion, max_leaf: int, node_cost: float, node_stride: int,
                      new_quads=None):
     """rrt_refit_bvh_binned_ex (host only): build_bvh_binned's tree of `built_scene` with its boxes
@@ -428,13 +480,14 @@ class DeviceScene:
     """RrtScene*: scene + BVH resident on one device; renders tiles asynchronously on a stream."""
 
     def __init__(self, scene: SceneData, device: int = 0, f64: bool = False, device_bvh: bool = False,
-                 f64_book2: bool = False):
+                 f64_book2: bool = False, fast_bvh: bool = False):
         """f64=True: the books path's f64 kernel (RRT_FLAG_F64, book-1 scenes); with f64_book2=True also
         moving spheres, quads and checker textures (RRT_FLAG_F64_BOOK2, which implies f64). device_bvh=True:
-        the BVH is built on the device (RRT_FLAG_DEVICE_BVH) instead of the host."""
+        the BVH is built on the device (RRT_FLAG_DEVICE_BVH) instead of the host. fast_bvh=True: on the
+        device by the LBVH builder (RRT_FLAG_FAST_BVH, implies device_bvh): cheap rebuilds, a slower tree."""
         lib = _lib.load()
         self.scene = scene
-        flags = scene.flags | (_lib.FLAG_F64 if f64 else 0) | (_lib.FLAG_DEVICE_BVH if device_bvh else 0)
+        flags = scene.flags | (_lib.FLAG_F64 if f64 else 0) | (_lib.FLAG_DEVICE_BVH if device_bvh else 0) | (_lib.FLAG_FAST_BVH if fast_bvh else 0)
         flags |= _lib.FLAG_F64_BOOK2 if f64_book2 else 0
         self._lib = lib
         self._h = ctypes.c_void_p()
@@ -618,6 +671,22 @@ class DeviceScene:
         c = _lib.RrtTreeCost()
         _lib.check(self._lib.rrt_scene_tree_cost(self._h, ctypes.byref(c)))
         return {"sah": float(c.sah), "sah_at_build": float(c.sah_at_build), "refits_since_build": int(c.refits_since_build)}
+
+    def set_builder(self, builder: str) -> None:
+        """rrt_scene_set_builder: the builder of the next update_*: "binned" (quality) or "lbvh" (speed)."""
+        if builder not in _lib.BUILDERS:
+            raise ValueError(f"set_builder: {builder!r} is not one of {sorted(_lib.BUILDERS)}")
+        _lib.check(self._lib.rrt_scene_set_builder(self._h, _lib.BUILDERS[builder]))
+
+    def build_stats(self) -> dict:
+        """rrt_testing_scene_build_stats (test support): of the last device build, the builder ("binned" or
+        "lbvh"), its kernel launches (a library sort counts once), blocking reads, form (1: the LBVH's
+        single workgroup) and shape attempts."""
+        st = _lib.RrtSceneBuildStats()
+        _lib.check(self._lib.rrt_testing_scene_build_stats(self._h, ctypes.byref(st)))
+        d = {k: int(getattr(st, k)) for k, _ in st._fields_}
+        d["builder"] = {v: k for k, v in _lib.BUILDERS.items()}[d["builder"]]
+        return d
 
     def refit_stats(self) -> dict:
         """rrt_testing_scene_refit_stats (test support): refits so far; the last one's device
