@@ -114,12 +114,35 @@ __device__ __forceinline__ float sqrt_rn_big(float x) {
     s = rm <= 0.0f ? sm : s;
     return rp > 0.0f ? sp : s;
 }
+// The same value for x = +0 or x >= 2^-96 (+inf, NaN) in six instructions, one of them transcendental,
+// and no compare: y = v_rsq_f32(x), the estimate s = x * y and one residual step
+// s + fma(-s, s, x) * (y / 2) — the step the compiler's own expansion ends with, without its refinement
+// of y and its rescaling of small arguments. Where y is 0 or infinite (x = +inf, +0) the step gives
+// NaN, and v_div_fixup_f32 with y as the denominator of 1 / y puts the quotient's special value there
+// (+inf, +0) and passes the step's result on everywhere else. x is dead after the residual, so the form
+// holds no register more than sqrt_rn_big, which takes nine instructions and two wait-state no-ops.
+// Exhaustive on the device: rrt_testing_recip_check counts both forms; tools/recip/sqrt_check.hip
+// lists the candidates tried. The leaf loop takes it (sqrt_rn_disc).
+__device__ __forceinline__ float sqrt_rn_res(float x) {
+    const float y = __builtin_amdgcn_rsqf(x);
+    const float s = x * y, h = 0.5f * y;
+    const float r = __builtin_fmaf(-s, s, x);
+    const float t = __builtin_fmaf(r, h, s);
+    return __builtin_amdgcn_div_fixupf(t, y, 1.0f);
+}
 
 // sqrt(x) correctly rounded for any x: sqrt_rn_big unless an active lane of the wave holds a
 // nonzero |x| < 2^-96 (a wave-uniform branch to the library sequence; sqrt_rn_big differs from the
 // IEEE root only on positive and negative arguments below 2^-96 other than +-0, per the device check)
 __device__ __forceinline__ float sqrt_rn(float x) {
     if (__ballot(__builtin_fabsf(x) < 0x1.0p-96f && x != 0.0f) == 0) return sqrt_rn_big(x);
+    return __builtin_sqrtf(x);
+}
+// sqrt_rn for the leaf loop's discriminant, which is not below zero there (the loop has left on
+// disc < 0; NaN and -0 stay): x < 2^-96 alone is the range check, one compare into the ballot. A
+// disc of +-0 then takes the library arm, which returns the same +-0.
+__device__ __forceinline__ float sqrt_rn_disc(float x) {
+    if (__builtin_expect(__ballot(x < 0x1.0p-96f) == 0, 1)) return sqrt_rn_res(x);
     return __builtin_sqrtf(x);
 }
 
@@ -636,10 +659,24 @@ __device__ __forceinline__ void test_prim(const PR &prim_cr, float4 cr, float4 m
     // when no lane takes it.
     if (disc < 0.0f) return;
     if constexpr (RRT_PHASE_TIMING == 3) cnt.d2 += 1;
-    const float sq = sqrt_rn(disc);
+    const float sq = sqrt_rn_disc(disc);
     float root = div_by_a(h - sq, rk);
-    if (!(0.001f < root)) root = div_by_a(h + sq, rk);
-    const bool accept = 0.001f < root && root < closest;
+    // One compare of the near root against tmin: a wave in which every active lane passes it (no
+    // ray starts inside its sphere) accepts on root < closest alone and branches past the far-root
+    // arm, as div_by_a's rare arm is guarded. A NaN near root fails the compare and, like one at or
+    // below tmin, takes the far root, which is compared again inside the arm.
+    // `lt` is formed first (the empty asm holds the order): the tmin compare then fills one of the two
+    // wait states between the compare that writes the mask and the selects that read it.
+    uint64_t lt = __ballot(root < closest);
+    asm volatile("" : "+v"(root));
+    const bool below = !(0.001f < root);
+    if (__builtin_expect(__ballot(below) != 0, 0)) {
+        float hh = h;
+        asm volatile("" : "+v"(hh));
+        if (below) root = div_by_a(hh + sq, rk);
+        lt = __ballot(0.001f < root) & __ballot(root < closest);
+    }
+    const bool accept = __builtin_amdgcn_inverse_ballot_w64(lt);
     closest = accept ? root : closest;
     hit_prim = accept ? i : hit_prim;
 }
@@ -2175,7 +2212,8 @@ namespace {
 // Every f32 bit pattern: out[0] counts s with |s| in [2^-126, 2^126), +-0, +-inf or NaN whose
 // recip_rn(s) is not the IEEE 1.0f / s (NaN results compare equal); out[1] counts s with |s| <
 // 2^126 or NaN whose clamped_slope(s) is not clamp_inv(1.0f / s); out[2] counts s = +0 or s >=
-// 2^-96 (+inf and positive NaN patterns included) whose sqrt_rn_big(s) is not the IEEE sqrt.
+// 2^-96 (+inf and positive NaN patterns included) whose sqrt_rn_big(s) or sqrt_rn_res(s) is not the
+// IEEE sqrt.
 __global__ __launch_bounds__(256) void rrt_recip_check(unsigned long long *out) {
     uint32_t bad0 = 0, bad1 = 0, bad2 = 0;
     for (uint64_t k = blockIdx.x * 256ull + threadIdx.x; k < (1ull << 32); k += (uint64_t)gridDim.x * 256ull) {
@@ -2187,7 +2225,7 @@ __global__ __launch_bounds__(256) void rrt_recip_check(unsigned long long *out) 
         if ((normal || special) && !same(recip_rn(s), 1.0f / s)) ++bad0;
         if ((a < 0x7e800000u || a > 0x7f800000u) && !same(clamped_slope(s), clamp_inv(1.0f / s))) ++bad1;
         // +-0 and every |s| >= 2^-96 of either sign (negatives: NaN like the IEEE root; -0: -0), +-inf, NaN
-        if ((a == 0u || a >= 0x0f800000u) && !same(sqrt_rn_big(s), __builtin_sqrtf(s))) ++bad2;
+        if ((a == 0u || a >= 0x0f800000u) && !(same(sqrt_rn_big(s), __builtin_sqrtf(s)) && same(sqrt_rn_res(s), __builtin_sqrtf(s)))) ++bad2;
     }
     if (bad0) atomicAdd(&out[0], (unsigned long long)bad0);
     if (bad1) atomicAdd(&out[1], (unsigned long long)bad1);
