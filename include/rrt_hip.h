@@ -1060,6 +1060,10 @@ int32_t rrt_testing_sqrt64_check(uint64_t *out);
  *                                                 aux of both: u32 count, 12 bytes of padding, then count RrtLight records
  *                                                 (device records and the quads' derived planes formed by scene
  *                                                 creation's code); 1 <= count <= 65536
+ *   SLOPES      o.xyz, d.xyz                      ray_consts(o, d) as the traversal reads it: inv 3, oi 3, the plane-pair
+ *                                                 offsets ox, oy, oz (u32) of a staged node; then clamped_slope of each
+ *                                                 component of d on its own 3 (what inv must equal); last ox of the
+ *                                                 f16-node form (the three rotations packed, u32). 13 words.
  * div_by_a<true> / <false> (and with them exact_root<true> / <false> and test_range's two divisions)
  * are the same function since div_by_a guards its own range; both instantiations are still run.
  * Every input, NaN and infinities included, is ordinary arithmetic. */
@@ -1078,7 +1082,8 @@ enum RrtDeviceOp {
     RRT_OP_QUAD = 11,
     RRT_OP_SPHERE = 12,
     RRT_OP_LIGHTS_PDF = 13,
-    RRT_OP_LIGHTS_RANDOM = 14
+    RRT_OP_LIGHTS_RANDOM = 14,
+    RRT_OP_SLOPES = 15
 };
 int32_t rrt_testing_device_ops(uint32_t op, uint32_t n, const void *in, void *out, const void *aux);
 

@@ -194,7 +194,7 @@ DEVICE_OPS = {
     "SIN": (0, 1, 1), "COS": (1, 1, 1), "LOG": (2, 1, 1), "ACOS": (3, 1, 1), "ATAN2": (4, 2, 1),
     "DIV_A": (5, 2, 4), "DIV_CONST": (6, 1, 4), "FLOOR_I32": (7, 1, 1), "CHECKER": (8, 4, 1),
     "PERLIN": (9, 3, 8), "VEC": (10, 9, 13), "QUAD": (11, 9, 2), "SPHERE": (12, 11, 13),
-    "LIGHTS_PDF": (13, 6, 1), "LIGHTS_RANDOM": (14, 6, 4),
+    "LIGHTS_PDF": (13, 6, 1), "LIGHTS_RANDOM": (14, 6, 4), "SLOPES": (15, 6, 13),
 }
 
 # == RrtDeviceOp64 (include/rrt_hip.h, test support): op -> (code, f64 columns in, 64-bit words out)

@@ -319,6 +319,30 @@ __device__ __forceinline__ float clamped_slope(float s) {
     return __builtin_fabsf(s) < 0x1.0p-126f ? __builtin_copysignf(0x1.0p64f, s) : clamp_inv(recip_rn(s));
 }
 
+// clamped_slope of a direction's three components. A normal component (neither zero, subnormal,
+// infinite nor NaN) has a finite v_rcp_f32 estimate and a finite residual, so recip_rn keeps its
+// refined value without the NaN select and clamped_slope's small-|s| arm is not taken: the hot path
+// is the estimate, two fmas and the clamp per component, straight-line. One ballot over the three
+// v_cmp_class tests sends a wave that holds any other component to clamped_slope itself, per lane
+// (the div_by_a pattern: the empty asm keeps the arm behind its scalar branch). Three divergent
+// regions and three selects less per segment start.
+__device__ __forceinline__ float slope_normal(float s) {
+    const float r = __builtin_amdgcn_rcpf(s);
+    return clamp_inv(__builtin_fmaf(__builtin_fmaf(-s, r, 1.0f), r, r));
+}
+__device__ __forceinline__ V3 clamped_slopes(V3 d) {
+    constexpr int kNotNormal = 0x2f7;  // sNaN, qNaN, -inf, -subnormal, -0, +0, +subnormal, +inf
+    const bool outside = __builtin_amdgcn_classf(d.x, kNotNormal) | __builtin_amdgcn_classf(d.y, kNotNormal) |
+                         __builtin_amdgcn_classf(d.z, kNotNormal);
+    V3 inv = v3(slope_normal(d.x), slope_normal(d.y), slope_normal(d.z));
+    if (__ballot(outside) != 0) {
+        V3 c = d;
+        asm volatile("" : "+v"(c.x), "+v"(c.y), "+v"(c.z));
+        if (outside) inv = v3(clamped_slope(c.x), clamped_slope(c.y), clamped_slope(c.z));
+    }
+    return inv;
+}
+
 // kLdsNodes: ox, oy, oz are the byte offsets of the (entry, exit) plane pairs in an LDS GNode; for
 // the 32-B f16 nodes read from global memory (kOrd16) ox packs the rotations that put each
 // axis's lo | hi << 16 word in (entry, exit) order — 16 when 1/d_a < 0, else 0 — at bits 0, 5 and 10
@@ -369,7 +393,7 @@ __device__ __forceinline__ RayK ray_consts(V3 o, V3 d) {
     // aabb.rs:58 adinv, hoisted per ray, clamped to +-2^64: a zero component then gives a huge
     // finite slope, so fma(P, inv, -o*inv) keeps the sign of (P - o). Unclamped, inf * P - inf * o
     // is NaN or -inf, and a slab that straddles o (lo < 0 < hi about o's sign) rejects the ray.
-    r.inv = v3(clamped_slope(d.x), clamped_slope(d.y), clamped_slope(d.z));
+    r.inv = clamped_slopes(d);
     r.oi = v3(o.x * r.inv.x, o.y * r.inv.y, o.z * r.inv.z);
     if (kLdsNodes) {
         r.ox = r.inv.x < 0.0f ? 4u : 0u;
@@ -401,9 +425,11 @@ __device__ __forceinline__ float div_by_a(float n, const RayK &rk) {
     const float q0 = n * rk.ra;
     const float m = __builtin_fabsf(q0);
     const bool outside = !(m >= 0x1.0p-30f && m < __builtin_inff());
-    const float e0 = __builtin_fmaf(-rk.a, q0, n);
+    // (the remainders as fma(a, -q, n): the negation is a source modifier of q, where fma(-a, q, n)
+    // has the compiler hold -a in a register of its own through the whole traversal)
+    const float e0 = __builtin_fmaf(rk.a, -q0, n);
     const float q1 = __builtin_fmaf(e0, rk.ra, q0);
-    const float e1 = __builtin_fmaf(-rk.a, q1, n);
+    const float e1 = __builtin_fmaf(rk.a, -q1, n);
     float q = __builtin_fmaf(e1, rk.ra, q1);
     // The range check is one ballot over the active lanes and a scalar branch (as in sqrt_rn): the
     // four fmas run straight-line, and only a wave that holds a lane outside the range enters the
@@ -693,9 +719,11 @@ __device__ __forceinline__ void test_range(const PR &prim_cr, int first, int cou
     if (kCount) cnt.spheres += (uint32_t)count;  // every primitive of the range, the skipped one too
     const bool trim = (uint32_t)(skip - first) < (uint32_t)count;
     const int n = count - (trim ? 1 : 0);
-    const int gap = trim ? skip : 0x7fffffff;
+    // "no gap" is all ones under an unsigned compare (primitive indices are below 2^28): an inline
+    // constant of the select, where 0x7fffffff is a literal it cannot take beside vcc and so a register
+    const uint32_t gap = trim ? (uint32_t)skip : 0xffffffffu;
     for (int k = 0; k < n; ++k) {
-        const int i = first + k + (first + k >= gap ? 1 : 0);
+        const int i = first + k + ((uint32_t)(first + k) >= gap ? 1 : 0);
         if constexpr (RRT_PHASE_TIMING == 3) {
             cnt.d0 += wave_slot();
             cnt.d1 += 1;
@@ -912,10 +940,17 @@ __device__ __forceinline__ bool trav_step4(const GNode4 *__restrict__ nodes, con
 struct PathState {
     V3 o, d, T;
     RngState rng;
-    uint32_t k;  // bounce index (camera ray = 0)
+    // The lane's state word: bounce index k (camera ray = 0) << 2 | need_ray << 1 | has — has: the
+    // lane owns a work unit (0 without one: an idle lane's whole word is 0); need_ray: it must start
+    // the next segment of its path. One register through both traversal loops instead of three; the
+    // depth compares and k++ work on the shifted value.
+    uint32_t st;
     float time;  // the camera ray's time draw, kept by every bounce (book 2, moving spheres)
     int skip;    // leaf-order primitive the current segment leaves (exit_skip), -1 none
 };
+
+constexpr uint32_t kStHas = 1u, kStNeedRay = 2u, kStBounce = 4u;  // PathState::st
+constexpr uint32_t kStRouletteFrom = 5u * kStBounce;              // st >= this: k >= 5 (camera.rs:189)
 
 // The primitive a scattered ray cannot meet again in exact arithmetic, skipped by its next
 // closest-hit query (the oracle's exit_skip, oracle/rrt_oracle.cpp): a sphere it leaves
@@ -971,7 +1006,7 @@ __device__ __forceinline__ void camera_ray(const KParams &P, uint32_t x, uint32_
     ps.o = origin;
     ps.d = sub(sample, origin);
     ps.T = v3(1.0f, 1.0f, 1.0f);
-    ps.k = 0;
+    ps.st = kStHas | kStNeedRay;  // k = 0: a new path of a lane that owns a unit
 }
 
 __device__ __forceinline__ RngState path_rng(const KParams &P, uint32_t x, uint32_t y, uint32_t s) {
@@ -1174,6 +1209,13 @@ __device__ __forceinline__ bool shade(const KParams &P, const PR &prims, const G
     float4 qn;  // a quad's (normal, D): its motion slot
     const float4 cr = prims.at(prim, qn);  // the sphere's center at the ray's time (sphere.rs:48)
     const V3 p = v3(__builtin_fmaf(ps.d.x, t, ps.o.x), __builtin_fmaf(ps.d.y, t, ps.o.y), __builtin_fmaf(ps.d.z, t, ps.o.z));  // Ray::at, fused
+    // The next segment's origin and (below) direction are stored as soon as they exist, before the
+    // arms that end the path: a path that ends reads neither again (its lane takes a camera ray or
+    // goes idle), and stored only at the end the old and the new value are live side by side through
+    // every such arm — six registers of the shading pass, which put p and the throughput in scratch.
+    // From here on ps.o is the NEXT segment's origin: nothing below may read it as this ray's origin
+    // (and after `ps.d = dir` below, nothing may read ps.d as this ray's direction).
+    ps.o = p;
     V3 outward;
     bool is_quad = false, is_medium = false;
     if (PR::kHasQuads && cr.w < 0.0f) {  // a quad's plane normal (quad.rs:79); a medium's (1, 0, 0)
@@ -1236,7 +1278,10 @@ __device__ __forceinline__ bool shade(const KParams &P, const PR &prims, const G
         if constexpr (RRT_PHASE_TIMING == 6) cnt.d0 += 1;
         const V3 refl = unit(reflect(ps.d, nrm));
         dir = add(refl, muls(r, m.a.w));
-        if (!(dot(dir, nrm) > 0.0f)) return true;  // absorbed
+        if (!(dot(dir, nrm) > 0.0f)) {  // absorbed
+            ps.d = dir;
+            return true;
+        }
         att = v3(m.a.x, m.a.y, m.a.z);
     } else {  // Dielectric (material.rs:83-102)
         if constexpr (RRT_PHASE_TIMING == 5) {
@@ -1254,7 +1299,12 @@ __device__ __forceinline__ bool shade(const KParams &P, const PR &prims, const G
         else dir = refract(ud, nrm, ri);
         att = v3(1.0f, 1.0f, 1.0f);
     }
-    if (ps.k >= 5u) {  // camera.rs:189-200
+    ps.d = dir;
+    ps.skip = exit_skip(is_quad, is_medium, front, dir, nrm, prim);
+    // T * att first, for the lanes of both arms together: the roulette's survivors scale that same
+    // product by 1 / pr, and a lane it ends has no further use for T
+    ps.T = mul(ps.T, att);
+    if (ps.st >= kStRouletteFrom) {  // camera.rs:189-200
         float pr = att.x;
         if (att.y > pr) pr = att.y;
         if (att.z > pr) pr = att.z;
@@ -1268,14 +1318,9 @@ __device__ __forceinline__ bool shade(const KParams &P, const PR &prims, const G
         float inv_pr;
         if (kBook2 == kBook1Untextured) inv_pr = kind == 2 ? 1.0f / 0.95f : __int_as_float(m.b.y);
         else inv_pr = recip_rn(pr);
-        ps.T = muls(mul(ps.T, att), inv_pr);
-    } else {
-        ps.T = mul(ps.T, att);
+        ps.T = muls(ps.T, inv_pr);
     }
-    ps.o = p;
-    ps.d = dir;
-    ps.k++;
-    ps.skip = exit_skip(is_quad, is_medium, front, dir, nrm, prim);
+    ps.st += kStBounce;
     return false;
 }
 
@@ -1369,6 +1414,7 @@ __device__ __forceinline__ bool shade_b3(const KParams &P, const PR &prims, cons
     float4 qn;  // a quad's (normal, D): its motion slot
     const float4 cr = prims.at(prim, qn);
     const V3 p = v3(__builtin_fmaf(ps.d.x, t, ps.o.x), __builtin_fmaf(ps.d.y, t, ps.o.y), __builtin_fmaf(ps.d.z, t, ps.o.z));  // Ray::at, fused
+    ps.o = p;  // stored at once, as in shade: nothing below may read ps.o as this ray's origin
     V3 outward;
     bool is_quad = false, is_medium = false;
     if (cr.w < 0.0f) {
@@ -1412,7 +1458,8 @@ __device__ __forceinline__ bool shade_b3(const KParams &P, const PR &prims, cons
             else dir = refract(ud, nrm, ri);
             att = v3(1.0f, 1.0f, 1.0f);
         }
-        if (ps.k >= 5u) {
+        ps.d = dir;
+        if (ps.st >= kStRouletteFrom) {
             float pr = att.x;
             if (att.y > pr) pr = att.y;
             if (att.z > pr) pr = att.z;
@@ -1423,13 +1470,17 @@ __device__ __forceinline__ bool shade_b3(const KParams &P, const PR &prims, cons
         } else {
             ps.T = mul(ps.T, att);
         }
-        ps.o = p;
-        ps.d = dir;
-        ps.k++;
+        ps.st += kStBounce;
         ps.skip = exit_skip(is_quad, is_medium, front, dir, nrm, prim);
         return false;
     }
-    // pdf path: the material's attenuation (texture value at the hit)
+    // pdf path. The incoming direction is dead from here on (every exit below ends the path or stores
+    // the new direction): handing its registers the normal, which stays live, says so, and frees them
+    // through the texture and light-sampling code. The stored value is a placeholder that is never
+    // read: NOTHING below this line may read ps.d (a reader, a debug trace included, would get the
+    // normal); code that needs the incoming direction must take it above.
+    ps.d = nrm;
+    // the material's attenuation (texture value at the hit)
     if (kind == 3) {
         const float theta = rrt_acosf(-outward.y);
         const float phi = rrt_atan2f(-outward.z, outward.x) + kPi;
@@ -1444,7 +1495,7 @@ __device__ __forceinline__ bool shade_b3(const KParams &P, const PR &prims, cons
         att = v3(m.a.x, m.a.y, m.a.z);
     }
     float rr = 1.0f;
-    if (ps.k >= 5u) {
+    if (ps.st >= kStRouletteFrom) {
         rr = att.x;
         if (att.y > rr) rr = att.y;
         if (att.z > rr) rr = att.z;
@@ -1481,9 +1532,8 @@ __device__ __forceinline__ bool shade_b3(const KParams &P, const PR &prims, cons
         spdf = cosine < 0.0f ? 0.0f : cosine / kPi;
     }
     ps.T = mul(ps.T, muls(muls(att, spdf), 1.0f / (pdf * rr)));
-    ps.o = p;
     ps.d = dir;
-    ps.k++;
+    ps.st += kStBounce;
     ps.skip = exit_skip(is_quad, is_medium, front, dir, nrm, prim);
     return false;
 }
@@ -1500,7 +1550,7 @@ __device__ __forceinline__ bool shade_any(const KParams &P, const PR &prims, con
 __device__ __forceinline__ void trace_segment(uint32_t xy, uint32_t s, const PathState &ps, float t, int prim) {
 #ifdef RRT_TRACE_X
     if ((xy & 0xffffu) == RRT_TRACE_X && (xy >> 16) == RRT_TRACE_Y && s == RRT_TRACE_S)
-        printf("K k=%u o=(%a %a %a) d=(%a %a %a) t=%a prim=%d T=(%a %a %a) rng=%llx\n", ps.k, ps.o.x, ps.o.y, ps.o.z,
+        printf("K k=%u o=(%a %a %a) d=(%a %a %a) t=%a prim=%d T=(%a %a %a) rng=%llx\n", ps.st >> 2, ps.o.x, ps.o.y, ps.o.z,
                ps.d.x, ps.d.y, ps.d.z, t, prim, ps.T.x, ps.T.y, ps.T.z, (unsigned long long)rng_key(ps.rng));
 #endif
 }
@@ -1586,8 +1636,7 @@ __device__ __forceinline__ void render_body(const KParams &P) {
     const uint32_t lane = threadIdx.x & 63u;
     Counters cnt = {0, 0, 0, 0, 0, 0};
     uint32_t w_rays = 0, w_paths = 0;  // wave-uniform (scalar) ray / path counts
-    // Per-lane flags as 0/1 integers (VGPRs) rather than bools (SGPR lane masks), see tr.node.
-    uint32_t has = 0;     // lane owns a unit
+    // Per-lane flags as integer bits (a VGPR: ps.st) rather than bools (SGPR lane masks), see tr.node.
     bool q_open = true;   // wave-uniform: the queue may still hold units
     // lane's unit: global pixel (x | y << 16), next sample s, end of its sample chunk s_hi
     uint32_t xy = 0, s = 0, s_hi = 0;
@@ -1599,7 +1648,7 @@ __device__ __forceinline__ void render_body(const KParams &P) {
     // leaf tests): lane state lives in VGPR integers, so updating it in divergent code is one
     // v_mov instead of the three exec-mask merges a bool held in an SGPR pair costs.
     tr.node = -1;
-    uint32_t need_ray = 0;  // the lane must start the next segment of its path
+    ps.st = 0;
     // wave-uniform: claimed, not yet assigned units; a wave's first claim goes to its block's queue
     uint32_t pool_base = (blockIdx.x & (kQueues - 1u)) * 64u, pool_left = 0;
     [[maybe_unused]] uint64_t ph0 = 0, ph1 = 0, ph2 = 0, tp = 0;
@@ -1611,7 +1660,7 @@ __device__ __forceinline__ void render_body(const KParams &P) {
         // that shades runs long divergent code; the others hold its successors' work and LDS
         // requests. Same-box against all-equal priorities: C2 +3.0 %, C4 +3.5 %, C5 +2.4 %.
         __builtin_amdgcn_s_setprio(RRT_PRIO_REFILL);
-        uint64_t idle = __ballot(!has);
+        uint64_t idle = __ballot(ps.st == 0);
         if (idle != 0 && pool_left == 0 && q_open) {
             // kQueues interleaved queues with a counter each, 128 B apart: tile-chunk group g (64
             // units) is queue g % kQueues's (g / kQueues)-th claim. One counter took every wave's
@@ -1643,7 +1692,7 @@ __device__ __forceinline__ void render_body(const KParams &P) {
             const uint32_t n = min((uint32_t)__popcll(idle), pool_left);
             // idle lanes below this one (v_mbcnt: no 64-bit lane mask held across the loop)
             const uint32_t r = __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
-            if (!has && r < n) {
+            if (ps.st == 0 && r < n) {
                 const uint32_t u = pool_base + r;
                 {
                     const auto &Q = *kernarg_params();
@@ -1673,32 +1722,30 @@ __device__ __forceinline__ void render_body(const KParams &P) {
                         sum = v3(0.0f, 0.0f, 0.0f);
                         pkey = pixel_key(Q, x, y);
                         ps.rng = path_rng_k(pkey, s);
-                        camera_ray<kBook2 == 4>(P, x, y, s, ps, cnt);
-                        need_ray = 1;
-                        has = 1;
+                        camera_ray<kBook2 == 4>(P, x, y, s, ps, cnt);  // st: has, need_ray
                     }
                 }
             }
             pool_base += n;
             pool_left -= n;
         }
-        if (__ballot(has) == 0) break;
+        if (__ballot(ps.st != 0) == 0) break;
 
         uint32_t seg_done = 0;  // the lane's path ended without a query (depth limit)
         uint32_t started = 0;   // the lane starts a closest-hit query this iteration
-        if (has && need_ray) {
-            if (ps.k >= P.max_depth) {  // ray_color: depth <= 0 -> 0 (no query)
+        if ((ps.st & (kStHas | kStNeedRay)) == (kStHas | kStNeedRay)) {
+            if ((ps.st >> 2) >= P.max_depth) {  // ray_color: depth <= 0 -> 0 (no query)
                 seg_done = 1;
             } else {
                 trav_begin(tr, kWide ? 0 : (int)node_base, kWide ? 0u : stack.bottom);
-                need_ray = 0;
+                ps.st &= ~kStNeedRay;
                 started = 1;
             }
         }
         w_rays += (uint32_t)__popcll(__ballot(started));
         // Traverse until too few lanes of the wave are still in the tree, then let the
         // finished lanes shade and fetch their next segment (wave-uniform ballot exit).
-        const uint32_t live = (uint32_t)__popcll(__ballot(has));
+        const uint32_t live = (uint32_t)__popcll(__ballot(ps.st != 0));
         const uint32_t min_active = (live * P.trav_frac) >> 8;
         if constexpr (RRT_PHASE_TIMING == 1) {
             const uint64_t t = __builtin_amdgcn_s_memtime();
@@ -1711,7 +1758,7 @@ __device__ __forceinline__ void render_body(const KParams &P) {
         constexpr bool kOrd16 = !kLds && !kWide && kBook2 <= RRT_F16_ORDERED_MAX_CLASS;
         constexpr bool kHoldRa = !(kOrd16 && kBook2 == 3);
         if (tr.node >= 0) rk = ray_consts<!kOrd16, kHoldRa>(ps.o, ps.d);
-        const Prims<kBook2> pr{prims, motion, ps.time, P.quads, P.media, P.n_quads, rng_key(ps.rng) ^ ((uint64_t)ps.k << 32), perlin};
+        const Prims<kBook2> pr{prims, motion, ps.time, P.quads, P.media, P.n_quads, rng_key(ps.rng) ^ ((uint64_t)(ps.st >> 2) << 32), perlin};
         if constexpr (kWide) {
             for (;;) {
                 if constexpr (RRT_PHASE_TIMING == 2) {
@@ -1785,10 +1832,10 @@ __device__ __forceinline__ void render_body(const KParams &P) {
             ph1 += t - tp;
             tp = t;
         }
-        const bool shading = has && !need_ray && tr.node < 0;
+        const bool shading = (ps.st & (kStHas | kStNeedRay)) == kStHas && tr.node < 0;
         if (shading) {
-            need_ray = 1;
-            const Prims<kBook2> spr{prims, motion, ps.time, P.quads, P.media, P.n_quads, rng_key(ps.rng) ^ ((uint64_t)ps.k << 32), perlin};
+            ps.st |= kStNeedRay;
+            const Prims<kBook2> spr{prims, motion, ps.time, P.quads, P.media, P.n_quads, rng_key(ps.rng) ^ ((uint64_t)(ps.st >> 2) << 32), perlin};
             if constexpr (Prims<kBook2>::kHasMedia) {
                 // The unbounded media (a fog around the whole scene; rrt_host.cpp unbounded_media):
                 // not in the tree, tested here against the closest hit of the walk, every lane whose
@@ -1833,7 +1880,7 @@ __device__ __forceinline__ void render_body(const KParams &P) {
                 const float4 out = make_float4(sum.x, sum.y, sum.z, (float)(s_hi - (Q.sample_begin + chunk_first(Q, chunk))));
                 if (Q.n_chunks == 1) Q.accum[px] = out;
                 else Q.partial[(size_t)(chunk - Q.chunk_begin) * ((size_t)Q.tile_rows * Q.width) + px] = F3{sum.x, sum.y, sum.z};
-                has = 0;
+                ps.st = 0;
             }
         }
         if constexpr (RRT_PHASE_TIMING == 1) ph2 += __builtin_amdgcn_s_memtime() - tp;
@@ -1860,12 +1907,15 @@ __device__ __forceinline__ void render_body(const KParams &P) {
         st = wave_sum_u32(cnt.spheres);
     }
     if (lane == 0) {
-        if (r) atomicAdd(&P.counters[0], (unsigned long long)r);
-        if (pa) atomicAdd(&P.counters[1], (unsigned long long)pa);
+        // the pointer re-read from the kernarg segment: held from the kernel's start it is a scalar
+        // pair spilled to a VGPR's lanes through the whole work loop
+        unsigned long long *counters = kernarg_params()->counters;
+        if (r) atomicAdd(&counters[0], (unsigned long long)r);
+        if (pa) atomicAdd(&counters[1], (unsigned long long)pa);
         if (kCount) {
-            atomicAdd(&P.counters[2], (unsigned long long)nv);
-            atomicAdd(&P.counters[3], (unsigned long long)bt);
-            atomicAdd(&P.counters[4], (unsigned long long)st);
+            atomicAdd(&counters[2], (unsigned long long)nv);
+            atomicAdd(&counters[3], (unsigned long long)bt);
+            atomicAdd(&counters[4], (unsigned long long)st);
         }
     }
 }
@@ -2342,6 +2392,18 @@ __global__ __launch_bounds__(256) void rrt_device_ops(uint32_t op, uint32_t n, u
             r[12] = sphere_root(make_float4(x[6], x[7], x[8], rad), o, d, 0.001f) ? 1u : 0u;
             break;
         }
+        case RRT_OP_SLOPES: {
+            const V3 o = ld3(x), d = ld3(x + 3);
+            const RayK rk = ray_consts(o, d);  // staged-node form: three plane-pair offsets
+            st3(r, rk.inv);
+            st3(r + 3, rk.oi);
+            r[6] = rk.ox;
+            r[7] = rk.oy;
+            r[8] = rk.oz;
+            st3(r + 9, v3(clamped_slope(d.x), clamped_slope(d.y), clamped_slope(d.z)));
+            r[12] = ray_consts<false>(o, d).ox;  // f16-node form: the three rotations packed
+            break;
+        }
         case RRT_OP_LIGHTS_PDF: r[0] = __float_as_uint(lights_pdf(LP, ld3(x), ld3(x + 3))); break;
         case RRT_OP_LIGHTS_RANDOM: {
             KParams Q = LP;  // the path key: pixel_key reads seed and y * width + x
@@ -2425,6 +2487,7 @@ void device_op_columns(uint32_t op, uint32_t &cols_in, uint32_t &cols_out) {
     case RRT_OP_SPHERE: cols_in = 11, cols_out = 13; break;
     case RRT_OP_LIGHTS_PDF: cols_in = 6, cols_out = 1; break;
     case RRT_OP_LIGHTS_RANDOM: cols_in = 6, cols_out = 4; break;
+    case RRT_OP_SLOPES: cols_in = 6, cols_out = 13; break;
     default: cols_in = cols_out = 0; break;
     }
 }
