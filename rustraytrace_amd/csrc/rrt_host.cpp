@@ -1704,6 +1704,41 @@ static void bvh_info_tree(RrtBvhInfo &bi, const FlatBvh &fb, size_t node_bytes, 
     bi.n_unbounded = fb.n_unbounded;
 }
 
+// ---- the frame of the host twins (rrt_build_bvh_ex, the build twins, the refit twins) -----------------
+// A quad-bounded medium's range lies inside the boundary quads.
+static int32_t check_boundary_ranges(const ExtView &ex, const std::string &prefix) {
+    for (uint32_t m = 0; m < ex.n_media; ++m)
+        if (ex.media[m].boundary_kind == RRT_BOUNDARY_QUADS &&
+            (ex.media[m].count == 0 || (uint64_t)ex.media[m].first + ex.media[m].count > ex.n_bquads))
+            return fail(RRT_E_INVALID, prefix + "medium " + std::to_string(m) + ": boundary quad range out of bounds");
+    return RRT_OK;
+}
+static int32_t check_twin_shape(uint32_t max_leaf, double node_cost, uint32_t node_stride, uint64_t n_prims) {
+    if (max_leaf == 0 || max_leaf > rrt::kMaxLeafPrims || (node_stride != 80u && node_stride != 32u) || !(node_cost == node_cost))
+        return fail(RRT_E_INVALID, "max_leaf must be 1..7, node_stride 80 or 32");
+    if (n_prims >= (1u << 24)) return fail(RRT_E_INVALID, ">= 2^24 primitives");
+    return RRT_OK;
+}
+// n_order: the primitives in the leaf order (the tree's and the unbounded media).
+static void fill_bvh_info(RrtBvhInfo *info, const FlatBvh &fb, size_t n_order, const ExtView &ex, uint32_t max_leaf) {
+    if (!info) return;
+    const bool book2 = ex.motion || ex.n_quads || ex.n_media;
+    *info = RrtBvhInfo{};
+    bvh_info_tree(*info, fb, fb.bytes.size(), max_leaf);
+    info->prim_bytes = (uint64_t)n_order * (rrt::kPrimBytes + (book2 ? rrt::kMotionBytes : 0)) +
+                       ((uint64_t)ex.n_quads + ex.n_bquads) * sizeof(rrt::GQuad) + (uint64_t)ex.n_media * sizeof(rrt::GMedium);
+}
+// The second call of a twin: the nodes and the leaf order into the caller's buffers (nodes_cap 0: the size call).
+static int32_t copy_tree_out(const FlatBvh &fb, const std::vector<uint32_t> &order, void *nodes_out, size_t nodes_cap,
+                             uint32_t *prim_order_out) {
+    if (nodes_cap == 0) return RRT_OK;
+    if (!nodes_out || nodes_cap < fb.bytes.size() || (order.size() && !prim_order_out))
+        return fail(RRT_E_INVALID, "nodes buffer too small (need " + std::to_string(fb.bytes.size()) + " bytes)");
+    std::memcpy(nodes_out, fb.bytes.data(), fb.bytes.size());
+    if (order.size()) std::memcpy(prim_order_out, order.data(), order.size() * sizeof(uint32_t));
+    return RRT_OK;
+}
+
 // What scene creation and a world change (rrt_scene_update_world) alike refuse of a medium's phase
 // material and density. kind_of(k): material k's kind.
 template <class KindOf>
@@ -1736,13 +1771,10 @@ static int32_t scene_create(const RrtCamera *cam, const RrtSphere *spheres, uint
         const RrtMedium &md = ex.media[m];
         const std::string what = "medium " + std::to_string(m);
         if (int rc = check_medium_phase(md, what, n_materials, [&](uint32_t k) { return materials[k].kind; })) return rc;
-        if (md.boundary_kind == RRT_BOUNDARY_QUADS) {
-            if (md.count == 0 || (uint64_t)md.first + md.count > ex.n_bquads)
-                return fail(RRT_E_INVALID, what + ": boundary quad range out of bounds");
-        } else if (md.boundary_kind != RRT_BOUNDARY_SPHERE) {
+        if (md.boundary_kind != RRT_BOUNDARY_QUADS && md.boundary_kind != RRT_BOUNDARY_SPHERE)
             return fail(RRT_E_INVALID, what + ": unknown boundary_kind");
-        }
     }
+    if (int rc = check_boundary_ranges(ex, "")) return rc;
     bool has_motion = false;
     if (motion)
         for (size_t i = 0; i < (size_t)n_spheres * 4 && !has_motion; ++i)
@@ -2155,10 +2187,7 @@ int32_t rrt_build_bvh_ex(const RrtSphere *spheres, uint32_t n_spheres, const Rrt
                          RrtBvhInfo *info) {
     if (n_spheres && !spheres) return fail(RRT_E_INVALID, "null spheres");
     const ExtView ex(ext);
-    for (uint32_t m = 0; m < ex.n_media; ++m)
-        if (ex.media[m].boundary_kind == RRT_BOUNDARY_QUADS &&
-            (ex.media[m].count == 0 || (uint64_t)ex.media[m].first + ex.media[m].count > ex.n_bquads))
-            return fail(RRT_E_INVALID, "medium " + std::to_string(m) + ": boundary quad range out of bounds");
+    if (int rc = check_boundary_ranges(ex, "")) return rc;
     uint32_t dw, dl;
     bvh_defaults(dw, dl);
     if (width == 0) width = dw;
@@ -2171,27 +2200,8 @@ int32_t rrt_build_bvh_ex(const RrtSphere *spheres, uint32_t n_spheres, const Rrt
     // with such materials and no book-2 geometry (then the node price and the tree differ too)
     const bool book2 = ex.motion || ex.n_quads || ex.n_media;
     const FlatBvh fb = scene_bvh(spheres, n_spheres, ex, width, max_leaf, book2, false, order);
-    if (info) {
-        *info = RrtBvhInfo{};
-        info->n_nodes = fb.n_nodes;
-        info->n_leaves = fb.n_leaves;
-        info->max_depth = fb.max_depth;
-        info->max_leaf_size = fb.max_leaf;
-        info->node_bytes = fb.bytes.size();
-        info->node_stride = fb.stride;
-        info->prim_bytes = (uint64_t)order.size() * (rrt::kPrimBytes + (book2 ? rrt::kMotionBytes : 0)) +
-                           ((uint64_t)ex.n_quads + ex.n_bquads) * sizeof(rrt::GQuad) +
-                           (uint64_t)ex.n_media * sizeof(rrt::GMedium);
-        info->width = fb.width;
-        info->max_leaf_param = max_leaf;
-        info->n_unbounded = fb.n_unbounded;
-    }
-    if (nodes_cap == 0) return RRT_OK;
-    if (!nodes_out || nodes_cap < fb.bytes.size() || (order.size() && !prim_order_out))
-        return fail(RRT_E_INVALID, "nodes buffer too small (need " + std::to_string(fb.bytes.size()) + " bytes)");
-    std::memcpy(nodes_out, fb.bytes.data(), fb.bytes.size());
-    if (order.size()) std::memcpy(prim_order_out, order.data(), order.size() * sizeof(uint32_t));
-    return RRT_OK;
+    fill_bvh_info(info, fb, order.size(), ex, max_leaf);
+    return copy_tree_out(fb, order, nodes_out, nodes_cap, prim_order_out);
 }
 
 int32_t rrt_scene_destroy(RrtScene *scene) {
@@ -2228,12 +2238,69 @@ int32_t rrt_scene_set_camera(RrtScene *scene, const RrtCamera *cam) {
 
 namespace {
 
-// What rrt_scene_update_spheres and rrt_scene_refit_spheres refuse before any device call.
-// geometry: the caller is a geometry entry, which brings a book-3 scene's lights along. world: a
-// world entry, which brings the media along too.
-int check_sphere_change(const RrtScene *s, const std::string &fn, const RrtSphere *spheres, uint32_t n_spheres,
-                        const float *motion, bool &has_motion, bool geometry = false, bool world = false) {
+// The three tiers of scene-change entries: the sphere entries (rrt_scene_update_spheres,
+// rrt_scene_refit_spheres), the geometry entries, which bring the quads and a book-3 scene's lights
+// along, and the world entries, which bring the media and the boundary quads along too.
+enum class Tier { Spheres, Geometry, World };
+
+// The six row arrays a change can bring, in staging order: a sphere entry stages the first two, a
+// geometry entry the first four, a world entry all six.
+enum RowKind { kSpheres, kMotion, kQuads, kLights, kMedia, kBquads, kRowKinds };
+
+struct ChangeRows {
+    const void *src;   // the caller's rows; null: the scene's are kept
+    uint32_t count;    // the scene's count of them, fixed at creation
+    size_t elem;       // bytes per row
+    const char *noun;  // "the <noun>" in the error messages
+};
+
+// One change of a scene: what check_change makes of an entry's arguments, and all that update_scene
+// and refit_scene are given.
+struct SceneChange {
+    Tier tier = Tier::Spheres;
+    bool has_motion = false;
+    // the new quads' prim_cr rows pass the sphere32 range check (scene creation's quads_in_sphere32,
+    // from the caller's rows through rrt_quad_form.h)
+    bool quads_in32 = true;
+    // a world update: the new classification, as the unbounded media and the tree's primitives in
+    // their original order
+    std::vector<uint32_t> unbounded, objs;
+    ChangeRows rows[kRowKinds] = {};
+    // how many rows of array k the call brings
+    uint32_t n(int k) const { return rows[k].src ? rows[k].count : 0u; }
+    // new media or boundary quads re-form the boxes of all media (a quad boundary's box needs both)
+    uint32_t n_medium_boxes() const { return (n(kMedia) || n(kBquads)) ? rows[kMedia].count : 0u; }
+    int n_staged() const { return tier == Tier::World ? 6 : tier == Tier::Geometry ? 4 : 2; }
+};
+
+// The device staging of row array k. (static, like the new functions below: this unnamed namespace
+// lies inside the extern "C" block, whose functions the library exports unless they are static.)
+static void **row_slot(RrtScene *s, int k) {
+    switch (k) {
+    case kSpheres: return (void **)&s->d_src_spheres;
+    case kMotion: return (void **)&s->d_src_motion;
+    case kQuads: return (void **)&s->d_src_quads;
+    case kLights: return (void **)&s->d_src_lights;
+    case kMedia: return (void **)&s->d_src_media;
+    default: return (void **)&s->d_src_bquads;
+    }
+}
+
+// What the six entries refuse before any device call, and the change they describe. g: a sphere
+// entry's spheres and motion rows stand in one too. A geometry entry runs the sphere entries' list
+// but for RRT_FLAG_BOOK3, then the quads' and lights' own; a world entry runs that list without its
+// refusal of media and boundary quads, then the media's and boundary quads' own. is_update: the
+// classification of a world entry's new inputs is formed here (unbounded_media, scene creation's
+// rule) and must leave a tree of 2.
+static int check_change(const RrtScene *s, const std::string &fn, Tier tier, const RrtSceneGeometry *g,
+                        const RrtSceneMedia *wm, bool is_update, SceneChange &out) {
     if (!s) return fail(RRT_E_INVALID, fn + "null scene");
+    if (!g) return fail(RRT_E_INVALID, fn + "null geometry");
+    const RrtSphere *spheres = g->spheres;
+    const float *motion = g->sphere_motion;
+    const uint32_t n_spheres = g->n_spheres;
+    bool &has_motion = out.has_motion;
+    out.tier = tier;
     if (n_spheres != s->n_spheres)
         return fail(RRT_E_INVALID, fn + "n_spheres is " + std::to_string(n_spheres) + ", the scene's is " +
                                        std::to_string(s->n_spheres) + " (the primitive count is fixed at creation)");
@@ -2241,10 +2308,10 @@ int check_sphere_change(const RrtScene *s, const std::string &fn, const RrtSpher
     if (!s->device_bvh)
         return fail(RRT_E_INVALID, fn + "the scene was not created with RRT_FLAG_DEVICE_BVH (its tree is rebuilt or "
                                         "refitted by the device builder)");
-    if (s->base.n_media && !world)
+    if (s->base.n_media && tier != Tier::World)
         return fail(RRT_E_INVALID, fn + "scenes with constant media are not updated (which media are unbounded "
                                         "depends on every sphere)");
-    if (!geometry && (s->base.flags & RRT_FLAG_BOOK3))
+    if (tier == Tier::Spheres && (s->base.flags & RRT_FLAG_BOOK3))
         return fail(RRT_E_INVALID, fn + "RRT_FLAG_BOOK3 scenes are not updated (their light list restates geometry)");
     if (!s->builder)
         return fail(RRT_E_INVALID, fn + "a tree of fewer than 2 primitives is the root-leaf form the host builder writes");
@@ -2260,21 +2327,128 @@ int check_sphere_change(const RrtScene *s, const std::string &fn, const RrtSpher
                                         "class is fixed at creation)");
     if (has_motion && !(s->base.flags & RRT_FLAG_RAY_TIME))
         return fail(RRT_E_INVALID, fn + "moving spheres need RRT_FLAG_RAY_TIME (rays carry the camera's time draw)");
+    if (s->n_bquads && tier == Tier::Geometry)
+        return fail(RRT_E_INVALID, fn + "scenes with boundary quads are not updated (they bound constant media)");
+    const uint32_t n_quads = s->base.n_quads, n_lights = s->base.n_lights;
+    const uint32_t n_media = s->base.n_media, n_bquads = s->n_bquads;
+    const RrtQuad *quads = nullptr, *bquads = nullptr;
+    const RrtLight *lights = nullptr;
+    const RrtMedium *media = nullptr;
+    if (g->quads) {
+        if (g->n_quads != n_quads)
+            return fail(RRT_E_INVALID, fn + "n_quads is " + std::to_string(g->n_quads) + ", the scene's is " +
+                                           std::to_string(n_quads) + " (the primitive count is fixed at creation)");
+        for (uint32_t j = 0; j < n_quads; ++j) {
+            const RrtQuad &qd = g->quads[j];
+            const std::string what = fn + "quad " + std::to_string(j);
+            if (qd.material_index >= s->n_materials) return fail(RRT_E_INVALID, what + " material_index out of range");
+            if (s->mat_kinds[qd.material_index] == RRT_MAT_TEXTURED_LAMBERTIAN)
+                return fail(RRT_E_INVALID, what + ": image textures on quads are not supported");
+            if (!rrt::quad_is_regular(qd.q, qd.u, qd.v))
+                return fail(RRT_E_INVALID, what + " is degenerate: q, u and v must be finite and u x v must have a "
+                                                  "finite, non-zero length");
+            out.quads_in32 = out.quads_in32 && row_in_sphere32(qd.q[0], qd.q[1], qd.q[2], -(float)(j + 1));
+        }
+        quads = g->quads;
+    }
+    if (s->base.flags & RRT_FLAG_BOOK3) {
+        if (!g->lights)
+            return fail(RRT_E_INVALID, fn + "lights are missing: an RRT_FLAG_BOOK3 scene's light list restates geometry "
+                                            "and is given with it");
+        if (g->n_lights != n_lights)
+            return fail(RRT_E_INVALID, fn + "n_lights is " + std::to_string(g->n_lights) + ", the scene's is " +
+                                           std::to_string(n_lights) + " (the light count is fixed at creation)");
+        for (uint32_t l = 0; l < n_lights; ++l) {
+            const RrtLight &L = g->lights[l];
+            const std::string what = fn + "light " + std::to_string(l);
+            if (L.kind != s->light_kinds[l])
+                return fail(RRT_E_INVALID, what + ": kind " + std::to_string(L.kind) + " differs from the scene's entry (" +
+                                               std::to_string(s->light_kinds[l]) + ")");
+            if (L.kind == RRT_LIGHT_QUAD && !rrt::quad_is_regular(L.a, L.u, L.v))
+                return fail(RRT_E_INVALID, what + " is a degenerate quad: a, u and v must be finite and u x v must have "
+                                                  "a finite, non-zero length");
+        }
+        lights = g->lights;
+    } else if (g->lights || g->n_lights) {
+        return fail(RRT_E_INVALID, fn + "lights are given, but the scene was not created with RRT_FLAG_BOOK3");
+    }
+    if (wm && wm->media) {
+        if (wm->n_media != n_media)
+            return fail(RRT_E_INVALID, fn + "n_media is " + std::to_string(wm->n_media) + ", the scene's is " +
+                                           std::to_string(n_media) + " (the primitive count is fixed at creation)");
+        for (uint32_t m = 0; m < n_media; ++m) {
+            const RrtMedium &md = wm->media[m], &was = s->h_media[m];
+            const std::string what = fn + "medium " + std::to_string(m);
+            if (md.boundary_kind != was.boundary_kind || md.first != was.first || md.count != was.count)
+                return fail(RRT_E_INVALID, what + ": boundary_kind, first or count differs from the scene's entry (a "
+                                                  "medium's structure is fixed at creation)");
+            if (int rc = check_medium_phase(md, what, s->n_materials, [&](uint32_t k) { return s->mat_kinds[k]; })) return rc;
+            if (md.boundary_kind == RRT_BOUNDARY_SPHERE && !rrt::medium_sphere_is_finite(md))
+                return fail(RRT_E_INVALID, what + ": the sphere row must be finite");
+        }
+        media = wm->media;
+    }
+    if (wm && wm->boundary_quads) {
+        if (wm->n_boundary_quads != n_bquads)
+            return fail(RRT_E_INVALID, fn + "n_boundary_quads is " + std::to_string(wm->n_boundary_quads) + ", the scene's is " +
+                                           std::to_string(n_bquads) + " (the boundaries' structure is fixed at creation)");
+        for (uint32_t k = 0; k < n_bquads; ++k) {
+            const RrtQuad &qd = wm->boundary_quads[k];
+            if (!rrt::quad_is_regular(qd.q, qd.u, qd.v))
+                return fail(RRT_E_INVALID, fn + "boundary quad " + std::to_string(k) + " is degenerate: q, u and v must be "
+                                                "finite and u x v must have a finite, non-zero length");
+        }
+        bquads = wm->boundary_quads;
+    }
+    out.rows[kSpheres] = {spheres, n_spheres, sizeof(RrtSphere), "spheres"};
+    out.rows[kMotion] = {has_motion ? motion : nullptr, n_spheres, 4 * sizeof(float), "motion rows"};
+    out.rows[kQuads] = {quads, n_quads, sizeof(RrtQuad), "quads"};
+    out.rows[kLights] = {lights, n_lights, sizeof(RrtLight), "lights"};
+    out.rows[kMedia] = {media, n_media, sizeof(RrtMedium), "media"};
+    out.rows[kBquads] = {bquads, n_bquads, sizeof(RrtQuad), "boundary quads"};
+    if (tier != Tier::World || !is_update) return RRT_OK;
+    RrtSceneExt e{};
+    e.sphere_motion = has_motion ? motion : nullptr;
+    e.quads = quads ? quads : s->h_quads.data(), e.n_quads = n_quads;
+    e.media = media ? media : s->h_media.data(), e.n_media = n_media;
+    e.boundary_quads = bquads ? bquads : s->h_bquads.data(), e.n_boundary_quads = n_bquads;
+    const uint32_t first_medium = n_spheres + n_quads;
+    for (uint32_t m : unbounded_media(spheres, n_spheres, ExtView(&e))) out.unbounded.push_back(first_medium + m);
+    if (s->base.n_prims - (uint32_t)out.unbounded.size() < 2u)
+        return fail(RRT_E_INVALID, fn + "the new classification leaves fewer than 2 primitives in the tree (" +
+                                       std::to_string(out.unbounded.size()) + " media are unbounded)");
+    size_t u = 0;  // the unbounded media are in ascending order
+    for (uint32_t i = 0; i < s->base.n_prims; ++i) {
+        if (u < out.unbounded.size() && out.unbounded[u] == i) ++u;
+        else out.objs.push_back(i);
+    }
     return RRT_OK;
 }
 
-// The first update or refit of a scene: the device staging of the rows, the node buffer at capacity,
-// the builder's reserve. A failure leaves the scene as it was. own_allocs counts the allocations.
-int ensure_change_buffers(RrtScene *s, const std::string &fn, uint64_t &own_allocs) {
+// What a change needs on the device before its rows are copied. The first change of a scene: the
+// staging of the sphere and motion rows, the node buffer at capacity, the builder's reserve. The
+// first change that brings quads (lights): their staging. The first world change: the staging of the
+// media and boundary-quad rows, filled with the scene's own (a later call may keep either array), and
+// the quads' and lights' whether or not this call brings them, so that no later world change
+// allocates. A failure leaves the scene as it was. own_allocs counts the allocations.
+int ensure_change_buffers(RrtScene *s, const std::string &fn, const SceneChange &c, uint64_t &own_allocs) {
     rrt::KParams &p = s->base;
-    const uint32_t n_spheres = s->n_spheres;
-    if (!s->d_src_spheres) {
+    const bool world = c.tier == Tier::World;
+    for (int k = kSpheres; k <= kLights; ++k) {
+        const ChangeRows &r = c.rows[k];
+        // the spheres always, the motion rows of a book-2 scene, the quads and lights the scene has
+        const bool wanted = k == kSpheres || (k == kMotion ? s->book2 : r.count && (world || r.src));
+        if (!wanted || *row_slot(s, k)) continue;
         ++own_allocs;
-        HIP_TRY(hipMalloc((void **)&s->d_src_spheres, std::max<size_t>(n_spheres, 1) * sizeof(RrtSphere)), "hipMalloc spheres");
+        HIP_TRY(hipMalloc(row_slot(s, k), std::max<size_t>(r.count, 1) * r.elem), std::string("hipMalloc ") + r.noun);
     }
-    if (s->book2 && !s->d_src_motion) {
+    if (world && !s->h_media.empty() && !s->d_src_media) {
         ++own_allocs;
-        HIP_TRY(hipMalloc((void **)&s->d_src_motion, std::max<size_t>(n_spheres, 1) * 4 * sizeof(float)), "hipMalloc motion");
+        if (int rc = upload(&s->d_src_media, s->h_media.data(), s->h_media.size(), "media rows")) return rc;
+    }
+    if (world && !s->h_bquads.empty() && !s->d_src_bquads) {
+        ++own_allocs;
+        if (int rc = upload(&s->d_src_bquads, s->h_bquads.data(), s->h_bquads.size(), "boundary quad rows")) return rc;
     }
     if (!s->nodes_cap) {
         const size_t cap = (size_t)(p.n_prims - 1u) * sizeof(rrt::GNode);  // a binary tree's internal nodes, 80-B form
@@ -2327,174 +2501,60 @@ void sphere32_recheck(RrtScene *s, const RrtSphere *spheres, uint32_t n_spheres)
     s->base.sphere32 = sphere32_flag(in);
 }
 
-// What a geometry entry (rrt_scene_update_geometry, rrt_scene_refit_geometry) changes beyond the
-// spheres; all null for the sphere entries. quads_in32: the new quads' prim_cr rows pass the sphere32
-// range check (scene creation's quads_in_sphere32, from the caller's rows through rrt_quad_form.h).
-struct GeometryChange {
-    const RrtQuad *quads = nullptr;
-    const RrtLight *lights = nullptr;
-    bool quads_in32 = true;
-    // a world entry (rrt_scene_update_world, rrt_scene_refit_world): the media and boundary quads it
-    // brings (null: kept), and for the update the new classification: the unbounded media and the
-    // tree's primitives in their original order
-    bool world = false;
-    const RrtMedium *media = nullptr;
-    const RrtQuad *bquads = nullptr;
-    std::vector<uint32_t> unbounded, objs;
-};
-
-int check_geometry_change(const RrtScene *s, const std::string &fn, const RrtSceneGeometry *g, bool &has_motion,
-                          GeometryChange &out, bool world);
-
-// What the world entries refuse beyond check_geometry_change's list (which they run without its
-// refusal of media and boundary quads), before any device call. update: the classification of the
-// new inputs is formed here (unbounded_media, scene creation's rule) and must leave a tree of 2.
-int check_world_change(const RrtScene *s, const std::string &fn, const RrtSceneGeometry *g, const RrtSceneMedia *wm,
-                       bool update, bool &has_motion, GeometryChange &out) {
-    if (int rc = check_geometry_change(s, fn, g, has_motion, out, true)) return rc;
-    out.world = true;
-    const uint32_t n_media = s->base.n_media, n_bquads = s->n_bquads;
-    if (wm && wm->media) {
-        if (wm->n_media != n_media)
-            return fail(RRT_E_INVALID, fn + "n_media is " + std::to_string(wm->n_media) + ", the scene's is " +
-                                           std::to_string(n_media) + " (the primitive count is fixed at creation)");
-        for (uint32_t m = 0; m < n_media; ++m) {
-            const RrtMedium &md = wm->media[m], &was = s->h_media[m];
-            const std::string what = fn + "medium " + std::to_string(m);
-            if (md.boundary_kind != was.boundary_kind || md.first != was.first || md.count != was.count)
-                return fail(RRT_E_INVALID, what + ": boundary_kind, first or count differs from the scene's entry (a "
-                                                  "medium's structure is fixed at creation)");
-            if (int rc = check_medium_phase(md, what, s->n_materials, [&](uint32_t k) { return s->mat_kinds[k]; })) return rc;
-            if (md.boundary_kind == RRT_BOUNDARY_SPHERE && !rrt::medium_sphere_is_finite(md))
-                return fail(RRT_E_INVALID, what + ": the sphere row must be finite");
-        }
-        out.media = wm->media;
-    }
-    if (wm && wm->boundary_quads) {
-        if (wm->n_boundary_quads != n_bquads)
-            return fail(RRT_E_INVALID, fn + "n_boundary_quads is " + std::to_string(wm->n_boundary_quads) + ", the scene's is " +
-                                           std::to_string(n_bquads) + " (the boundaries' structure is fixed at creation)");
-        for (uint32_t k = 0; k < n_bquads; ++k) {
-            const RrtQuad &qd = wm->boundary_quads[k];
-            if (!rrt::quad_is_regular(qd.q, qd.u, qd.v))
-                return fail(RRT_E_INVALID, fn + "boundary quad " + std::to_string(k) + " is degenerate: q, u and v must be "
-                                                "finite and u x v must have a finite, non-zero length");
-        }
-        out.bquads = wm->boundary_quads;
-    }
-    if (!update) return RRT_OK;
-    RrtSceneExt e{};
-    e.sphere_motion = has_motion ? g->sphere_motion : nullptr;
-    e.quads = out.quads ? out.quads : s->h_quads.data(), e.n_quads = s->base.n_quads;
-    e.media = out.media ? out.media : s->h_media.data(), e.n_media = n_media;
-    e.boundary_quads = out.bquads ? out.bquads : s->h_bquads.data(), e.n_boundary_quads = n_bquads;
-    const uint32_t first_medium = s->n_spheres + s->base.n_quads;
-    for (uint32_t m : unbounded_media(g->spheres, g->n_spheres, ExtView(&e))) out.unbounded.push_back(first_medium + m);
-    if (s->base.n_prims - (uint32_t)out.unbounded.size() < 2u)
-        return fail(RRT_E_INVALID, fn + "the new classification leaves fewer than 2 primitives in the tree (" +
-                                       std::to_string(out.unbounded.size()) + " media are unbounded)");
-    size_t u = 0;  // the unbounded media are in ascending order
-    for (uint32_t i = 0; i < s->base.n_prims; ++i) {
-        if (u < out.unbounded.size() && out.unbounded[u] == i) ++u;
-        else out.objs.push_back(i);
-    }
-    return RRT_OK;
-}
-
-// What the geometry entries refuse before any device call: check_sphere_change's list but for
-// RRT_FLAG_BOOK3, then the quads' and lights' own.
-int check_geometry_change(const RrtScene *s, const std::string &fn, const RrtSceneGeometry *g, bool &has_motion,
-                          GeometryChange &out, bool world = false) {
-    if (!s) return fail(RRT_E_INVALID, fn + "null scene");
-    if (!g) return fail(RRT_E_INVALID, fn + "null geometry");
-    if (int rc = check_sphere_change(s, fn, g->spheres, g->n_spheres, g->sphere_motion, has_motion, true, world)) return rc;
-    if (s->n_bquads && !world)
-        return fail(RRT_E_INVALID, fn + "scenes with boundary quads are not updated (they bound constant media)");
-    const uint32_t n_quads = s->base.n_quads, n_lights = s->base.n_lights;
-    if (g->quads) {
-        if (g->n_quads != n_quads)
-            return fail(RRT_E_INVALID, fn + "n_quads is " + std::to_string(g->n_quads) + ", the scene's is " +
-                                           std::to_string(n_quads) + " (the primitive count is fixed at creation)");
-        for (uint32_t j = 0; j < n_quads; ++j) {
-            const RrtQuad &qd = g->quads[j];
-            const std::string what = fn + "quad " + std::to_string(j);
-            if (qd.material_index >= s->n_materials) return fail(RRT_E_INVALID, what + " material_index out of range");
-            if (s->mat_kinds[qd.material_index] == RRT_MAT_TEXTURED_LAMBERTIAN)
-                return fail(RRT_E_INVALID, what + ": image textures on quads are not supported");
-            if (!rrt::quad_is_regular(qd.q, qd.u, qd.v))
-                return fail(RRT_E_INVALID, what + " is degenerate: q, u and v must be finite and u x v must have a "
-                                                  "finite, non-zero length");
-            out.quads_in32 = out.quads_in32 && row_in_sphere32(qd.q[0], qd.q[1], qd.q[2], -(float)(j + 1));
-        }
-        out.quads = g->quads;
-    }
-    if (s->base.flags & RRT_FLAG_BOOK3) {
-        if (!g->lights)
-            return fail(RRT_E_INVALID, fn + "lights are missing: an RRT_FLAG_BOOK3 scene's light list restates geometry "
-                                            "and is given with it");
-        if (g->n_lights != n_lights)
-            return fail(RRT_E_INVALID, fn + "n_lights is " + std::to_string(g->n_lights) + ", the scene's is " +
-                                           std::to_string(n_lights) + " (the light count is fixed at creation)");
-        for (uint32_t l = 0; l < n_lights; ++l) {
-            const RrtLight &L = g->lights[l];
-            const std::string what = fn + "light " + std::to_string(l);
-            if (L.kind != s->light_kinds[l])
-                return fail(RRT_E_INVALID, what + ": kind " + std::to_string(L.kind) + " differs from the scene's entry (" +
-                                               std::to_string(s->light_kinds[l]) + ")");
-            if (L.kind == RRT_LIGHT_QUAD && !rrt::quad_is_regular(L.a, L.u, L.v))
-                return fail(RRT_E_INVALID, what + " is a degenerate quad: a, u and v must be finite and u x v must have "
-                                                  "a finite, non-zero length");
-        }
-        out.lights = g->lights;
-    } else if (g->lights || g->n_lights) {
-        return fail(RRT_E_INVALID, fn + "lights are given, but the scene was not created with RRT_FLAG_BOOK3");
-    }
-    return RRT_OK;
-}
-
-// The first geometry change that brings quads (lights): the device staging of those rows.
-int ensure_geometry_rows(RrtScene *s, bool quads, bool lights, uint64_t &own_allocs) {
-    if (quads && s->base.n_quads && !s->d_src_quads) {
-        ++own_allocs;
-        HIP_TRY(hipMalloc((void **)&s->d_src_quads, (size_t)s->base.n_quads * sizeof(RrtQuad)), "hipMalloc quads");
-    }
-    if (lights && s->base.n_lights && !s->d_src_lights) {
-        ++own_allocs;
-        HIP_TRY(hipMalloc((void **)&s->d_src_lights, (size_t)s->base.n_lights * sizeof(RrtLight)), "hipMalloc lights");
-    }
-    return RRT_OK;
-}
-int ensure_geometry_buffers(RrtScene *s, const GeometryChange &g, uint64_t &own_allocs) {
-    return ensure_geometry_rows(s, g.quads != nullptr, g.lights != nullptr, own_allocs);
-}
-
-// The first world change of a scene: the device staging of the media and boundary-quad rows, filled
-// with the scene's own (a later call may keep either array), and the quads' and lights' staging
-// whether or not this call brings them, so that no later world change allocates.
-int ensure_world_buffers(RrtScene *s, const GeometryChange &g, uint64_t &own_allocs) {
-    if (!g.world) return RRT_OK;
-    if (int rc = ensure_geometry_rows(s, true, true, own_allocs)) return rc;
-    if (!s->h_media.empty() && !s->d_src_media) {
-        ++own_allocs;
-        if (int rc = upload(&s->d_src_media, s->h_media.data(), s->h_media.size(), "media rows")) return rc;
-    }
-    if (!s->h_bquads.empty() && !s->d_src_bquads) {
-        ++own_allocs;
-        if (int rc = upload(&s->d_src_bquads, s->h_bquads.data(), s->h_bquads.size(), "boundary quad rows")) return rc;
-    }
-    return RRT_OK;
-}
-
 // After a world change: the rows a later call may keep.
-void keep_world_rows(RrtScene *s, const GeometryChange &g) {
-    if (!g.world || (s->h_media.empty() && s->h_bquads.empty())) return;
-    if (g.quads && s->base.n_quads) s->h_quads.assign(g.quads, g.quads + s->base.n_quads);
-    if (g.media && s->base.n_media) s->h_media.assign(g.media, g.media + s->base.n_media);
-    if (g.bquads && s->n_bquads) s->h_bquads.assign(g.bquads, g.bquads + s->n_bquads);
+void keep_world_rows(RrtScene *s, const SceneChange &c) {
+    if (c.tier != Tier::World || (s->h_media.empty() && s->h_bquads.empty())) return;
+    const RrtQuad *quads = (const RrtQuad *)c.rows[kQuads].src, *bquads = (const RrtQuad *)c.rows[kBquads].src;
+    const RrtMedium *media = (const RrtMedium *)c.rows[kMedia].src;
+    if (c.n(kQuads)) s->h_quads.assign(quads, quads + c.n(kQuads));
+    if (c.n(kMedia)) s->h_media.assign(media, media + c.n(kMedia));
+    if (c.n(kBquads)) s->h_bquads.assign(bquads, bquads + c.n(kBquads));
 }
 
-int32_t update_scene(RrtScene *s, const std::string &fn, const RrtSphere *spheres, uint32_t n_spheres, const float *motion,
-                     bool has_motion, const GeometryChange &g, void *stream) {
+// A failure after a change's allocations leaves the scene invalid.
+static int broke(RrtScene *s, const std::string &fn, int code, const std::string &msg) {
+    s->failed_update = fn + msg;
+    return fail(code, fn + msg);
+}
+
+// The boxes of what changed, into the builder's, on `st`.
+static int form_boxes(RrtScene *s, const std::string &fn, const SceneChange &c, hipStream_t st) {
+    const uint32_t n_spheres = s->n_spheres;
+    auto *boxes = s->builder->device_boxes();
+    if (rrt::launch_sphere_boxes(c.n(kSpheres), s->d_src_spheres, c.has_motion ? s->d_src_motion : nullptr, boxes, st) != hipSuccess)
+        return broke(s, fn, RRT_E_HIP, "the sphere-box launch failed");
+    if (rrt::launch_quad_boxes(c.n(kQuads), s->d_src_quads, boxes + n_spheres, st) != hipSuccess)
+        return broke(s, fn, RRT_E_HIP, "the quad-box launch failed");
+    if (rrt::launch_medium_boxes(c.n_medium_boxes(), s->d_src_media, s->d_src_bquads, s->n_bquads,
+                                 boxes + n_spheres + s->base.n_quads, st) != hipSuccess)
+        return broke(s, fn, RRT_E_HIP, "the medium-box launch failed");
+    return RRT_OK;
+}
+
+// Once the tree stands: the records of what changed, on `st`, each launch into its own part of the
+// scene (the quads' records d_quads[0, n_quads) with their rows and material indices; the lights with
+// their GQuads behind the boundary quads'; d_media; the boundary quads' records d_quads + n_quads),
+// then the leaf tables, which read the rows. Then, on the host, the sphere32 range check and the rows
+// a later world change may keep.
+static int form_records(RrtScene *s, const std::string &fn, const SceneChange &c, hipStream_t st) {
+    const uint32_t n_quads = s->base.n_quads;
+    if (rrt::launch_quad_records(c.n(kQuads), s->d_src_quads, s->d_quads, s->d_quads64, s->d_quad_rows, s->d_quad_mat, st) != hipSuccess)
+        return broke(s, fn, RRT_E_HIP, "the quad-record launch failed");
+    if (rrt::launch_lights(c.n(kLights), s->d_src_lights, s->d_light_quad, s->d_lights, s->d_quads, st) != hipSuccess)
+        return broke(s, fn, RRT_E_HIP, "the light launch failed");
+    if (rrt::launch_medium_records(c.n(kMedia), s->d_src_media, n_quads, s->d_media, st) != hipSuccess)
+        return broke(s, fn, RRT_E_HIP, "the medium-record launch failed");
+    if (rrt::launch_bquad_records(c.n(kBquads), s->d_src_bquads, s->d_quads ? s->d_quads + n_quads : nullptr, st) != hipSuccess)
+        return broke(s, fn, RRT_E_HIP, "the boundary-quad launch failed");
+    if (rrt::launch_leaf_tables(leaf_tables_of(s, c.has_motion ? s->d_src_motion : nullptr), st) != hipSuccess)
+        return broke(s, fn, RRT_E_HIP, "the leaf-table launch failed");
+    if (s->f64 && c.rows[kQuads].src) s->quads_in_sphere32 = c.quads_in32;  // the quads' part, from the caller's rows
+    if (s->f64) sphere32_recheck(s, (const RrtSphere *)c.rows[kSpheres].src, c.n(kSpheres));
+    keep_world_rows(s, c);
+    return RRT_OK;
+}
+
+int32_t update_scene(RrtScene *s, const std::string &fn, const SceneChange &c, void *stream) {
     // ---- device work, on the default stream after `stream` (and a refit still in flight) has
     // drained. The first update's allocations fail without touching the scene; a failure after them
     // leaves it invalid (broke).
@@ -2505,75 +2565,37 @@ int32_t update_scene(RrtScene *s, const std::string &fn, const RrtSphere *sphere
     const uint32_t n_prims = p.n_prims;
     const uint64_t allocs_before = s->builder->allocations();
     uint64_t own_allocs = 0;
-    if (int rc = ensure_change_buffers(s, fn, own_allocs)) return rc;
-    if (int rc = ensure_geometry_buffers(s, g, own_allocs)) return rc;
-    if (int rc = ensure_world_buffers(s, g, own_allocs)) return rc;
-    auto broke = [&](int code, const std::string &msg) {
-        s->failed_update = fn + msg;
-        return fail(code, fn + msg);
-    };
-    // a world change: the rows it brings, then the boxes of all media (a quad boundary's box needs both)
-    const uint32_t n_media = g.media ? p.n_media : 0u, n_bquads = g.bquads ? s->n_bquads : 0u;
-    const uint32_t n_medium_boxes = (n_media || n_bquads) ? p.n_media : 0u;
-    if (n_media && hipMemcpy(s->d_src_media, g.media, (size_t)n_media * sizeof(RrtMedium), hipMemcpyHostToDevice) != hipSuccess)
-        return broke(RRT_E_HIP, "copying the media failed");
-    if (n_bquads && hipMemcpy(s->d_src_bquads, g.bquads, (size_t)n_bquads * sizeof(RrtQuad), hipMemcpyHostToDevice) != hipSuccess)
-        return broke(RRT_E_HIP, "copying the boundary quads failed");
-    if (n_spheres && hipMemcpy(s->d_src_spheres, spheres, (size_t)n_spheres * sizeof(RrtSphere), hipMemcpyHostToDevice) != hipSuccess)
-        return broke(RRT_E_HIP, "copying the spheres failed");
-    if (has_motion && hipMemcpy(s->d_src_motion, motion, (size_t)n_spheres * 4 * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
-        return broke(RRT_E_HIP, "copying the motion rows failed");
-    const uint32_t n_quads = g.quads ? p.n_quads : 0u, n_lights = g.lights ? p.n_lights : 0u;
-    if (n_quads && hipMemcpy(s->d_src_quads, g.quads, (size_t)n_quads * sizeof(RrtQuad), hipMemcpyHostToDevice) != hipSuccess)
-        return broke(RRT_E_HIP, "copying the quads failed");
-    if (n_lights && hipMemcpy(s->d_src_lights, g.lights, (size_t)n_lights * sizeof(RrtLight), hipMemcpyHostToDevice) != hipSuccess)
-        return broke(RRT_E_HIP, "copying the lights failed");
-    const float *d_motion = has_motion ? s->d_src_motion : nullptr;
-    if (rrt::launch_sphere_boxes(n_spheres, s->d_src_spheres, d_motion, s->builder->device_boxes()) != hipSuccess)
-        return broke(RRT_E_HIP, "the sphere-box launch failed");
-    if (rrt::launch_quad_boxes(n_quads, s->d_src_quads, s->builder->device_boxes() + n_spheres) != hipSuccess)
-        return broke(RRT_E_HIP, "the quad-box launch failed");
-    if (rrt::launch_medium_boxes(n_medium_boxes, s->d_src_media, s->d_src_bquads, s->n_bquads,
-                                 s->builder->device_boxes() + n_spheres + p.n_quads) != hipSuccess)
-        return broke(RRT_E_HIP, "the medium-box launch failed");
+    if (int rc = ensure_change_buffers(s, fn, c, own_allocs)) return rc;
+    for (int k = 0; k < kRowKinds; ++k)
+        if (c.n(k) && hipMemcpy(*row_slot(s, k), c.rows[k].src, c.n(k) * c.rows[k].elem, hipMemcpyHostToDevice) != hipSuccess)
+            return broke(s, fn, RRT_E_HIP, std::string("copying the ") + c.rows[k].noun + " failed");
+    if (int rc = form_boxes(s, fn, c, nullptr)) return rc;
     // the classification the host formed: the tree's primitives to the builder, the unbounded media
     // behind its leaf order
+    const bool world = c.tier == Tier::World;
     BinnedInput cls;
-    cls.unbounded = g.world ? g.unbounded : s->unbounded;
-    if (g.world && s->builder->set_objects(g.objs.data(), (uint32_t)g.objs.size()) != hipSuccess)
-        return broke(RRT_E_HIP, "device BVH: replacing the tree's primitives failed");
+    cls.unbounded = world ? c.unbounded : s->unbounded;
+    if (world && s->builder->set_objects(c.objs.data(), (uint32_t)c.objs.size()) != hipSuccess)
+        return broke(s, fn, RRT_E_HIP, "device BVH: replacing the tree's primitives failed");
     bvhb::Summary sum{};
     uint32_t stride = 0, leaf_param = s->max_leaf, levels = 0;
     if (!s->fast_bvh && s->builder->reserve() != hipSuccess)  // allocates after a switch from the fast builder only
-        return broke(RRT_E_NOMEM, "reserving the builder's workspace failed");
+        return broke(s, fn, RRT_E_NOMEM, "reserving the builder's workspace failed");
     if (int rc = bvh_device_shape(*s->builder, s->fast_bvh, n_prims, s->max_leaf, s->book2, s->f64, sum, stride, leaf_param, levels))
-        return broke(rc, g_err);
+        return broke(s, fn, rc, g_err);
     const FlatBvh fb = flat_of_summary(sum, stride, cls);
-    if (int rc = tree_limits(fb, s->f64)) return broke(rc, g_err);
+    if (int rc = tree_limits(fb, s->f64)) return broke(s, fn, rc, g_err);
     const size_t node_bytes = (size_t)fb.n_nodes * fb.stride;
     if (s->builder->emit_into(stride, s->d_nodes, s->nodes_cap, s->order.data()) != hipSuccess)
-        return broke(RRT_E_HIP, "device BVH: emit failed");
+        return broke(s, fn, RRT_E_HIP, "device BVH: emit failed");
     std::copy(cls.unbounded.begin(), cls.unbounded.end(), s->order.begin() + s->builder->n_tree());
     s->unbounded = cls.unbounded;
-    if (rrt::launch_medium_records(n_media, s->d_src_media, p.n_quads, s->d_media) != hipSuccess)
-        return broke(RRT_E_HIP, "the medium-record launch failed");
-    if (rrt::launch_bquad_records(n_bquads, s->d_src_bquads, s->d_quads ? s->d_quads + p.n_quads : nullptr) != hipSuccess)
-        return broke(RRT_E_HIP, "the boundary-quad launch failed");
-    // the quads' records, rows and material indices, then the lights with their GQuads; the leaf
-    // tables read the rows
-    if (rrt::launch_quad_records(n_quads, s->d_src_quads, s->d_quads, s->d_quads64, s->d_quad_rows, s->d_quad_mat) != hipSuccess)
-        return broke(RRT_E_HIP, "the quad-record launch failed");
-    if (rrt::launch_lights(n_lights, s->d_src_lights, s->d_light_quad, s->d_lights, s->d_quads) != hipSuccess)
-        return broke(RRT_E_HIP, "the light launch failed");
-    if (rrt::launch_leaf_tables(leaf_tables_of(s, d_motion)) != hipSuccess) return broke(RRT_E_HIP, "the leaf-table launch failed");
-    if (s->f64 && g.quads) s->quads_in_sphere32 = g.quads_in32;  // the quads' part, from the caller's rows
-    if (s->f64) sphere32_recheck(s, spheres, n_spheres);
+    if (int rc = form_records(s, fn, c, nullptr)) return rc;
     tree_params(p, fb, node_bytes, s->book2);
-    if (int rc = plan_check(p)) return broke(rc, g_err);
+    if (int rc = plan_check(p)) return broke(s, fn, rc, g_err);
     bvh_info_tree(s->info, fb, node_bytes, leaf_param);
-    if (hipDeviceSynchronize() != hipSuccess) return broke(RRT_E_HIP, "hipDeviceSynchronize failed");
+    if (hipDeviceSynchronize() != hipSuccess) return broke(s, fn, RRT_E_HIP, "hipDeviceSynchronize failed");
     s->failed_update.clear();
-    keep_world_rows(s, g);
     s->n_updates++;
     s->last_update_allocs = own_allocs + (s->builder->allocations() - allocs_before);
     s->last_update_levels = levels;
@@ -2585,17 +2607,17 @@ int32_t update_scene(RrtScene *s, const std::string &fn, const RrtSphere *sphere
 int32_t rrt_scene_update_spheres(RrtScene *scene, const RrtSphere *spheres, uint32_t n_spheres, const float *motion,
                                  void *stream) {
     const std::string fn = "rrt_scene_update_spheres: ";
-    bool has_motion = false;
-    if (int rc = check_sphere_change(scene, fn, spheres, n_spheres, motion, has_motion)) return rc;
-    return update_scene(scene, fn, spheres, n_spheres, motion, has_motion, GeometryChange{}, stream);
+    const RrtSceneGeometry g{spheres, n_spheres, motion, nullptr, 0, nullptr, 0};
+    SceneChange c;
+    if (int rc = check_change(scene, fn, Tier::Spheres, &g, nullptr, true, c)) return rc;
+    return update_scene(scene, fn, c, stream);
 }
 
 int32_t rrt_scene_update_geometry(RrtScene *scene, const RrtSceneGeometry *geometry, void *stream) {
     const std::string fn = "rrt_scene_update_geometry: ";
-    bool has_motion = false;
-    GeometryChange g;
-    if (int rc = check_geometry_change(scene, fn, geometry, has_motion, g)) return rc;
-    return update_scene(scene, fn, geometry->spheres, geometry->n_spheres, geometry->sphere_motion, has_motion, g, stream);
+    SceneChange c;
+    if (int rc = check_change(scene, fn, Tier::Geometry, geometry, nullptr, true, c)) return rc;
+    return update_scene(scene, fn, c, stream);
 }
 
 // The build twins' common body (lbvh: rrt_bvh_lbvh.h's builder, which takes no node_cost).
@@ -2604,38 +2626,13 @@ static int32_t build_bvh_twin(bool lbvh, const RrtSphere *spheres, uint32_t n_sp
                               uint32_t *prim_order_out, RrtBvhInfo *info) {
     if (n_spheres && !spheres) return fail(RRT_E_INVALID, "null spheres");
     const ExtView ex(ext);
-    for (uint32_t m = 0; m < ex.n_media; ++m)
-        if (ex.media[m].boundary_kind == RRT_BOUNDARY_QUADS &&
-            (ex.media[m].count == 0 || (uint64_t)ex.media[m].first + ex.media[m].count > ex.n_bquads))
-            return fail(RRT_E_INVALID, "medium " + std::to_string(m) + ": boundary quad range out of bounds");
-    if (max_leaf == 0 || max_leaf > rrt::kMaxLeafPrims || (node_stride != 80u && node_stride != 32u) || !(node_cost == node_cost))
-        return fail(RRT_E_INVALID, "max_leaf must be 1..7, node_stride 80 or 32");
-    if ((uint64_t)n_spheres + ex.n_quads + ex.n_media >= (1u << 24)) return fail(RRT_E_INVALID, ">= 2^24 primitives");
+    if (int rc = check_boundary_ranges(ex, "")) return rc;
+    if (int rc = check_twin_shape(max_leaf, node_cost, node_stride, (uint64_t)n_spheres + ex.n_quads + ex.n_media)) return rc;
     const BinnedInput in = binned_input(spheres, n_spheres, ex);
     std::vector<uint32_t> order;
     const FlatBvh fb = flatten_binned(lbvh ? build_lbvh_host(in, max_leaf) : build_binned_host(in, max_leaf, node_cost), node_stride, in, order);
-    if (info) {
-        const bool book2 = ex.motion || ex.n_quads || ex.n_media;
-        *info = RrtBvhInfo{};
-        info->n_nodes = fb.n_nodes;
-        info->n_leaves = fb.n_leaves;
-        info->max_depth = fb.max_depth;
-        info->max_leaf_size = fb.max_leaf;
-        info->node_bytes = fb.bytes.size();
-        info->node_stride = fb.stride;
-        info->prim_bytes = (uint64_t)order.size() * (rrt::kPrimBytes + (book2 ? rrt::kMotionBytes : 0)) +
-                           ((uint64_t)ex.n_quads + ex.n_bquads) * sizeof(rrt::GQuad) +
-                           (uint64_t)ex.n_media * sizeof(rrt::GMedium);
-        info->width = 2;
-        info->max_leaf_param = max_leaf;
-        info->n_unbounded = fb.n_unbounded;
-    }
-    if (nodes_cap == 0) return RRT_OK;
-    if (!nodes_out || nodes_cap < fb.bytes.size() || (order.size() && !prim_order_out))
-        return fail(RRT_E_INVALID, "nodes buffer too small (need " + std::to_string(fb.bytes.size()) + " bytes)");
-    std::memcpy(nodes_out, fb.bytes.data(), fb.bytes.size());
-    if (order.size()) std::memcpy(prim_order_out, order.data(), order.size() * sizeof(uint32_t));
-    return RRT_OK;
+    fill_bvh_info(info, fb, order.size(), ex, max_leaf);
+    return copy_tree_out(fb, order, nodes_out, nodes_cap, prim_order_out);
 }
 
 int32_t rrt_build_bvh_binned(const RrtSphere *spheres, uint32_t n_spheres, const RrtSceneExt *ext, uint32_t max_leaf,
@@ -2657,8 +2654,7 @@ int32_t rrt_build_bvh_lbvh(const RrtSphere *spheres, uint32_t n_spheres, const R
 // A geometry refit stages the quad and light rows behind the spheres' and motion's; its staging
 // buffer is sized for all four at once, whichever of them the call brings. A world refit stages the
 // media and the boundary quads behind those, its buffer sized for all six.
-static int32_t refit_scene(RrtScene *s, const std::string &fn, const RrtSphere *spheres, uint32_t n_spheres, const float *motion,
-                           bool has_motion, const GeometryChange &g, bool geometry, void *stream) {
+static int32_t refit_scene(RrtScene *s, const std::string &fn, const SceneChange &c, void *stream) {
     if (!s->failed_update.empty())
         return fail(RRT_E_INVALID, fn + "the scene is invalid since a change of it failed (" + s->failed_update +
                                        "); only an update that succeeds makes it valid again");
@@ -2669,25 +2665,13 @@ static int32_t refit_scene(RrtScene *s, const std::string &fn, const RrtSphere *
     hipStream_t st = (hipStream_t)stream;
     const uint64_t allocs_before = s->builder->allocations();
     uint64_t own_allocs = 0;
-    const size_t sphere_bytes = (size_t)n_spheres * sizeof(RrtSphere), motion_bytes = (size_t)n_spheres * 4 * sizeof(float);
-    if (!s->d_src_spheres || !s->nodes_cap || (s->book2 && !s->d_src_motion)) {
-        // the first change of this scene replaces its node array: what the stream still renders must be done
-        HIP_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
-        if (int rc = ensure_change_buffers(s, fn, own_allocs)) return rc;
-    }
-    if (int rc = ensure_geometry_buffers(s, g, own_allocs)) return rc;
-    // the first world change: blocking copies of the scene's own rows, which no launch in flight reads
-    if (int rc = ensure_world_buffers(s, g, own_allocs)) return rc;
-    const uint32_t n_quads = g.quads ? s->base.n_quads : 0u, n_lights = g.lights ? s->base.n_lights : 0u;
-    const size_t quad_bytes = (size_t)n_quads * sizeof(RrtQuad), light_bytes = (size_t)n_lights * sizeof(RrtLight);
-    const size_t quads_at = sphere_bytes + motion_bytes, lights_at = quads_at + (size_t)s->base.n_quads * sizeof(RrtQuad);
-    const uint32_t n_media = g.media ? s->base.n_media : 0u, n_bquads = g.bquads ? s->n_bquads : 0u;
-    const uint32_t n_medium_boxes = (n_media || n_bquads) ? s->base.n_media : 0u;
-    const size_t media_bytes = (size_t)n_media * sizeof(RrtMedium), bquad_bytes = (size_t)n_bquads * sizeof(RrtQuad);
-    const size_t media_at = lights_at + (size_t)s->base.n_lights * sizeof(RrtLight);
-    const size_t bquads_at = media_at + (size_t)s->base.n_media * sizeof(RrtMedium);
-    const size_t stage_need = std::max<size_t>(
-        g.world ? bquads_at + (size_t)s->n_bquads * sizeof(RrtQuad) : geometry ? media_at : sphere_bytes + motion_bytes, 16);
+    // the first change of this scene replaces its node array: what the stream still renders must be
+    // done. The first world change: blocking copies of the scene's own rows, which no launch in flight reads
+    if (!s->nodes_cap) HIP_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
+    if (int rc = ensure_change_buffers(s, fn, c, own_allocs)) return rc;
+    size_t stage_need = 0;  // every array of the tier at once, whichever of them the call brings
+    for (int k = 0; k < c.n_staged(); ++k) stage_need += c.rows[k].count * c.rows[k].elem;
+    stage_need = std::max<size_t>(stage_need, 16);
     if (s->stage_cap < stage_need) {  // the first refit, or the first geometry refit after sphere refits
         if (s->h_stage) {
             if (s->n_refits) HIP_TRY(hipEventSynchronize(s->ev_staged), "hipEventSynchronize");
@@ -2702,58 +2686,29 @@ static int32_t refit_scene(RrtScene *s, const std::string &fn, const RrtSphere *
     if (!s->ev_staged) HIP_TRY(hipEventCreateWithFlags(&s->ev_staged, hipEventDisableTiming), "hipEventCreate");
     if (!s->ev_refit_done) HIP_TRY(hipEventCreateWithFlags(&s->ev_refit_done, hipEventDisableTiming), "hipEventCreate");
     if (s->builder->reserve_refit() != hipSuccess) return fail(RRT_E_NOMEM, fn + "reserving the refit's workspace failed");
-    auto broke = [&](int code, const std::string &msg) {
-        s->failed_update = fn + msg;
-        return fail(code, fn + msg);
-    };
-    if (s->n_refits && hipEventSynchronize(s->ev_staged) != hipSuccess) return broke(RRT_E_HIP, "waiting for the staging buffer failed");
-    if (sphere_bytes) std::memcpy(s->h_stage, spheres, sphere_bytes);
-    if (has_motion) std::memcpy(s->h_stage + sphere_bytes, motion, motion_bytes);
-    if (sphere_bytes && hipMemcpyAsync(s->d_src_spheres, s->h_stage, sphere_bytes, hipMemcpyHostToDevice, st) != hipSuccess)
-        return broke(RRT_E_HIP, "copying the spheres failed");
-    if (has_motion && hipMemcpyAsync(s->d_src_motion, s->h_stage + sphere_bytes, motion_bytes, hipMemcpyHostToDevice, st) != hipSuccess)
-        return broke(RRT_E_HIP, "copying the motion rows failed");
-    if (quad_bytes) std::memcpy(s->h_stage + quads_at, g.quads, quad_bytes);
-    if (light_bytes) std::memcpy(s->h_stage + lights_at, g.lights, light_bytes);
-    if (quad_bytes && hipMemcpyAsync(s->d_src_quads, s->h_stage + quads_at, quad_bytes, hipMemcpyHostToDevice, st) != hipSuccess)
-        return broke(RRT_E_HIP, "copying the quads failed");
-    if (light_bytes && hipMemcpyAsync(s->d_src_lights, s->h_stage + lights_at, light_bytes, hipMemcpyHostToDevice, st) != hipSuccess)
-        return broke(RRT_E_HIP, "copying the lights failed");
-    if (media_bytes) std::memcpy(s->h_stage + media_at, g.media, media_bytes);
-    if (bquad_bytes) std::memcpy(s->h_stage + bquads_at, g.bquads, bquad_bytes);
-    if (media_bytes && hipMemcpyAsync(s->d_src_media, s->h_stage + media_at, media_bytes, hipMemcpyHostToDevice, st) != hipSuccess)
-        return broke(RRT_E_HIP, "copying the media failed");
-    if (bquad_bytes && hipMemcpyAsync(s->d_src_bquads, s->h_stage + bquads_at, bquad_bytes, hipMemcpyHostToDevice, st) != hipSuccess)
-        return broke(RRT_E_HIP, "copying the boundary quads failed");
-    if (hipEventRecord(s->ev_staged, st) != hipSuccess) return broke(RRT_E_HIP, "hipEventRecord failed");
-    const float *d_motion = has_motion ? s->d_src_motion : nullptr;
-    if (rrt::launch_sphere_boxes(n_spheres, s->d_src_spheres, d_motion, s->builder->device_boxes(), st) != hipSuccess)
-        return broke(RRT_E_HIP, "the sphere-box launch failed");
-    if (rrt::launch_quad_boxes(n_quads, s->d_src_quads, s->builder->device_boxes() + n_spheres, st) != hipSuccess)
-        return broke(RRT_E_HIP, "the quad-box launch failed");
-    if (rrt::launch_medium_boxes(n_medium_boxes, s->d_src_media, s->d_src_bquads, s->n_bquads,
-                                 s->builder->device_boxes() + n_spheres + s->base.n_quads, st) != hipSuccess)
-        return broke(RRT_E_HIP, "the medium-box launch failed");
-    if (s->builder->refit(st) != hipSuccess) return broke(RRT_E_HIP, "device BVH: refit failed");
+    if (s->n_refits && hipEventSynchronize(s->ev_staged) != hipSuccess)
+        return broke(s, fn, RRT_E_HIP, "waiting for the staging buffer failed");
+    size_t at = 0;  // array k's place in the staging: behind the full arrays before it
+    for (int k = 0; k < kRowKinds; ++k) {
+        const ChangeRows &r = c.rows[k];
+        const size_t bytes = c.n(k) * r.elem;
+        if (bytes) std::memcpy(s->h_stage + at, r.src, bytes);
+        if (bytes && hipMemcpyAsync(*row_slot(s, k), s->h_stage + at, bytes, hipMemcpyHostToDevice, st) != hipSuccess)
+            return broke(s, fn, RRT_E_HIP, std::string("copying the ") + r.noun + " failed");
+        at += r.count * r.elem;
+    }
+    if (hipEventRecord(s->ev_staged, st) != hipSuccess) return broke(s, fn, RRT_E_HIP, "hipEventRecord failed");
+    if (int rc = form_boxes(s, fn, c, st)) return rc;
+    if (s->builder->refit(st) != hipSuccess) return broke(s, fn, RRT_E_HIP, "device BVH: refit failed");
     if (s->builder->emit_refit(s->info.node_stride, s->d_nodes, s->nodes_cap, st) != hipSuccess)
-        return broke(RRT_E_HIP, "device BVH: emit failed");
-    if (rrt::launch_quad_records(n_quads, s->d_src_quads, s->d_quads, s->d_quads64, s->d_quad_rows, s->d_quad_mat, st) != hipSuccess)
-        return broke(RRT_E_HIP, "the quad-record launch failed");
-    if (rrt::launch_lights(n_lights, s->d_src_lights, s->d_light_quad, s->d_lights, s->d_quads, st) != hipSuccess)
-        return broke(RRT_E_HIP, "the light launch failed");
-    if (rrt::launch_medium_records(n_media, s->d_src_media, s->base.n_quads, s->d_media, st) != hipSuccess)
-        return broke(RRT_E_HIP, "the medium-record launch failed");
-    if (rrt::launch_bquad_records(n_bquads, s->d_src_bquads, s->d_quads ? s->d_quads + s->base.n_quads : nullptr, st) != hipSuccess)
-        return broke(RRT_E_HIP, "the boundary-quad launch failed");
-    if (rrt::launch_leaf_tables(leaf_tables_of(s, d_motion), st) != hipSuccess) return broke(RRT_E_HIP, "the leaf-table launch failed");
-    if (hipEventRecord(s->ev_refit_done, st) != hipSuccess) return broke(RRT_E_HIP, "hipEventRecord failed");
-    if (s->f64 && g.quads) s->quads_in_sphere32 = g.quads_in32;  // the quads' part, from the caller's rows
-    if (s->f64) sphere32_recheck(s, spheres, n_spheres);
-    keep_world_rows(s, g);
+        return broke(s, fn, RRT_E_HIP, "device BVH: emit failed");
+    if (int rc = form_records(s, fn, c, st)) return rc;
+    if (hipEventRecord(s->ev_refit_done, st) != hipSuccess) return broke(s, fn, RRT_E_HIP, "hipEventRecord failed");
     s->n_refits++;
     s->last_refit_allocs = own_allocs + (s->builder->allocations() - allocs_before);
-    s->last_refit_launches = (n_spheres ? 1u : 0u) + (n_quads ? 2u : 0u) + (n_lights ? 1u : 0u) + (n_medium_boxes ? 1u : 0u) +
-                             (n_media ? 1u : 0u) + (n_bquads ? 1u : 0u) + s->builder->refit_launches() + 2u;
+    s->last_refit_launches = (c.n(kSpheres) ? 1u : 0u) + (c.n(kQuads) ? 2u : 0u) + (c.n(kLights) ? 1u : 0u) +
+                             (c.n_medium_boxes() ? 1u : 0u) + (c.n(kMedia) ? 1u : 0u) + (c.n(kBquads) ? 1u : 0u) +
+                             s->builder->refit_launches() + 2u;
     s->last_refit_form = s->builder->refit_form();
     return RRT_OK;
 }
@@ -2761,33 +2716,31 @@ static int32_t refit_scene(RrtScene *s, const std::string &fn, const RrtSphere *
 int32_t rrt_scene_refit_spheres(RrtScene *scene, const RrtSphere *spheres, uint32_t n_spheres, const float *motion,
                                 void *stream) {
     const std::string fn = "rrt_scene_refit_spheres: ";
-    bool has_motion = false;
-    if (int rc = check_sphere_change(scene, fn, spheres, n_spheres, motion, has_motion)) return rc;
-    return refit_scene(scene, fn, spheres, n_spheres, motion, has_motion, GeometryChange{}, false, stream);
+    const RrtSceneGeometry g{spheres, n_spheres, motion, nullptr, 0, nullptr, 0};
+    SceneChange c;
+    if (int rc = check_change(scene, fn, Tier::Spheres, &g, nullptr, false, c)) return rc;
+    return refit_scene(scene, fn, c, stream);
 }
 
 int32_t rrt_scene_refit_geometry(RrtScene *scene, const RrtSceneGeometry *geometry, void *stream) {
     const std::string fn = "rrt_scene_refit_geometry: ";
-    bool has_motion = false;
-    GeometryChange g;
-    if (int rc = check_geometry_change(scene, fn, geometry, has_motion, g)) return rc;
-    return refit_scene(scene, fn, geometry->spheres, geometry->n_spheres, geometry->sphere_motion, has_motion, g, true, stream);
+    SceneChange c;
+    if (int rc = check_change(scene, fn, Tier::Geometry, geometry, nullptr, false, c)) return rc;
+    return refit_scene(scene, fn, c, stream);
 }
 
 int32_t rrt_scene_update_world(RrtScene *scene, const RrtSceneGeometry *geometry, const RrtSceneMedia *media, void *stream) {
     const std::string fn = "rrt_scene_update_world: ";
-    bool has_motion = false;
-    GeometryChange g;
-    if (int rc = check_world_change(scene, fn, geometry, media, true, has_motion, g)) return rc;
-    return update_scene(scene, fn, geometry->spheres, geometry->n_spheres, geometry->sphere_motion, has_motion, g, stream);
+    SceneChange c;
+    if (int rc = check_change(scene, fn, Tier::World, geometry, media, true, c)) return rc;
+    return update_scene(scene, fn, c, stream);
 }
 
 int32_t rrt_scene_refit_world(RrtScene *scene, const RrtSceneGeometry *geometry, const RrtSceneMedia *media, void *stream) {
     const std::string fn = "rrt_scene_refit_world: ";
-    bool has_motion = false;
-    GeometryChange g;
-    if (int rc = check_world_change(scene, fn, geometry, media, false, has_motion, g)) return rc;
-    return refit_scene(scene, fn, geometry->spheres, geometry->n_spheres, geometry->sphere_motion, has_motion, g, true, stream);
+    SceneChange c;
+    if (int rc = check_change(scene, fn, Tier::World, geometry, media, false, c)) return rc;
+    return refit_scene(scene, fn, c, stream);
 }
 
 int32_t rrt_scene_set_builder(RrtScene *scene, uint32_t builder) {
@@ -2831,13 +2784,8 @@ static int32_t refit_bvh_binned(bool lbvh, const RrtSphere *built_spheres, uint3
                                 RrtBvhInfo *info, double *sah_out) {
     if (n_spheres && (!built_spheres || !new_spheres)) return fail(RRT_E_INVALID, "null spheres");
     const ExtView ex(built_ext);
-    for (uint32_t m = 0; m < ex.n_media; ++m)
-        if (ex.media[m].boundary_kind == RRT_BOUNDARY_QUADS &&
-            (ex.media[m].count == 0 || (uint64_t)ex.media[m].first + ex.media[m].count > ex.n_bquads))
-            return fail(RRT_E_INVALID, "medium " + std::to_string(m) + ": boundary quad range out of bounds");
-    if (max_leaf == 0 || max_leaf > rrt::kMaxLeafPrims || (node_stride != 80u && node_stride != 32u) || !(node_cost == node_cost))
-        return fail(RRT_E_INVALID, "max_leaf must be 1..7, node_stride 80 or 32");
-    if ((uint64_t)n_spheres + ex.n_quads + ex.n_media >= (1u << 24)) return fail(RRT_E_INVALID, ">= 2^24 primitives");
+    if (int rc = check_boundary_ranges(ex, "")) return rc;
+    if (int rc = check_twin_shape(max_leaf, node_cost, node_stride, (uint64_t)n_spheres + ex.n_quads + ex.n_media)) return rc;
     BinnedInput in = binned_input(built_spheres, n_spheres, ex);
     BinnedTree bt = lbvh ? build_lbvh_host(in, max_leaf) : build_binned_host(in, max_leaf, node_cost);
     for (uint32_t i = 0; i < n_spheres; ++i)
@@ -2862,28 +2810,8 @@ static int32_t refit_bvh_binned(bool lbvh, const RrtSphere *built_spheres, uint3
     }
     std::vector<uint32_t> order;
     const FlatBvh fb = flatten_binned(bt, node_stride, in, order);
-    if (info) {
-        const bool book2 = ex.motion || ex.n_quads || ex.n_media;
-        *info = RrtBvhInfo{};
-        info->n_nodes = fb.n_nodes;
-        info->n_leaves = fb.n_leaves;
-        info->max_depth = fb.max_depth;
-        info->max_leaf_size = fb.max_leaf;
-        info->node_bytes = fb.bytes.size();
-        info->node_stride = fb.stride;
-        info->prim_bytes = (uint64_t)order.size() * (rrt::kPrimBytes + (book2 ? rrt::kMotionBytes : 0)) +
-                           ((uint64_t)ex.n_quads + ex.n_bquads) * sizeof(rrt::GQuad) +
-                           (uint64_t)ex.n_media * sizeof(rrt::GMedium);
-        info->width = 2;
-        info->max_leaf_param = max_leaf;
-        info->n_unbounded = fb.n_unbounded;
-    }
-    if (nodes_cap == 0) return RRT_OK;
-    if (!nodes_out || nodes_cap < fb.bytes.size() || (order.size() && !prim_order_out))
-        return fail(RRT_E_INVALID, "nodes buffer too small (need " + std::to_string(fb.bytes.size()) + " bytes)");
-    std::memcpy(nodes_out, fb.bytes.data(), fb.bytes.size());
-    if (order.size()) std::memcpy(prim_order_out, order.data(), order.size() * sizeof(uint32_t));
-    return RRT_OK;
+    fill_bvh_info(info, fb, order.size(), ex, max_leaf);
+    return copy_tree_out(fb, order, nodes_out, nodes_cap, prim_order_out);
 }
 
 int32_t rrt_refit_bvh_binned_ex(const RrtSphere *built_spheres, uint32_t n_spheres, const RrtSceneExt *built_ext,
@@ -3107,14 +3035,14 @@ extern "C" int32_t rrt_testing_medium_records(const RrtMedium *media, uint32_t n
                                               uint32_t n_boundary_quads, uint32_t n_quads, double *boxes6, void *gmedium) {
     const std::string fn = "rrt_testing_medium_records: ";
     if (n_media && !media) return fail(RRT_E_INVALID, fn + "null media");
+    RrtSceneExt e{};
+    e.media = media, e.n_media = n_media;
+    e.boundary_quads = boundary_quads, e.n_boundary_quads = n_boundary_quads;  // null quads: ExtView counts none
+    if (int rc = check_boundary_ranges(ExtView(&e), fn)) return rc;
     for (uint32_t m = 0; m < n_media; ++m) {
         const RrtMedium &md = media[m];
-        if (md.boundary_kind == RRT_BOUNDARY_QUADS) {
-            if (md.count == 0 || (uint64_t)md.first + md.count > n_boundary_quads || !boundary_quads)
-                return fail(RRT_E_INVALID, fn + "medium " + std::to_string(m) + ": boundary quad range out of bounds");
-        } else if (md.boundary_kind != RRT_BOUNDARY_SPHERE) {
+        if (md.boundary_kind != RRT_BOUNDARY_QUADS && md.boundary_kind != RRT_BOUNDARY_SPHERE)
             return fail(RRT_E_INVALID, fn + "medium " + std::to_string(m) + ": unknown boundary_kind");
-        }
         if (boxes6) {
             const bvhb::Box6 b = rrt::medium_box(md, boundary_quads);
             for (int a = 0; a < 3; ++a) boxes6[6 * (size_t)m + a] = b.mn[a], boxes6[6 * (size_t)m + 3 + a] = b.mx[a];

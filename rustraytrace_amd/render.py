@@ -285,6 +285,26 @@ def tile_row_indices(height: int, tile) -> np.ndarray:
     return out
 
 
+def _two_call(call, n_prims: int, info):
+    """The BVH entries' two calls: call(nodes_p, cap, order_p), which fills `info`, once for the size
+    and once into buffers of that size. Returns (node bytes uint8, leaf order uint32, info dict)."""
+    _lib.check(call(None, 0, None))
+    nodes = np.zeros(info.node_bytes, dtype=np.uint8)
+    order = np.zeros(max(n_prims, 1), dtype=np.uint32)
+    _lib.check(call(_lib.ptr(nodes), nodes.size, _lib.ptr(order)))
+    return nodes, order[:n_prims], info.as_dict()
+
+
+def _sphere_rows(spheres, motion):
+    """(spheres as SPHERE_DTYPE, motion as (n_spheres, 4) float32 or None) of a change's new rows."""
+    sp = np.ascontiguousarray(spheres, dtype=_lib.SPHERE_DTYPE)
+    m = None
+    if motion is not None:
+        m = np.ascontiguousarray(motion, dtype=np.float32)
+        assert m.shape == (len(sp), 4), "motion is (n_spheres, 4) float32"
+    return sp, m
+
+
 def build_bvh(scene: SceneData, width: int = 0, max_leaf: int = 0):
     """The BVH rrt_scene_create builds for `scene` (host only): (node bytes uint8, leaf-order
     permutation uint32, info dict). width/max_leaf 0 = the library defaults."""
@@ -302,11 +322,7 @@ def build_bvh(scene: SceneData, width: int = 0, max_leaf: int = 0):
         return lib.rrt_build_bvh_ex(_lib.ptr(scene.spheres), n, ctypes.byref(ext), width, max_leaf, nodes_p, cap,
                                     order_p, ctypes.byref(info))
 
-    _lib.check(build(None, 0, None))
-    nodes = np.zeros(info.node_bytes, dtype=np.uint8)
-    order = np.zeros(max(n_prims, 1), dtype=np.uint32)
-    _lib.check(build(_lib.ptr(nodes), nodes.size, _lib.ptr(order)))
-    return nodes, order[:n_prims], info.as_dict()
+    return _two_call(build, n_prims, info)
 
 
 def build_bvh_binned(scene: SceneData, max_leaf: int, node_cost: float, node_stride: int):
@@ -324,12 +340,7 @@ def build_bvh_binned(scene: SceneData, max_leaf: int, node_cost: float, node_str
         return lib.rrt_build_bvh_binned(_lib.ptr(scene.spheres), n, extp, int(max_leaf), float(node_cost),
                                         int(node_stride), nodes_p, cap, order_p, ctypes.byref(info))
 
-    _lib.check(build(None, 0, None))
-    nodes = np.zeros(info.node_bytes, dtype=np.uint8)
-    order = np.zeros(max(n_prims, 1), dtype=np.uint32)
-    _lib.check(build(_lib.ptr(nodes), nodes.size, _lib.ptr(order)))
-    del keep
-    return nodes, order[:n_prims], info.as_dict()
+    return _two_call(build, n_prims, info)
 
 
 def build_bvh_lbvh(scene: SceneData, max_leaf: int, node_stride: int):
@@ -347,12 +358,7 @@ def build_bvh_lbvh(scene: SceneData, max_leaf: int, node_stride: int):
         return lib.rrt_build_bvh_lbvh(_lib.ptr(scene.spheres), n, extp, int(max_leaf), int(node_stride), nodes_p, cap,
                                       order_p, ctypes.byref(info))
 
-    _lib.check(build(None, 0, None))
-    nodes = np.zeros(info.node_bytes, dtype=np.uint8)
-    order = np.zeros(max(n_prims, 1), dtype=np.uint32)
-    _lib.check(build(_lib.ptr(nodes), nodes.size, _lib.ptr(order)))
-    del keep
-    return nodes, order[:n_prims], info.as_dict()
+    return _two_call(build, n_prims, info)
 
 
 def refit_bvh_lbvh_world(built_scene: SceneData, new_scene: SceneData, max_leaf: int, node_stride: int):
@@ -376,12 +382,7 @@ def refit_bvh_lbvh_world(built_scene: SceneData, new_scene: SceneData, max_leaf:
                                             _lib.ptr(sp), new_extp, nodes_p, cap, order_p, ctypes.byref(info),
                                             ctypes.byref(sah))
 
-    _lib.check(refit(None, 0, None))
-    nodes = np.zeros(info.node_bytes, dtype=np.uint8)
-    order = np.zeros(max(n_prims, 1), dtype=np.uint32)
-    _lib.check(refit(_lib.ptr(nodes), nodes.size, _lib.ptr(order)))
-    del keep, keep_new
-    return nodes, order[:n_prims], info.as_dict(), float(sah.value)
+    return (*_two_call(refit, n_prims, info), float(sah.value))
 
 
 def refit_bvh_binned(built_scene: SceneData, new_spheres, new_motion, max_leaf: int, node_cost: float, node_stride: int,
@@ -394,12 +395,8 @@ def refit_bvh_binned(built_scene: SceneData, new_spheres, new_motion, max_leaf: 
     info = _lib.RrtBvhInfo()
     sah = ctypes.c_double(0.0)
     n = len(built_scene.spheres)
-    sp = np.ascontiguousarray(new_spheres, dtype=_lib.SPHERE_DTYPE)
+    sp, m = _sphere_rows(new_spheres, new_motion)
     assert len(sp) == n, "a refit keeps the sphere count"
-    m = None
-    if new_motion is not None:
-        m = np.ascontiguousarray(new_motion, dtype=np.float32)
-        assert m.shape == (n, 4), "motion is (n_spheres, 4) float32"
     ext, keep = scene_ext(built_scene)
     n_prims = n + (0 if ext is None else ext.n_quads + ext.n_media)
     extp = ctypes.byref(ext) if ext is not None else None
@@ -413,12 +410,7 @@ def refit_bvh_binned(built_scene: SceneData, new_spheres, new_motion, max_leaf: 
                                            int(node_stride), _lib.ptr(sp), _lib.ptr(m), _lib.ptr(q), nodes_p, cap,
                                            order_p, ctypes.byref(info), ctypes.byref(sah))
 
-    _lib.check(refit(None, 0, None))
-    nodes = np.zeros(info.node_bytes, dtype=np.uint8)
-    order = np.zeros(max(n_prims, 1), dtype=np.uint32)
-    _lib.check(refit(_lib.ptr(nodes), nodes.size, _lib.ptr(order)))
-    del keep
-    return nodes, order[:n_prims], info.as_dict(), float(sah.value)
+    return (*_two_call(refit, n_prims, info), float(sah.value))
 
 
 def refit_bvh_binned_world(built_scene: SceneData, new_scene: SceneData, max_leaf: int, node_cost: float, node_stride: int):
@@ -443,12 +435,7 @@ def refit_bvh_binned_world(built_scene: SceneData, new_scene: SceneData, max_lea
                                               int(node_stride), _lib.ptr(sp), new_extp, nodes_p, cap, order_p,
                                               ctypes.byref(info), ctypes.byref(sah))
 
-    _lib.check(refit(None, 0, None))
-    nodes = np.zeros(info.node_bytes, dtype=np.uint8)
-    order = np.zeros(max(n_prims, 1), dtype=np.uint32)
-    _lib.check(refit(_lib.ptr(nodes), nodes.size, _lib.ptr(order)))
-    del keep, keep_new
-    return nodes, order[:n_prims], info.as_dict(), float(sah.value)
+    return (*_two_call(refit, n_prims, info), float(sah.value))
 
 
 def decode_bvh2(nodes: np.ndarray, stride: int):
@@ -563,37 +550,37 @@ class DeviceScene:
         None = all zero) of a DeviceScene(device_bvh=True), rebuilds the BVH on the device and re-forms
         the per-primitive tables; the scene then equals one freshly created from the new inputs. Waits
         for the stream, returns synchronised."""
-        sp = np.ascontiguousarray(spheres, dtype=_lib.SPHERE_DTYPE)
-        m = None
-        if motion is not None:
-            m = np.ascontiguousarray(motion, dtype=np.float32)
-            assert m.shape == (len(sp), 4), "motion is (n_spheres, 4) float32"
-        _lib.check(self._lib.rrt_scene_update_spheres(self._h, _lib.ptr(sp), len(sp), _lib.ptr(m),
-                                                      ctypes.c_void_p(stream_ptr)))
-        self.scene = dataclasses.replace(self.scene, spheres=sp.copy(), motion=None if m is None else m.copy())
+        self._change("rrt_scene_update_spheres", stream_ptr, spheres, motion)
 
     def refit_spheres(self, spheres, motion=None, stream_ptr: int = 0) -> None:
         """rrt_scene_refit_spheres: replaces the spheres (and motion rows) like update_spheres but keeps
         the tree's topology and leaf order and recomputes only its boxes; everything is enqueued on
         the stream and the call does not wait for the device. tree_cost() tells when to rebuild."""
-        sp = np.ascontiguousarray(spheres, dtype=_lib.SPHERE_DTYPE)
-        m = None
-        if motion is not None:
-            m = np.ascontiguousarray(motion, dtype=np.float32)
-            assert m.shape == (len(sp), 4), "motion is (n_spheres, 4) float32"
-        _lib.check(self._lib.rrt_scene_refit_spheres(self._h, _lib.ptr(sp), len(sp), _lib.ptr(m),
-                                                     ctypes.c_void_p(stream_ptr)))
-        self.scene = dataclasses.replace(self.scene, spheres=sp.copy(), motion=None if m is None else m.copy())
+        self._change("rrt_scene_refit_spheres", stream_ptr, spheres, motion)
+
+    def _change(self, entry: str, stream_ptr: int, spheres, motion, quads=None, lights=None, media=None,
+                boundary_quads=None) -> None:
+        """The body of the six update_* and refit_* methods: calls the library's `entry` with the new
+        rows and, once it succeeded, makes them self.scene's."""
+        fn, stream = getattr(self._lib, entry), ctypes.c_void_p(stream_ptr)
+        if entry.endswith("_spheres"):
+            sp, m = _sphere_rows(spheres, motion)
+            _lib.check(fn(self._h, _lib.ptr(sp), len(sp), _lib.ptr(m), stream))
+            self.scene = dataclasses.replace(self.scene, spheres=sp.copy(), motion=None if m is None else m.copy())
+            return
+        g, new = self._geometry(spheres, motion, quads, lights)
+        args = [ctypes.byref(g)]
+        if entry.endswith("_world"):
+            wm, new = self._media(new, media, boundary_quads)
+            args.append(None if wm is None else ctypes.byref(wm))
+        _lib.check(fn(self._h, *args, stream))
+        self.scene = new
 
     def _geometry(self, spheres, motion, quads, lights):
         """(RrtSceneGeometry, the replaced SceneData) of a geometry change; the struct borrows the
         new scene's arrays."""
         sc = self.scene
-        sp = np.ascontiguousarray(sc.spheres if spheres is None else spheres, dtype=_lib.SPHERE_DTYPE)
-        m = None
-        if motion is not None:
-            m = np.ascontiguousarray(motion, dtype=np.float32)
-            assert m.shape == (len(sp), 4), "motion is (n_spheres, 4) float32"
+        sp, m = _sphere_rows(sc.spheres if spheres is None else spheres, motion)
         new = dataclasses.replace(sc, spheres=sp.copy(), motion=None if m is None else m.copy())
         g = _lib.RrtSceneGeometry()
         g.spheres, g.n_spheres = (new.spheres.ctypes.data if len(sp) else None), len(sp)
@@ -614,17 +601,13 @@ class DeviceScene:
         everything derived from the geometry re-formed there; the scene then equals one freshly created
         from the new inputs. spheres=None passes the current spheres; motion=None is all zero. Waits
         for the stream, returns synchronised."""
-        g, new = self._geometry(spheres, motion, quads, lights)
-        _lib.check(self._lib.rrt_scene_update_geometry(self._h, ctypes.byref(g), ctypes.c_void_p(stream_ptr)))
-        self.scene = new
+        self._change("rrt_scene_update_geometry", stream_ptr, spheres, motion, quads, lights)
 
     def refit_geometry(self, spheres=None, motion=None, quads=None, lights=None, stream_ptr: int = 0) -> None:
         """rrt_scene_refit_geometry: the same replacement as update_geometry, but the tree keeps its
         topology and leaf order and only its boxes are recomputed; everything is enqueued on the stream
         and the call does not wait for the device. tree_cost() tells when to rebuild."""
-        g, new = self._geometry(spheres, motion, quads, lights)
-        _lib.check(self._lib.rrt_scene_refit_geometry(self._h, ctypes.byref(g), ctypes.c_void_p(stream_ptr)))
-        self.scene = new
+        self._change("rrt_scene_refit_geometry", stream_ptr, spheres, motion, quads, lights)
 
     def _media(self, new, media, boundary_quads):
         """(RrtSceneMedia or None, the replaced SceneData) of a world change; the struct borrows the
@@ -647,11 +630,7 @@ class DeviceScene:
         decided again from the new inputs, the BVH rebuilt on the device over the rest and everything
         derived re-formed there; the scene then equals one freshly created from the new inputs. Waits
         for the stream, returns synchronised."""
-        g, new = self._geometry(spheres, motion, quads, lights)
-        wm, new = self._media(new, media, boundary_quads)
-        _lib.check(self._lib.rrt_scene_update_world(self._h, ctypes.byref(g), None if wm is None else ctypes.byref(wm),
-                                                    ctypes.c_void_p(stream_ptr)))
-        self.scene = new
+        self._change("rrt_scene_update_world", stream_ptr, spheres, motion, quads, lights, media, boundary_quads)
 
     def refit_world(self, spheres=None, motion=None, quads=None, lights=None, media=None, boundary_quads=None,
                     stream_ptr: int = 0) -> None:
@@ -659,11 +638,7 @@ class DeviceScene:
         its leaf order and the last build's choice of the media tested outside it, and only its boxes
         are recomputed; everything is enqueued on the stream and the call does not wait for the device.
         tree_cost() tells when to rebuild."""
-        g, new = self._geometry(spheres, motion, quads, lights)
-        wm, new = self._media(new, media, boundary_quads)
-        _lib.check(self._lib.rrt_scene_refit_world(self._h, ctypes.byref(g), None if wm is None else ctypes.byref(wm),
-                                                   ctypes.c_void_p(stream_ptr)))
-        self.scene = new
+        self._change("rrt_scene_refit_world", stream_ptr, spheres, motion, quads, lights, media, boundary_quads)
 
     def tree_cost(self) -> dict:
         """rrt_scene_tree_cost: the SAH cost of the tree held now, of the last build's tree, and the

@@ -270,6 +270,41 @@ def test_first_geometry_refit_after_sphere_refits_grows_the_staging_once():
     assert_refitted(got, sc, new, fresh_g(sc, key="mixed"), fresh_g(new, frame=False), False)
 
 
+def test_one_scene_through_all_three_tiers_equals_the_geometry_entries_alone():
+    """Sphere, geometry and world entries on one media-free scene, against a second scene taken through
+    the same inputs by the geometry entries alone: every table and the tree bit for bit, and without
+    media the world tier needs no more staging than the geometry tier has allocated."""
+    sc = G.scene("mixed")
+    tiers, plain = open_scene(sc), open_scene(sc)
+
+    def same():
+        assert_equals_fresh_g(snapshot_g(tiers, frame=False), snapshot_g(plain, frame=False))
+        for t in _lib.SCENE_MEDIA_TABLES:
+            assert tiers.read_table(t).tobytes() == plain.read_table(t).tobytes(), f"table {t} differs"
+        assert tiers.refit_stats()["last_allocations"] == 0
+
+    sp = jittered(sc, 61)
+    tiers.refit_spheres(sp, sc.motion)
+    plain.refit_geometry(spheres=sp, motion=sc.motion)
+    sp, q, _ = G.moved(sc, 62, 0.02)
+    tiers.refit_geometry(spheres=sp, motion=sc.motion, quads=q)
+    plain.refit_geometry(spheres=sp, motion=sc.motion, quads=q)
+    sp, q, _ = G.moved(sc, 63, 0.02)
+    tiers.refit_world(spheres=sp, motion=sc.motion, quads=q, media=None)
+    plain.refit_geometry(spheres=sp, motion=sc.motion, quads=q)
+    same()
+    sp, q, _ = G.moved(sc, 64, 0.3)
+    tiers.update_world(spheres=sp, motion=sc.motion, quads=q)
+    plain.update_geometry(spheres=sp, motion=sc.motion, quads=q)
+    sp = jittered(sc, 65)
+    tiers.refit_spheres(sp, sc.motion)
+    plain.refit_geometry(spheres=sp, motion=sc.motion)
+    same()
+    assert tiers.refit_stats()["refits"] == 4 and tiers.update_stats()["updates"] == 1
+    tiers.close()
+    plain.close()
+
+
 # ---- 3. refusals ------------------------------------------------------------------------------------
 def _geometry_call(entry, **fields):
     """The C entry with an RrtSceneGeometry filled field by field (arrays the caller keeps alive)."""
@@ -304,7 +339,7 @@ def _refusals(entry):
     do = lambda **kw: (lambda ds: getattr(ds, how)(**kw))
     on = dict(device_bvh=True)
     return {
-        # check_sphere_change's list but for RRT_FLAG_BOOK3
+        # check_change's list for the sphere entries but for RRT_FLAG_BOOK3
         "sphere_count": (c2, on, do(spheres=c2.spheres[:-1]), "n_spheres"),
         "null_spheres": (c2, on, _geometry_call(entry, spheres=None), "null spheres"),
         "sphere_material": (c2, on, do(spheres=bad_sphere), "material_index"),
