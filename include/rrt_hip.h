@@ -657,6 +657,53 @@ int32_t rrt_refit_bvh_lbvh_world(const RrtSphere *built_spheres, uint32_t n_sphe
 enum { RRT_BUILDER_BINNED = 0, RRT_BUILDER_LBVH = 1 };
 int32_t rrt_scene_set_builder(RrtScene *scene, uint32_t builder);
 
+/* ---- ray queries on a created scene ---------------------------------------------------- */
+
+/* The render's closest-hit query (world.hit(ray, Interval(0.001, t_max)): hittable_list.rs,
+ * bvh.rs:159-172, camera.rs:187) on the caller's rays, without shading: the kernel runs the node step
+ * and the leaf tests the render runs, on the tree and the primitive tables the render reads.
+ *
+ * One ray: origin o, direction d (any length), the interval's end tmax, and the time at which moving
+ * spheres are met (center + time * motion, rounded as the render rounds it; ignored by a scene
+ * without motion rows). A sphere's root is accepted in the open interval (0.001, tmax), a quad's in
+ * the closed interval [0.001, tmax], each against the running closest hit exactly as the render's leaf
+ * tests accept it: tmax is the closest hit the walk starts from (the render starts from +inf, which
+ * gives the render's own query). A tmax that is NaN or <= 0.001 finds nothing. No primitive is skipped.
+ *
+ * One answer: prim is the hit primitive's index in source order, spheres first, then quads as
+ * n_spheres + j (rrt_build_bvh_ex's order), and t its root; a miss gives prim = RRT_NO_PRIM, t = 0.
+ * RRT_QUERY_CLOSEST: the closest hit; of two primitives at exactly the same t the tree's order decides,
+ * as in the render. RRT_QUERY_ANY: the ray leaves the tree after the first batch of leaf tests that
+ * accepted something, and (t, prim) is that hit: prim != RRT_NO_PRIM exactly when the closest query
+ * finds a hit, but it need not be the closest one. A ray's answer does not depend on the other rays of
+ * the call. */
+typedef struct RrtRay { float o[3]; float tmax; float d[3]; float time; } RrtRay;   /* 32 B */
+typedef struct RrtHit { float t; uint32_t prim; } RrtHit;                           /* 8 B  */
+#define RRT_NO_PRIM 0xffffffffu
+enum { RRT_QUERY_CLOSEST = 0, RRT_QUERY_ANY = 1 };
+
+/* n rays at d_rays (device memory, 16-byte aligned) answered into d_hits (device memory, 8-byte
+ * aligned), enqueued on `stream`: the query sees every update or refit enqueued on that stream before
+ * it, and like a render it is the scene's one piece of work in flight. RrtCounters are left alone.
+ * n = 0 enqueues nothing. The first query of a scene allocates a device copy of the leaf order (blocking);
+ * an rrt_scene_update_* replaces its contents, a refit keeps it, and later queries allocate nothing.
+ * Refused with RRT_E_INVALID before any device call, the message naming the item: a null scene, null
+ * or misaligned pointers with n > 0, an unknown mode, a scene with constant media (volumes with a
+ * stochastic free flight, not surfaces), an RRT_FLAG_F64 scene (it holds the f64 kernel's tables), a
+ * width-4 tree (RRT_BVH_WIDTH=4), a scene left invalid by a failed update. Book-3 scenes without media
+ * are accepted. */
+int32_t rrt_scene_query_async(RrtScene *scene, const RrtRay *d_rays, uint32_t n, uint32_t mode,
+                              RrtHit *d_hits, void *stream);
+/* The same for host arrays, synchronous, through device buffers the scene keeps and grows. */
+int32_t rrt_scene_query(RrtScene *scene, const RrtRay *rays, uint32_t n, uint32_t mode, RrtHit *hits);
+/* width * height records in row-major order (the camera's as rrt_scene_set_camera last left it):
+ * record (x, y) is the closest hit of the path tracer's camera ray with zero jitter and no defocus,
+ * origin = camera.origin, direction = ((pixel00 + du * (float)x) + dv * (float)y) - origin per
+ * component with every operation rounded to f32, tmax = +inf, the given time. The same kernel as
+ * the ray-array entries, the ray formed in the kernel; 64 consecutive lanes take an 8 x 8 pixel tile.
+ * Refusals as above. */
+int32_t rrt_scene_primary_hits_async(RrtScene *scene, float time, RrtHit *d_hits, void *stream);
+
 /* ---- host-side callers of the boundary ------------------------------------------------ */
 
 /* == gpu::build_in_one_weekend_scene (gpu/mod.rs:124-301): RTOW final scene from

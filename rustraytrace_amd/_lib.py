@@ -121,7 +121,17 @@ EXPORTED_SYMBOLS = (
     "rrt_scene_set_builder",
     "rrt_testing_scene_build_stats",
     "rrt_testing_lbvh_form",
+    "rrt_scene_query_async",
+    "rrt_scene_query",
+    "rrt_scene_primary_hits_async",
 )
+
+# == RrtRay / RrtHit (include/rrt_hip.h): a query ray and its answer
+RAY_DTYPE = np.dtype([("o", "<f4", 3), ("tmax", "<f4"), ("d", "<f4", 3), ("time", "<f4")])
+HIT_DTYPE = np.dtype([("t", "<f4"), ("prim", "<u4")])
+assert RAY_DTYPE.itemsize == 32 and HIT_DTYPE.itemsize == 8
+NO_PRIM = 0xFFFFFFFF  # RRT_NO_PRIM
+QUERY_MODES = {"closest": 0, "any": 1}  # RRT_QUERY_CLOSEST, RRT_QUERY_ANY
 
 # == RrtSceneTable (include/rrt_hip.h, test support): table -> (code, row dtype)
 SCENE_TABLES = {
@@ -532,6 +542,9 @@ def load() -> ctypes.CDLL:
         "rrt_testing_scene_build_stats": (c_int32, [P, P]),
         "rrt_testing_lbvh_form": (c_int32, [c_int32]),
         "rrt_testing_medium_records": (c_int32, [P, c_uint32, P, c_uint32, c_uint32, P, P]),
+        "rrt_scene_query_async": (c_int32, [P, P, c_uint32, c_uint32, P, P]),
+        "rrt_scene_query": (c_int32, [P, P, c_uint32, c_uint32, P]),
+        "rrt_scene_primary_hits_async": (c_int32, [P, c_float, P, P]),
     }
     experiment = "RRT_LIB_PATH" in os.environ  # A/B of older builds: tolerate symbols they lack
     for name, (res, args) in sig.items():

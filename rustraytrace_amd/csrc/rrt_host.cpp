@@ -1243,6 +1243,12 @@ struct RrtScene {
     std::vector<uint32_t> unbounded;
     RrtMedium *d_src_media = nullptr;
     RrtQuad *d_src_bquads = nullptr;
+    // rrt_scene_query_*: the leaf order on the device (first query on; an update rewrites it) and the
+    // host-array entry's device buffers, grown to the largest call
+    uint32_t *d_query_order = nullptr;
+    RrtRay *d_query_rays = nullptr;
+    RrtHit *d_query_hits = nullptr;
+    size_t query_cap = 0;  // rays and hits
 };
 
 namespace {
@@ -1282,6 +1288,9 @@ void free_scene(RrtScene *s) {
     (void)hipFree(s->d_src_lights);
     (void)hipFree(s->d_src_media);
     (void)hipFree(s->d_src_bquads);
+    (void)hipFree(s->d_query_order);
+    (void)hipFree(s->d_query_rays);
+    (void)hipFree(s->d_query_hits);
     if (s->h_stage) (void)hipHostFree(s->h_stage);
     if (s->ev_staged) (void)hipEventDestroy(s->ev_staged);
     if (s->ev_refit_done) (void)hipEventDestroy(s->ev_refit_done);
@@ -2590,6 +2599,10 @@ int32_t update_scene(RrtScene *s, const std::string &fn, const SceneChange &c, v
         return broke(s, fn, RRT_E_HIP, "device BVH: emit failed");
     std::copy(cls.unbounded.begin(), cls.unbounded.end(), s->order.begin() + s->builder->n_tree());
     s->unbounded = cls.unbounded;
+    // the queries' copy of the leaf order (rrt_scene_query_async), once a query has made one
+    if (s->d_query_order &&
+        hipMemcpy(s->d_query_order, s->order.data(), s->order.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess)
+        return broke(s, fn, RRT_E_HIP, "copying the leaf order for the queries failed");
     if (int rc = form_records(s, fn, c, nullptr)) return rc;
     tree_params(p, fb, node_bytes, s->book2);
     if (int rc = plan_check(p)) return broke(s, fn, rc, g_err);
@@ -2943,6 +2956,87 @@ double render_progress(RrtScene *scene, hipStream_t side, uint32_t *host_heads, 
     return std::min(0.999, (pass + in_pass) / passes);
 }
 }  // namespace
+
+// ---- ray queries ------------------------------------------------------------------------
+namespace {
+// The refusals of the three query entries, before any device call; d_rays may be null for the
+// primary-hit entry (primary), n is then the camera's pixel count.
+int check_query(const RrtScene *s, const std::string &fn, const void *d_rays, bool primary, uint64_t n, uint32_t mode,
+                const void *d_hits) {
+    if (!s) return fail(RRT_E_INVALID, fn + "null scene");
+    if (mode != RRT_QUERY_CLOSEST && mode != RRT_QUERY_ANY)
+        return fail(RRT_E_INVALID, fn + "unknown mode " + std::to_string(mode) + " (RRT_QUERY_CLOSEST or RRT_QUERY_ANY)");
+    if (n && !primary && !d_rays) return fail(RRT_E_INVALID, fn + "null rays with n > 0");
+    if (n && !d_hits) return fail(RRT_E_INVALID, fn + "null hits with n > 0");
+    if (n && !primary && ((uintptr_t)d_rays & 15u)) return fail(RRT_E_INVALID, fn + "rays must be 16-byte aligned");
+    if (n && ((uintptr_t)d_hits & 7u)) return fail(RRT_E_INVALID, fn + "hits must be 8-byte aligned");
+    if (n > 0xffffffffull) return fail(RRT_E_INVALID, fn + "more than 2^32 - 1 rays");
+    if (s->f64) return fail(RRT_E_INVALID, fn + "an RRT_FLAG_F64 scene holds the f64 kernel's tables; queries need an f32 scene");
+    if (s->base.n_media)
+        return fail(RRT_E_INVALID, fn + "the scene has constant media, which are volumes with a stochastic free flight, "
+                                        "not surfaces; queries do not see through them");
+    if (s->base.bvh_width != 2u) return fail(RRT_E_INVALID, fn + "a width-4 tree (RRT_BVH_WIDTH=4); queries walk the binary tree");
+    if (!s->failed_update.empty())
+        return fail(RRT_E_INVALID, fn + "the scene is invalid since a change of it failed (" + s->failed_update +
+                                       "); a later update that succeeds makes it valid again");
+    return RRT_OK;
+}
+
+// Checked arguments: the first query's order table, then the launch on `stream`.
+int query_launch(RrtScene *s, const RrtRay *d_rays, uint32_t n, uint32_t mode, float time, RrtHit *d_hits, void *stream) {
+    HIP_TRY(hipSetDevice(s->device), "hipSetDevice");
+    if (!s->d_query_order) {
+        if (int rc = upload(&s->d_query_order, s->order.data(), s->order.size(), "query leaf order")) {
+            (void)hipFree(s->d_query_order);
+            s->d_query_order = nullptr;
+            return rc;
+        }
+    }
+    rrt::QParams q{};
+    q.order = s->d_query_order;
+    q.rays = reinterpret_cast<const float4 *>(d_rays);
+    q.hits = reinterpret_cast<uint2 *>(d_hits);
+    q.n = n;
+    q.mode = mode;
+    q.time = time;
+    HIP_TRY(rrt::launch_query(s->base, q, (hipStream_t)stream), "query kernel launch");
+    return RRT_OK;
+}
+}  // namespace
+
+int32_t rrt_scene_query_async(RrtScene *scene, const RrtRay *d_rays, uint32_t n, uint32_t mode, RrtHit *d_hits, void *stream) {
+    if (int rc = check_query(scene, "rrt_scene_query_async: ", d_rays, false, n, mode, d_hits)) return rc;
+    if (n == 0) return RRT_OK;
+    return query_launch(scene, d_rays, n, mode, 0.0f, d_hits, stream);
+}
+
+int32_t rrt_scene_query(RrtScene *scene, const RrtRay *rays, uint32_t n, uint32_t mode, RrtHit *hits) {
+    // (host arrays: no alignment beyond the records' own)
+    if (int rc = check_query(scene, "rrt_scene_query: ", nullptr, true, 0, mode, nullptr)) return rc;
+    if (n && !rays) return fail(RRT_E_INVALID, "rrt_scene_query: null rays with n > 0");
+    if (n && !hits) return fail(RRT_E_INVALID, "rrt_scene_query: null hits with n > 0");
+    if (n == 0) return RRT_OK;
+    HIP_TRY(hipSetDevice(scene->device), "hipSetDevice");
+    if (scene->query_cap < n) {
+        (void)hipFree(scene->d_query_rays);
+        (void)hipFree(scene->d_query_hits);
+        scene->d_query_rays = nullptr, scene->d_query_hits = nullptr, scene->query_cap = 0;
+        HIP_TRY(hipMalloc((void **)&scene->d_query_rays, (size_t)n * sizeof(RrtRay)), "hipMalloc query rays");
+        HIP_TRY(hipMalloc((void **)&scene->d_query_hits, (size_t)n * sizeof(RrtHit)), "hipMalloc query hits");
+        scene->query_cap = n;
+    }
+    HIP_TRY(hipMemcpy(scene->d_query_rays, rays, (size_t)n * sizeof(RrtRay), hipMemcpyHostToDevice), "copy rays");
+    if (int rc = query_launch(scene, scene->d_query_rays, n, mode, 0.0f, scene->d_query_hits, nullptr)) return rc;
+    HIP_TRY(hipMemcpy(hits, scene->d_query_hits, (size_t)n * sizeof(RrtHit), hipMemcpyDeviceToHost), "copy hits");
+    return RRT_OK;
+}
+
+int32_t rrt_scene_primary_hits_async(RrtScene *scene, float time, RrtHit *d_hits, void *stream) {
+    const uint64_t n = scene ? (uint64_t)scene->base.width * scene->base.height : 0u;
+    if (int rc = check_query(scene, "rrt_scene_primary_hits_async: ", nullptr, true, n, RRT_QUERY_CLOSEST, d_hits)) return rc;
+    if (n == 0) return RRT_OK;
+    return query_launch(scene, nullptr, (uint32_t)n, RRT_QUERY_CLOSEST, time, d_hits, stream);
+}
 
 int32_t rrt_scene_read_counters(RrtScene *scene, RrtCounters *out) {
     if (!scene || !out) return fail(RRT_E_INVALID, "null scene or out");

@@ -370,6 +370,29 @@ LaunchPlan plan_launch_f64(const KParams &p);  // rrt_books64.hip; plan_launch f
 // still fits the default 64 KiB.
 bool perlin_fits_lds(KParams p);
 
+// The ray-query kernel's parameters (rrt_scene_query_async, rrt_scene_primary_hits_async): the
+// scene's tree and geometry tables as the render reads them, the leaf order, and the rays.
+struct QParams {
+    const void *nodes;          // GNode[] (staged in LDS) or GNodeH[]
+    const float4 *prim_cr;      // leaf order
+    const float4 *prim_motion;  // leaf order; null = a book-1 scene (r * r records)
+    const GQuad *quads;
+    const uint32_t *order;      // leaf position -> primitive in source order (spheres, then quads)
+    const float4 *rays;         // RrtRay as (o.xyz, tmax), (d.xyz, time); null = the camera's primary rays
+    uint2 *hits;                // RrtHit as (t bits, prim)
+    uint32_t n;                 // rays, or width * height
+    uint32_t n_groups;          // 64-ray groups: ceil(n / 64), or the camera's 8 x 8 pixel tiles
+    uint32_t mode;              // RRT_QUERY_CLOSEST / RRT_QUERY_ANY
+    uint32_t n_nodes, n_prims, n_quads;
+    uint32_t stack_depth, leaf_frac;
+    uint32_t width, height, tiles_x;  // primary rays
+    float time;                       // primary rays
+    float p00[3], du[3], dv[3], center[3];
+};
+// The query on `stream`, in the instantiation the scene's render plan names (tree placement, stack
+// type) for the scene's geometry form; p.n_groups, tiles_x are the launcher's. n_cus: grid sizing.
+hipError_t launch_query(const KParams &scene, QParams q, hipStream_t stream);
+
 // Launch wrappers implemented in rrt_kernel.hip.
 hipError_t launch_render(const KParams &p, hipStream_t stream);
 hipError_t launch_render_counting(const KParams &p, hipStream_t stream);

@@ -1925,6 +1925,133 @@ __global__ __launch_bounds__(kBlk, kWaves) void rrt_render(KParams P) {
     render_body<kLds, kCount, StackT, kWide, kBook2, kBlk, kNoise>(P);
 }
 
+// ---- ray queries (rrt_scene_query_async, rrt_scene_primary_hits_async; include/rrt_hip.h) -----
+// The render's closest-hit query on the caller's rays: one ray per lane through render_body's BVH2
+// loop — trav_node, the step / pm / nm ballots, the postponed leaf batches through trav_leaves —
+// with no refill and no shading, so the loop runs until no lane of the wave is in the tree
+// (min_active = 0). A wave takes 64 consecutive rays at a time (a caller's coherent order stays
+// coherent), or the 8 x 8 pixel tile of a primary-hit launch, whose rays it forms by camera_ray's
+// expression at zero jitter; the waves of the persistent grid stride over these groups. A staged
+// scene (kLds) is staged as render_body stages it, without the materials and the Perlin tables:
+// [nodes][primitives][motion][stack], the node array at the block's LDS offset 0 (lds_node_link).
+// kGeom is the Prims<> form: kBook1Untextured (r * r records, every book-1 class), 1 (radius and
+// motion), 2 (quads too: the book-2 quad class and book 3). The mode and the ray source are
+// wave-uniform runtime branches. RRT_QUERY_ANY: a lane whose leaf batch accepted something leaves
+// the tree.
+constexpr int kQueryBlock = 256;
+template <bool kLds, typename StackT, int kGeom, int kBlk>
+__global__ __launch_bounds__(kBlk) void rrt_query(QParams P) {
+    extern __shared__ uint4 lds_dyn[];
+    using Node = typename std::conditional<kLds, GNode, GNodeH>::type;
+    [[maybe_unused]] const uint32_t node_base = kLds ? lds_addr(lds_dyn) : 0u;
+    const Node *nodes = reinterpret_cast<const Node *>(P.nodes);
+    const float4 *prims = P.prim_cr;
+    const float4 *motion = P.prim_motion;
+    uint32_t stack16 = 0;  // the stack's offset in 16-B units
+    if constexpr (kLds) {
+        uint4 *dst = lds_dyn;
+        const uint4 *src_n = reinterpret_cast<const uint4 *>(P.nodes);
+        constexpr uint32_t kNode16 = (uint32_t)(sizeof(GNode) / 16);
+        const uint32_t nn = P.n_nodes * kNode16;
+        for (uint32_t i = threadIdx.x; i < nn; i += kBlk) {
+            uint4 v = src_n[i];
+            if (i % kNode16 == kNode16 - 1u) {  // the links end a GNode (render_body)
+                v.z = lds_node_link(v.z) + (v.z > kLinkFirstMask ? 0u : node_base);
+                v.w = lds_node_link(v.w) + (v.w > kLinkFirstMask ? 0u : node_base);
+            }
+            dst[i] = v;
+        }
+        const uint4 *src_p = reinterpret_cast<const uint4 *>(P.prim_cr);
+        for (uint32_t i = threadIdx.x; i < P.n_prims; i += kBlk) dst[nn + i] = src_p[i];
+        stack16 = nn + P.n_prims;
+        if constexpr (kGeom > 0) {
+            const uint4 *src_v = reinterpret_cast<const uint4 *>(P.prim_motion);
+            for (uint32_t i = threadIdx.x; i < P.n_prims; i += kBlk) dst[nn + P.n_prims + i] = src_v[i];
+            motion = reinterpret_cast<const float4 *>(dst + nn + P.n_prims);
+            stack16 += P.n_prims;
+        }
+        __syncthreads();
+        nodes = reinterpret_cast<const Node *>(dst);
+        prims = reinterpret_cast<const float4 *>(dst + nn);
+    }
+    LdsStack<StackT, kBlk> stack;
+    stack.init(reinterpret_cast<StackT *>(lds_dyn + stack16), threadIdx.x);
+
+    const uint32_t lane = threadIdx.x & 63u;
+    constexpr uint32_t kWaves = (uint32_t)kBlk / 64u;
+    const uint32_t wave_in_block = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint32_t n_waves = gridDim.x * kWaves;
+    const bool any = P.mode == RRT_QUERY_ANY;
+    Counters cnt = {0, 0, 0, 0, 0, 0};
+    constexpr bool kOrd16 = !kLds;  // the ordered f16 slab for nodes read from global memory
+    for (uint32_t g = blockIdx.x * kWaves + wave_in_block; g < P.n_groups; g += n_waves) {
+        V3 o = v3(0.0f, 0.0f, 0.0f), d = o;
+        float tmax = 0.0f, time = 0.0f;
+        size_t slot;
+        bool valid;
+        if (P.rays == nullptr) {  // the camera's ray through pixel (x, y): camera_ray at ox = oy = 0, no defocus
+            const uint32_t ty = g / P.tiles_x, tx = g - ty * P.tiles_x;
+            const uint32_t x = tx * kTileW + lane % kTileW, y = ty * kTileH + lane / kTileW;
+            valid = x < P.width && y < P.height;
+            slot = (size_t)y * P.width + x;
+            const float fi = (float)x, fj = (float)y;
+            o = v3(P.center[0], P.center[1], P.center[2]);
+            d = sub(v3(P.p00[0] + P.du[0] * fi + P.dv[0] * fj, P.p00[1] + P.du[1] * fi + P.dv[1] * fj,
+                       P.p00[2] + P.du[2] * fi + P.dv[2] * fj),
+                    o);
+            tmax = __builtin_inff();
+            time = P.time;
+        } else {
+            slot = (size_t)g * 64u + lane;
+            valid = slot < (size_t)P.n;
+            if (valid) {
+                const float4 r0 = P.rays[2 * slot], r1 = P.rays[2 * slot + 1];
+                o = v3(r0.x, r0.y, r0.z);
+                d = v3(r1.x, r1.y, r1.z);
+                tmax = r0.w;
+                time = r1.w;
+            }
+        }
+        Trav tr;
+        trav_begin(tr, (int)node_base, stack.bottom);
+        tr.closest = tmax;  // the interval's end instead of camera.rs:187's +inf
+        // a NaN or <= 0.001 end finds nothing (a NaN would be dropped by the slab's min and walk the tree)
+        if (!valid || !(tmax > 0.001f) || P.n_nodes == 0u) tr.node = -1;
+        const uint32_t live = (uint32_t)__popcll(__ballot(valid));
+        const uint32_t leaf_min = (live * P.leaf_frac) >> 8;
+        RayK rk;
+        if (tr.node >= 0) rk = ray_consts<!kOrd16, true>(o, d);
+        const Prims<kGeom> pr{prims, motion, time, P.quads, nullptr, P.n_quads, 0ull, nullptr};
+        Leaves lv = 0;
+        uint64_t step = __ballot(tr.node >= 0);
+        for (;;) {  // render_body's BVH2 loop at min_active = 0
+            if (__builtin_amdgcn_inverse_ballot_w64(step)) trav_node<false, kOrd16>(nodes, stack, rk, tr, lv, cnt);
+            const uint64_t pm = __ballot(lv != 0);
+            const uint64_t nm = __ballot(tr.node >= 0);
+            step = nm & ~pm;
+            const int32_t waiting = __popcll(pm), stepping = __popcll(step);
+            const int32_t leave = waiting + stepping - 1;  // < 0: no lane is in the tree
+            const int32_t batch = ((int32_t)leaf_min - waiting) | leave | (stepping - 1);  // < 0: batch
+            if (batch < 0) {
+                if (__builtin_amdgcn_inverse_ballot_w64(pm)) {
+                    trav_leaves<false, true>(pr, lv, o, d, rk, -1, tr, cnt);
+                    lv = 0;
+                    if (any && tr.hit_prim >= 0) tr.node = -1;  // any-hit: this batch accepted something
+                }
+                step = any ? __ballot(tr.node >= 0) : nm;
+            }
+            if (leave < 0) break;
+        }
+        if (valid) {
+            const bool hit = tr.hit_prim >= 0;
+            uint2 h;
+            h.x = hit ? __float_as_uint(tr.closest) : 0u;
+            h.y = hit ? P.order[tr.hit_prim] : RRT_NO_PRIM;
+            P.hits[slot] = h;
+        }
+    }
+}
+
 // The pass's chunk sums into accum, continuing the left fold over chunks in order: the first
 // pass starts from its chunk 0, later passes from the accum so far; w = the tile's sample count.
 // partial is [pass chunk][pixel], so each chunk row is read coalesced.
@@ -2216,6 +2343,82 @@ hipError_t launch_render_pass(const KParams &p, bool count, hipStream_t stream) 
     default: break;
     }
     return p.bvh_width == 4 ? launch_width<true, 0>(p, pl, count, stream) : launch_width<false, 0>(p, pl, count, stream);
+}
+
+namespace {
+
+// One rrt_query instantiation on a persistent grid: at most occupancy x CUs blocks (each stages the
+// scene once and its waves stride over the ray groups), fewer when the groups are few.
+template <bool kLds, typename StackT, int kGeom>
+hipError_t launch_query_variant(const KParams &s, const QParams &q, hipStream_t stream) {
+    constexpr int kBlk = kQueryBlock;
+    size_t lds = ((size_t)s.stack_depth * kBlk * sizeof(StackT) + 15u) / 16u * 16u;
+    if (kLds) {
+        // staged links are byte offsets held in 16-bit stack entries (lds_node_link)
+        if ((size_t)s.n_nodes * sizeof(GNode) > 65536u) return hipErrorInvalidValue;
+        lds += (size_t)s.n_nodes * sizeof(GNode) + (size_t)s.n_prims * (sizeof(float4) + (kGeom > 0 ? kMotionBytes : 0));
+    }
+    if (lds > kLdsBlockMax) return hipErrorInvalidValue;
+    auto kernel = rrt_query<kLds, StackT, kGeom, kBlk>;
+    hipError_t e;
+    if (lds > kLdsDefaultMax) {
+        e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    int per_cu = 0;
+    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kBlk, lds);
+    if (e != hipSuccess) return e;
+    if (per_cu < 1) per_cu = 1;
+    const uint32_t want = (q.n_groups + (uint32_t)kBlk / 64u - 1u) / ((uint32_t)kBlk / 64u);
+    const uint32_t blocks = std::max<uint32_t>(1u, std::min<uint32_t>(want, (uint32_t)per_cu * std::max(1u, s.n_cus)));
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kBlk), lds, stream, q);
+    e = hipGetLastError();
+    static const bool log = std::getenv("RRT_LAUNCH_LOG") != nullptr;  // debug: one line per launch on stderr
+    if (log)
+        std::fprintf(stderr, "rrt query: geometry %d, %s, stack %d B x %u, %zu B of LDS, %d block(s)/CU, %u blocks, %u groups: %s\n",
+                     kGeom, kLds ? "LDS" : "global", (int)sizeof(StackT), s.stack_depth, lds, per_cu, blocks, q.n_groups,
+                     hipGetErrorString(e));
+    return e;
+}
+
+template <int kGeom>
+hipError_t launch_query_geom(const KParams &s, const LaunchPlan &pl, const QParams &q, hipStream_t stream) {
+    if (pl.stack_bytes == 4u) return launch_query_variant<false, uint32_t, kGeom>(s, q, stream);
+    return pl.scene_in_lds ? launch_query_variant<true, uint16_t, kGeom>(s, q, stream)
+                           : launch_query_variant<false, uint16_t, kGeom>(s, q, stream);
+}
+
+}  // namespace
+
+hipError_t launch_query(const KParams &s, QParams q, hipStream_t stream) {
+    // the tree form is the render plan's: where the tree lives decides the node format the scene holds
+    const LaunchPlan pl = plan_launch(s);
+    if (!pl.ok || pl.f64 || s.bvh_width != 2u || pl.kclass == 3) return hipErrorInvalidValue;
+    q.nodes = s.nodes;
+    q.prim_cr = s.prim_cr;
+    q.prim_motion = s.prim_motion;
+    q.quads = s.quads;
+    q.n_nodes = s.n_nodes;
+    q.n_prims = s.n_prims;
+    q.n_quads = s.n_quads;
+    q.stack_depth = s.stack_depth;
+    q.leaf_frac = s.leaf_frac;
+    if (q.rays == nullptr) {
+        q.width = s.width;
+        q.height = s.height;
+        q.tiles_x = (s.width + kTileW - 1u) / kTileW;
+        q.n_groups = q.tiles_x * ((s.height + kTileH - 1u) / kTileH);
+        q.n = s.width * s.height;
+        for (int i = 0; i < 3; ++i) q.p00[i] = s.p00[i], q.du[i] = s.du[i], q.dv[i] = s.dv[i], q.center[i] = s.center[i];
+    } else {
+        q.width = q.height = 0u;
+        q.tiles_x = 1u;
+        q.n_groups = (uint32_t)(((uint64_t)q.n + 63u) / 64u);
+    }
+    if (q.n_groups == 0u) return hipSuccess;
+    if (pl.kclass <= 0) return launch_query_geom<kBook1Untextured>(s, pl, q, stream);
+    if (pl.kclass == 1) return launch_query_geom<1>(s, pl, q, stream);
+    return launch_query_geom<2>(s, pl, q, stream);  // quads: the book-2 quad class and book 3
 }
 
 // One launch (+ combine) per sample pass of at most p.pass_chunks chunks, in chunk order.

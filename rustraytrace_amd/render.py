@@ -474,6 +474,7 @@ class DeviceScene:
         device by the LBVH builder (RRT_FLAG_FAST_BVH, implies device_bvh): cheap rebuilds, a slower tree."""
         lib = _lib.load()
         self.scene = scene
+        self.device = int(device)
         flags = scene.flags | (_lib.FLAG_F64 if f64 else 0) | (_lib.FLAG_DEVICE_BVH if device_bvh else 0) | (_lib.FLAG_FAST_BVH if fast_bvh else 0)
         flags |= _lib.FLAG_F64_BOOK2 if f64_book2 else 0
         self._lib = lib
@@ -544,6 +545,46 @@ class DeviceScene:
         cam = np.ascontiguousarray(camera, dtype=_lib.CAMERA_DTYPE).reshape(1)
         _lib.check(self._lib.rrt_scene_set_camera(self._h, _lib.ptr(cam)))
         self.scene = dataclasses.replace(self.scene, camera=cam.copy())
+
+    def query(self, rays, mode: str = "closest") -> np.ndarray:
+        """rrt_scene_query: the render's closest-hit query over (0.001, tmax) for each ray of `rays`
+        (_lib.RAY_DTYPE: o, tmax, d, time), without shading; returns _lib.HIT_DTYPE records (t, prim),
+        prim the primitive's index in source order (spheres, then quads) or _lib.NO_PRIM for a miss.
+        mode "any": a hit, not necessarily the closest. Synchronous; f32 scenes without media."""
+        r = np.ascontiguousarray(rays, dtype=_lib.RAY_DTYPE).ravel()
+        hits = np.zeros(len(r), dtype=_lib.HIT_DTYPE)
+        _lib.check(self._lib.rrt_scene_query(self._h, _lib.ptr(r), len(r), self._mode(mode), _lib.ptr(hits)))
+        return hits
+
+    @staticmethod
+    def _mode(mode) -> int:
+        return _lib.QUERY_MODES[mode] if isinstance(mode, str) else int(mode)
+
+    def query_async(self, d_rays_ptr: int, n: int, d_hits_ptr: int, mode="closest", stream_ptr: int = 0) -> None:
+        """rrt_scene_query_async: n RAY_DTYPE records at d_rays_ptr answered into n HIT_DTYPE records
+        at d_hits_ptr (device memory), enqueued on the stream behind the updates and refits on it."""
+        _lib.check(self._lib.rrt_scene_query_async(self._h, ctypes.c_void_p(d_rays_ptr), int(n), self._mode(mode),
+                                                   ctypes.c_void_p(d_hits_ptr), ctypes.c_void_p(stream_ptr)))
+
+    def primary_hits_async(self, d_hits_ptr: int, time: float = 0.0, stream_ptr: int = 0) -> None:
+        """rrt_scene_primary_hits_async: height x width HIT_DTYPE records at d_hits_ptr (device memory),
+        record (y, x) the closest hit of the camera's ray through pixel (x, y) with zero jitter and no
+        defocus, at `time`."""
+        _lib.check(self._lib.rrt_scene_primary_hits_async(self._h, ctypes.c_float(time), ctypes.c_void_p(d_hits_ptr),
+                                                          ctypes.c_void_p(stream_ptr)))
+
+    def primary_hits(self, time: float = 0.0) -> np.ndarray:
+        """primary_hits_async into a torch buffer on the scene's device, synchronised: an (H, W) array
+        of HIT_DTYPE (an id and depth buffer of the current camera)."""
+        import torch
+
+        h, w = self.scene.height, self.scene.width
+        with torch.cuda.device(self.device):
+            buf = torch.zeros(max(h * w, 1) * 2, dtype=torch.int32, device=f"cuda:{self.device}")
+            self.primary_hits_async(buf.data_ptr(), time, torch.cuda.current_stream().cuda_stream)
+            torch.cuda.current_stream().synchronize()
+            out = buf.cpu().numpy()[: h * w * 2]
+        return out.view(_lib.HIT_DTYPE).reshape(h, w).copy()
 
     def update_spheres(self, spheres, motion=None, stream_ptr: int = 0) -> None:
         """rrt_scene_update_spheres: replaces the spheres (and, for a book-2 world, their motion rows;
