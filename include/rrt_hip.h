@@ -704,6 +704,61 @@ int32_t rrt_scene_query(RrtScene *scene, const RrtRay *rays, uint32_t n, uint32_
  * Refusals as above. */
 int32_t rrt_scene_primary_hits_async(RrtScene *scene, float time, RrtHit *d_hits, void *stream);
 
+/* ---- surface records of a created scene ------------------------------------------------- */
+
+/* The closest-hit query above, answered with the reference's HitRecord (hittable.rs:20-32) instead of
+ * (t, prim): the kernel that walked the tree writes the record from the values it holds when the walk
+ * ends, each field in the f32 operations the render's shading step forms it by, so a picker, a
+ * denoiser's albedo and normal buffers or a light baker read what a path would have seen. Closest hit
+ * only. The rays, tmax and time mean what they mean for rrt_scene_query_async, and (prim, t) are bit for
+ * bit what RRT_QUERY_CLOSEST answers for the ray on a scene that entry accepts.
+ *
+ * A hit:
+ *   p          origin + t * direction, one fused multiply-add per component (Ray::at)
+ *   t, prim    the root and the primitive's index in source order, as in RrtHit
+ *   normal     the outward normal, negated when the ray meets the surface from inside (front_face = 0).
+ *              Outward: a sphere's (p - center(time)) * (1 / r) with the 1 / r the render reads; a
+ *              quad's stored unit normal
+ *   front_face 1 when dot(direction, outward normal) < 0
+ *   uv         a sphere's get_sphere_uv (sphere.rs:46-52) of the outward normal n:
+ *              ((atan2(-n.z, n.x) + pi) / 2 pi, acos(-n.y) / pi), computed for every sphere whatever its
+ *              material. A quad's is (0, 0): the kernels never read a quad's (u, v), because quads take
+ *              no image texture
+ *   kind       the material's kind (RrtMaterial): 0 Lambertian, 1 metal, 2 dielectric, 3 image texture,
+ *              4 diffuse light, 5 checker, 6 noise
+ *   albedo     by kind: 0, 1 the material's albedo; 2 (1, 1, 1); 3 the texel the render samples at uv;
+ *              4 the emitted radiance, unconditionally (book 3's lights emit from their front face only:
+ *              apply that with front_face); 5 the checker's colour at p; 6 the noise value at p in all
+ *              three channels
+ * A miss (also: a tmax that finds nothing, an empty tree): prim = RRT_NO_PRIM, kind = RRT_SURFACE_MISS,
+ * albedo = the background term the render adds for that ray (the camera's background colour in
+ * background mode 1, else the sky gradient on the unit direction), every other field 0. _pad is 0.
+ *
+ * Constant media are accepted here, and never answered: a medium, in the tree or tested after the walk,
+ * is passed over without a test, so the record is the closest SURFACE, as if the scene's media and
+ * their boundary quads were absent (kind 7, the isotropic phase function, is never reported). */
+typedef struct RrtSurface {      /* 64 B, 16-byte aligned on the device */
+    float p[3];      float t;
+    float normal[3]; uint32_t prim;
+    float albedo[3]; uint32_t kind;
+    float uv[2];     uint32_t front_face; uint32_t _pad;
+} RrtSurface;
+#define RRT_SURFACE_MISS 0xffffffffu
+
+/* n rays at d_rays answered into n records at d_out (device memory, both 16-byte aligned), enqueued on
+ * `stream` like rrt_scene_query_async: behind the updates and refits on that stream, the scene's one
+ * piece of work in flight, counters left alone, n = 0 enqueues nothing, the leaf-order copy shared with
+ * the queries above. Refusals as there, the message naming the item, except that constant media are
+ * accepted: a null scene, null or misaligned pointers with n > 0, an RRT_FLAG_F64 scene, a width-4
+ * tree, a scene left invalid by a failed update. */
+int32_t rrt_scene_surface_async(RrtScene *scene, const RrtRay *d_rays, uint32_t n, RrtSurface *d_out, void *stream);
+/* The same for host arrays, synchronous, through the device buffers rrt_scene_query grows. */
+int32_t rrt_scene_surface(RrtScene *scene, const RrtRay *rays, uint32_t n, RrtSurface *out);
+/* width * height records in row-major order: the G-buffer of the current camera. Record (x, y) is the
+ * surface record of rrt_scene_primary_hits_async's ray through pixel (x, y), formed in the kernel by
+ * that entry's expression, in the same 8 x 8 tiles. */
+int32_t rrt_scene_primary_surface_async(RrtScene *scene, float time, RrtSurface *d_out, void *stream);
+
 /* ---- host-side callers of the boundary ------------------------------------------------ */
 
 /* == gpu::build_in_one_weekend_scene (gpu/mod.rs:124-301): RTOW final scene from
@@ -1016,6 +1071,14 @@ typedef struct RrtSceneBuildStats {
 } RrtSceneBuildStats;
 int32_t rrt_testing_scene_build_stats(const RrtScene *scene, RrtSceneBuildStats *out);
 int32_t rrt_testing_lbvh_form(int32_t form);
+
+/* Test support, not part of the drop-in (RRT_ABI_VERSION is unchanged and the Rust shim does not bind
+ * it). rrt_testing_scene_fail_update: leaves the scene in the state a change that failed midway leaves
+ * it in (an update fails midway only on a device error, which no test provokes): the scene is invalid,
+ * every render, refit and query of it is refused with RRT_E_INVALID naming this call, and a later
+ * rrt_scene_update_* that succeeds makes it valid again. Touches no device memory. Returns
+ * RRT_E_INVALID itself, with the message the failed change would have set. */
+int32_t rrt_testing_scene_fail_update(RrtScene *scene);
 
 /* Test support, not part of the drop-in (no reference counterpart; RRT_ABI_VERSION is unchanged and
  * the Rust shim does not bind it): the launch shape the library picks for a scene, computed on the

@@ -124,6 +124,10 @@ EXPORTED_SYMBOLS = (
     "rrt_scene_query_async",
     "rrt_scene_query",
     "rrt_scene_primary_hits_async",
+    "rrt_scene_surface_async",
+    "rrt_scene_surface",
+    "rrt_scene_primary_surface_async",
+    "rrt_testing_scene_fail_update",
 )
 
 # == RrtRay / RrtHit (include/rrt_hip.h): a query ray and its answer
@@ -132,6 +136,11 @@ HIT_DTYPE = np.dtype([("t", "<f4"), ("prim", "<u4")])
 assert RAY_DTYPE.itemsize == 32 and HIT_DTYPE.itemsize == 8
 NO_PRIM = 0xFFFFFFFF  # RRT_NO_PRIM
 QUERY_MODES = {"closest": 0, "any": 1}  # RRT_QUERY_CLOSEST, RRT_QUERY_ANY
+# == RrtSurface (include/rrt_hip.h): the HitRecord of a closest hit
+SURFACE_DTYPE = np.dtype([("p", "<f4", 3), ("t", "<f4"), ("normal", "<f4", 3), ("prim", "<u4"), ("albedo", "<f4", 3),
+                          ("kind", "<u4"), ("uv", "<f4", 2), ("front_face", "<u4"), ("_pad", "<u4")])
+assert SURFACE_DTYPE.itemsize == 64
+SURFACE_MISS = 0xFFFFFFFF  # RRT_SURFACE_MISS
 
 # == RrtSceneTable (include/rrt_hip.h, test support): table -> (code, row dtype)
 SCENE_TABLES = {
@@ -545,6 +554,10 @@ def load() -> ctypes.CDLL:
         "rrt_scene_query_async": (c_int32, [P, P, c_uint32, c_uint32, P, P]),
         "rrt_scene_query": (c_int32, [P, P, c_uint32, c_uint32, P]),
         "rrt_scene_primary_hits_async": (c_int32, [P, c_float, P, P]),
+        "rrt_scene_surface_async": (c_int32, [P, P, c_uint32, P, P]),
+        "rrt_scene_surface": (c_int32, [P, P, c_uint32, P]),
+        "rrt_scene_primary_surface_async": (c_int32, [P, c_float, P, P]),
+        "rrt_testing_scene_fail_update": (c_int32, [P]),
     }
     experiment = "RRT_LIB_PATH" in os.environ  # A/B of older builds: tolerate symbols they lack
     for name, (res, args) in sig.items():

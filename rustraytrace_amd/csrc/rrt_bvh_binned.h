@@ -281,6 +281,10 @@ RRT_BB_HD void round_box(const double *box, const Slack *slack, float *lo, float
 RRT_BB_HD void never_hit(double *box) {
     for (int j = 0; j < 6; ++j) box[j] = 1e30;
 }
+// A never-hit slot as the 32-B packers (pack_node32, rrt_host.cpp put_node2) recognise it after
+// round_box: its lo is 1e30 rounded DOWN to f32, one step below 1e30f (which lies above 1e30), so the
+// test is against a bound under both; real boxes stay below 1e29 (round_box).
+constexpr float kNeverHitLo = 9e29f;
 
 // f32 -> f16 bits rounded toward -inf (up = false) or +inf, subnormal results pushed outward to 0
 // or the smallest normal (rrt_host.cpp f16_round, without the conversion instruction).
@@ -331,7 +335,9 @@ RRT_BB_HD void pack_node80(const float lo[2][3], const float hi[2][3], const uin
 }
 RRT_BB_HD void pack_node32(const float lo[2][3], const float hi[2][3], const uint32_t link[2], uint32_t *w /* 8 */) {
     for (int c = 0; c < 2; ++c) {
-        const bool never = lo[c][0] >= 1e30f;
+        // (compared with 1e30f the slot became the box [65504, +inf)^3, which a ray into the positive
+        // octant enters, and its link 0 is the root)
+        const bool never = lo[c][0] >= kNeverHitLo;
         for (int a = 0; a < 3; ++a) {
             const uint32_t l = never ? 0x7bffu : f16_round(lo[c][a], false);
             const uint32_t h = never ? 0x7bffu : f16_round(hi[c][a], true);

@@ -444,7 +444,10 @@ void put_node2(rrt::GNodeH &n, const float *lo0, const float *hi0, const float *
     const float *lo[2] = {lo0, lo1}, *hi[2] = {hi0, hi1};
     uint32_t *dst[2] = {n.c0, n.c1};
     for (int c = 0; c < 2; ++c) {
-        const bool never = lo[c][0] >= 1e30f;  // never_hit_box(): the point (65504, 65504, 65504)
+        // never_hit_box(): the point (65504, 65504, 65504). Its lo is 1e30 rounded DOWN to f32, one step
+        // below 1e30f (which lies above 1e30): compared with 1e30f the slot became the box
+        // [65504, +inf)^3, which a ray into the positive octant enters, and its link is the root's
+        const bool never = lo[c][0] >= rrt::bvhb::kNeverHitLo;
         for (int a = 0; a < 3; ++a) {
             const uint16_t l = never ? 0x7bffu : f16_round(lo[c][a], false);
             const uint16_t h = never ? 0x7bffu : f16_round(hi[c][a], true);
@@ -1247,8 +1250,9 @@ struct RrtScene {
     // host-array entry's device buffers, grown to the largest call
     uint32_t *d_query_order = nullptr;
     RrtRay *d_query_rays = nullptr;
-    RrtHit *d_query_hits = nullptr;
-    size_t query_cap = 0;  // rays and hits
+    void *d_query_out = nullptr;  // RrtHit or RrtSurface records
+    size_t query_cap = 0;         // rays
+    size_t query_out_bytes = 0;
 };
 
 namespace {
@@ -1290,7 +1294,7 @@ void free_scene(RrtScene *s) {
     (void)hipFree(s->d_src_bquads);
     (void)hipFree(s->d_query_order);
     (void)hipFree(s->d_query_rays);
-    (void)hipFree(s->d_query_hits);
+    (void)hipFree(s->d_query_out);
     if (s->h_stage) (void)hipHostFree(s->h_stage);
     if (s->ev_staged) (void)hipEventDestroy(s->ev_staged);
     if (s->ev_refit_done) (void)hipEventDestroy(s->ev_refit_done);
@@ -2959,20 +2963,23 @@ double render_progress(RrtScene *scene, hipStream_t side, uint32_t *host_heads, 
 
 // ---- ray queries ------------------------------------------------------------------------
 namespace {
-// The refusals of the three query entries, before any device call; d_rays may be null for the
-// primary-hit entry (primary), n is then the camera's pixel count.
+// The refusals of the query entries, before any device call; d_rays may be null for the primary
+// entries (primary), n is then the camera's pixel count. surface: the RrtSurface entries, whose
+// records are 16-byte aligned and which accept constant media (the walk passes over them).
 int check_query(const RrtScene *s, const std::string &fn, const void *d_rays, bool primary, uint64_t n, uint32_t mode,
-                const void *d_hits) {
+                const void *d_out, bool surface = false) {
+    const std::string out = surface ? "surface records" : "hits";
     if (!s) return fail(RRT_E_INVALID, fn + "null scene");
     if (mode != RRT_QUERY_CLOSEST && mode != RRT_QUERY_ANY)
         return fail(RRT_E_INVALID, fn + "unknown mode " + std::to_string(mode) + " (RRT_QUERY_CLOSEST or RRT_QUERY_ANY)");
     if (n && !primary && !d_rays) return fail(RRT_E_INVALID, fn + "null rays with n > 0");
-    if (n && !d_hits) return fail(RRT_E_INVALID, fn + "null hits with n > 0");
+    if (n && !d_out) return fail(RRT_E_INVALID, fn + "null " + out + " with n > 0");
     if (n && !primary && ((uintptr_t)d_rays & 15u)) return fail(RRT_E_INVALID, fn + "rays must be 16-byte aligned");
-    if (n && ((uintptr_t)d_hits & 7u)) return fail(RRT_E_INVALID, fn + "hits must be 8-byte aligned");
+    if (n && ((uintptr_t)d_out & (surface ? 15u : 7u)))
+        return fail(RRT_E_INVALID, fn + out + " must be " + (surface ? "16" : "8") + "-byte aligned");
     if (n > 0xffffffffull) return fail(RRT_E_INVALID, fn + "more than 2^32 - 1 rays");
     if (s->f64) return fail(RRT_E_INVALID, fn + "an RRT_FLAG_F64 scene holds the f64 kernel's tables; queries need an f32 scene");
-    if (s->base.n_media)
+    if (s->base.n_media && !surface)
         return fail(RRT_E_INVALID, fn + "the scene has constant media, which are volumes with a stochastic free flight, "
                                         "not surfaces; queries do not see through them");
     if (s->base.bvh_width != 2u) return fail(RRT_E_INVALID, fn + "a width-4 tree (RRT_BVH_WIDTH=4); queries walk the binary tree");
@@ -2982,8 +2989,10 @@ int check_query(const RrtScene *s, const std::string &fn, const void *d_rays, bo
     return RRT_OK;
 }
 
-// Checked arguments: the first query's order table, then the launch on `stream`.
-int query_launch(RrtScene *s, const RrtRay *d_rays, uint32_t n, uint32_t mode, float time, RrtHit *d_hits, void *stream) {
+// Checked arguments: the first query's order table, then the launch on `stream`. d_surf != null: the
+// surface records' kernels, which write there instead of d_hits.
+int query_launch(RrtScene *s, const RrtRay *d_rays, uint32_t n, uint32_t mode, float time, RrtHit *d_hits, void *stream,
+                 RrtSurface *d_surf = nullptr) {
     HIP_TRY(hipSetDevice(s->device), "hipSetDevice");
     if (!s->d_query_order) {
         if (int rc = upload(&s->d_query_order, s->order.data(), s->order.size(), "query leaf order")) {
@@ -2996,10 +3005,42 @@ int query_launch(RrtScene *s, const RrtRay *d_rays, uint32_t n, uint32_t mode, f
     q.order = s->d_query_order;
     q.rays = reinterpret_cast<const float4 *>(d_rays);
     q.hits = reinterpret_cast<uint2 *>(d_hits);
+    q.surf = reinterpret_cast<uint4 *>(d_surf);
     q.n = n;
     q.mode = mode;
     q.time = time;
     HIP_TRY(rrt::launch_query(s->base, q, (hipStream_t)stream), "query kernel launch");
+    return RRT_OK;
+}
+
+// The host-array entries: rays up, the launch on the null stream, n records of rec_bytes down, through
+// the scene's two device buffers, each grown to the largest call so far (the answers of both record
+// types share one).
+int query_host(RrtScene *s, const std::string &fn, const RrtRay *rays, uint32_t n, uint32_t mode, void *out, size_t rec_bytes) {
+    const bool surface = rec_bytes == sizeof(RrtSurface);
+    // (host arrays: no alignment beyond the records' own)
+    if (int rc = check_query(s, fn, nullptr, true, 0, mode, nullptr, surface)) return rc;
+    if (n && !rays) return fail(RRT_E_INVALID, fn + "null rays with n > 0");
+    if (n && !out) return fail(RRT_E_INVALID, fn + (surface ? "null surface records with n > 0" : "null hits with n > 0"));
+    if (n == 0) return RRT_OK;
+    HIP_TRY(hipSetDevice(s->device), "hipSetDevice");
+    if (s->query_cap < n) {
+        (void)hipFree(s->d_query_rays);
+        s->d_query_rays = nullptr, s->query_cap = 0;
+        HIP_TRY(hipMalloc((void **)&s->d_query_rays, (size_t)n * sizeof(RrtRay)), "hipMalloc query rays");
+        s->query_cap = n;
+    }
+    if (s->query_out_bytes < (size_t)n * rec_bytes) {
+        (void)hipFree(s->d_query_out);
+        s->d_query_out = nullptr, s->query_out_bytes = 0;
+        HIP_TRY(hipMalloc(&s->d_query_out, (size_t)n * rec_bytes), "hipMalloc query answers");
+        s->query_out_bytes = (size_t)n * rec_bytes;
+    }
+    HIP_TRY(hipMemcpy(s->d_query_rays, rays, (size_t)n * sizeof(RrtRay), hipMemcpyHostToDevice), "copy rays");
+    if (int rc = query_launch(s, s->d_query_rays, n, mode, 0.0f, surface ? nullptr : (RrtHit *)s->d_query_out, nullptr,
+                              surface ? (RrtSurface *)s->d_query_out : nullptr))
+        return rc;
+    HIP_TRY(hipMemcpy(out, s->d_query_out, (size_t)n * rec_bytes, hipMemcpyDeviceToHost), "copy answers");
     return RRT_OK;
 }
 }  // namespace
@@ -3011,24 +3052,7 @@ int32_t rrt_scene_query_async(RrtScene *scene, const RrtRay *d_rays, uint32_t n,
 }
 
 int32_t rrt_scene_query(RrtScene *scene, const RrtRay *rays, uint32_t n, uint32_t mode, RrtHit *hits) {
-    // (host arrays: no alignment beyond the records' own)
-    if (int rc = check_query(scene, "rrt_scene_query: ", nullptr, true, 0, mode, nullptr)) return rc;
-    if (n && !rays) return fail(RRT_E_INVALID, "rrt_scene_query: null rays with n > 0");
-    if (n && !hits) return fail(RRT_E_INVALID, "rrt_scene_query: null hits with n > 0");
-    if (n == 0) return RRT_OK;
-    HIP_TRY(hipSetDevice(scene->device), "hipSetDevice");
-    if (scene->query_cap < n) {
-        (void)hipFree(scene->d_query_rays);
-        (void)hipFree(scene->d_query_hits);
-        scene->d_query_rays = nullptr, scene->d_query_hits = nullptr, scene->query_cap = 0;
-        HIP_TRY(hipMalloc((void **)&scene->d_query_rays, (size_t)n * sizeof(RrtRay)), "hipMalloc query rays");
-        HIP_TRY(hipMalloc((void **)&scene->d_query_hits, (size_t)n * sizeof(RrtHit)), "hipMalloc query hits");
-        scene->query_cap = n;
-    }
-    HIP_TRY(hipMemcpy(scene->d_query_rays, rays, (size_t)n * sizeof(RrtRay), hipMemcpyHostToDevice), "copy rays");
-    if (int rc = query_launch(scene, scene->d_query_rays, n, mode, 0.0f, scene->d_query_hits, nullptr)) return rc;
-    HIP_TRY(hipMemcpy(hits, scene->d_query_hits, (size_t)n * sizeof(RrtHit), hipMemcpyDeviceToHost), "copy hits");
-    return RRT_OK;
+    return query_host(scene, "rrt_scene_query: ", rays, n, mode, hits, sizeof(RrtHit));
 }
 
 int32_t rrt_scene_primary_hits_async(RrtScene *scene, float time, RrtHit *d_hits, void *stream) {
@@ -3036,6 +3060,23 @@ int32_t rrt_scene_primary_hits_async(RrtScene *scene, float time, RrtHit *d_hits
     if (int rc = check_query(scene, "rrt_scene_primary_hits_async: ", nullptr, true, n, RRT_QUERY_CLOSEST, d_hits)) return rc;
     if (n == 0) return RRT_OK;
     return query_launch(scene, nullptr, (uint32_t)n, RRT_QUERY_CLOSEST, time, d_hits, stream);
+}
+
+int32_t rrt_scene_surface_async(RrtScene *scene, const RrtRay *d_rays, uint32_t n, RrtSurface *d_out, void *stream) {
+    if (int rc = check_query(scene, "rrt_scene_surface_async: ", d_rays, false, n, RRT_QUERY_CLOSEST, d_out, true)) return rc;
+    if (n == 0) return RRT_OK;
+    return query_launch(scene, d_rays, n, RRT_QUERY_CLOSEST, 0.0f, nullptr, stream, d_out);
+}
+
+int32_t rrt_scene_surface(RrtScene *scene, const RrtRay *rays, uint32_t n, RrtSurface *out) {
+    return query_host(scene, "rrt_scene_surface: ", rays, n, RRT_QUERY_CLOSEST, out, sizeof(RrtSurface));
+}
+
+int32_t rrt_scene_primary_surface_async(RrtScene *scene, float time, RrtSurface *d_out, void *stream) {
+    const uint64_t n = scene ? (uint64_t)scene->base.width * scene->base.height : 0u;
+    if (int rc = check_query(scene, "rrt_scene_primary_surface_async: ", nullptr, true, n, RRT_QUERY_CLOSEST, d_out, true)) return rc;
+    if (n == 0) return RRT_OK;
+    return query_launch(scene, nullptr, (uint32_t)n, RRT_QUERY_CLOSEST, time, nullptr, stream, d_out);
 }
 
 int32_t rrt_scene_read_counters(RrtScene *scene, RrtCounters *out) {
@@ -3200,6 +3241,11 @@ extern "C" int32_t rrt_testing_lbvh_form(int32_t form) {
     if (!rrt::set_lbvh_form(form)) return fail(RRT_E_INVALID, "rrt_testing_lbvh_form: the form is -1, 0 or 1");
     return RRT_OK;
 }
+extern "C" int32_t rrt_testing_scene_fail_update(RrtScene *scene) {
+    if (!scene) return fail(RRT_E_INVALID, "rrt_testing_scene_fail_update: null scene");
+    return broke(scene, "rrt_testing_scene_fail_update: ", RRT_E_INVALID, "the test hook stood in for a change that failed midway");
+}
+
 extern "C" int32_t rrt_testing_scene_build_stats(const RrtScene *scene, RrtSceneBuildStats *out) {
     if (!scene || !out) return fail(RRT_E_INVALID, "rrt_testing_scene_build_stats: null scene or out");
     if (!scene->builder)

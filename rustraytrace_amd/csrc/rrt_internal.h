@@ -388,6 +388,16 @@ struct QParams {
     uint32_t width, height, tiles_x;  // primary rays
     float time;                       // primary rays
     float p00[3], du[3], dv[3], center[3];
+    // surface records (rrt_scene_surface_async, rrt_scene_primary_surface_async), appended so the plain
+    // queries' field offsets stay: surf != null selects the kernels with the record epilogue, which
+    // write there instead of hits; the rest is the launcher's, the tables as the render reads them
+    uint4 *surf;                 // RrtSurface as four 16-byte words
+    const GMaterial *prim_mtl;   // leaf order
+    const GPerlin *perlin;
+    const uint8_t *tex_pool;
+    const GTexture *texs;
+    uint32_t bg_mode;
+    float background[3];
 };
 // The query on `stream`, in the instantiation the scene's render plan names (tree placement, stack
 // type) for the scene's geometry form; p.n_groups, tiles_x are the launcher's. n_cus: grid sizing.

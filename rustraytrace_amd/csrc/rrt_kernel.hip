@@ -468,6 +468,7 @@ struct Prims {
     const GPerlin *perlin;  // Perlin tables (LDS copy when staged, else KParams.perlin)
     static constexpr bool kHasQuads = kBook2 >= 2;
     static constexpr bool kHasMedia = kBook2 >= 3;
+    static constexpr bool kSkipMedia = false;  // SurfacePrims
     // Book-1 scenes store r * r (f32, rounded as the test would round it) in the record's w and
     // 1 / r (the normal's IEEE quotient, sphere.rs:48 through vec3.rs:142-148) in the material
     // record's b.w (rrt_host.cpp): one multiply less per sphere test, one division less per hit.
@@ -487,6 +488,14 @@ struct Prims {
         }
         return c;
     }
+};
+// The surface queries' form of a scene with constant media (rrt_scene_surface_async): the quad form,
+// whose leaf test rejects a medium's record (tag -(1 + n_quads + index)) without testing it —
+// medium_hit draws from a path's stream, which a query does not have — so the walk answers the
+// closest surface as if the media and their boundary quads were absent. md and seg are never read.
+struct SurfacePrims : Prims<2> {
+    static constexpr bool kSkipMedia = true;
+    __device__ __forceinline__ SurfacePrims(const Prims<2> &b) : Prims<2>(b) {}
 };
 
 // Quad::hit (the_next_week/quad.rs:61-87) in f32: plane distance, then the hit point's (alpha,
@@ -659,6 +668,7 @@ __device__ __forceinline__ void test_prim(const PR &prim_cr, float4 cr, float4 m
     if constexpr (PR::kHasQuads) {
         if (cr.w < 0.0f) {
             const int j = (int)(-cr.w) - 1;
+            if (PR::kSkipMedia && j >= (int)prim_cr.n_quads) return;
             float tq;
             bool h;
             if (PR::kHasMedia && j >= (int)prim_cr.n_quads) h = medium_hit(prim_cr, j - (int)prim_cr.n_quads, o, d, rk, closest, tq);
@@ -1164,7 +1174,8 @@ __device__ __forceinline__ bool checker_even(float inv_scale, V3 p) {
     return sum % 2 == 0;
 }
 
-__device__ __forceinline__ V3 texel(const KParams &P, int tex, float u, float v) {
+template <class KP>  // KParams, or the surface query's QParams: texs and tex_pool
+__device__ __forceinline__ V3 texel(const KP &P, int tex, float u, float v) {
     const GTexture t = P.texs[tex];
     if (t.height <= 0) return v3(0.0f, 1.0f, 1.0f);  // texture.rs:91-93
     u = (u < 0.0f) ? 0.0f : ((u > 1.0f) ? 1.0f : u);  // Interval::clamp
@@ -1938,9 +1949,82 @@ __global__ __launch_bounds__(kBlk, kWaves) void rrt_render(KParams P) {
 // motion), 2 (quads too: the book-2 quad class and book 3). The mode and the ray source are
 // wave-uniform runtime branches. RRT_QUERY_ANY: a lane whose leaf batch accepted something leaves
 // the tree.
+//
+// Surface records (rrt_scene_surface_async, rrt_scene_primary_surface_async): kSurf names the
+// material class of an epilogue that runs once per ray after the loop — the lane still holds o, d,
+// the time, the root and the hit's leaf-order index, which every per-primitive table is keyed by —
+// and writes an RrtSurface (surface_record) instead of the RrtHit. kSurfNone is the plain query;
+// the classes are the render's: kSurfBook1 (book-1 scenes without an image texture: no texel, no
+// checker, no noise), kSurfBook1Tex (book 1 with image textures), kSurfBook2 (books 2 and 3: checker
+// and noise too). kGeom = kGeomSurfaces is SurfacePrims, the quad form that passes over media.
 constexpr int kQueryBlock = 256;
-template <bool kLds, typename StackT, int kGeom, int kBlk>
+constexpr int kSurfNone = -1, kSurfBook1 = 0, kSurfBook1Tex = 1, kSurfBook2 = 2;
+constexpr int kGeomSurfaces = 3;
+
+// The HitRecord of a finished closest-hit query as an RrtSurface (include/rrt_hip.h), in shade's f32
+// operations restated (shade keeps its own copy: sharing it would move the render kernels'
+// registers): p by the fused Ray::at, the outward normal from the host's 1 / r or the quad's stored
+// unit normal, get_sphere_uv for every sphere, and the albedo by material kind; a miss carries the
+// background term shade adds. Materials, textures and Perlin tables are read from global memory: one
+// touch per ray. Four 16-byte stores.
+template <int kSurf, class PR>
+__device__ __forceinline__ void surface_record(const QParams &P, const PR &prims, V3 o, V3 d, float t, int prim, uint4 *out) {
+    if (prim < 0) {
+        V3 bg;
+        if (P.bg_mode == 1u) {
+            bg = v3(P.background[0], P.background[1], P.background[2]);
+        } else {
+            const V3 ud = unit(d);
+            const float a = 0.5f * (ud.y + 1.0f);
+            bg = v3((1.0f - a) * 1.0f + a * 0.5f, (1.0f - a) * 1.0f + a * 0.7f, (1.0f - a) * 1.0f + a * 1.0f);
+        }
+        out[0] = make_uint4(0u, 0u, 0u, 0u);
+        out[1] = make_uint4(0u, 0u, 0u, RRT_NO_PRIM);
+        out[2] = make_uint4(__float_as_uint(bg.x), __float_as_uint(bg.y), __float_as_uint(bg.z), RRT_SURFACE_MISS);
+        out[3] = make_uint4(0u, 0u, 0u, 0u);
+        return;
+    }
+    // HitRecord (sphere.rs:47-50, hittable.rs:20-32), as shade forms it
+    float4 qn;  // a quad's (normal, D): its motion slot
+    const float4 cr = prims.at(prim, qn);
+    const V3 p = v3(__builtin_fmaf(d.x, t, o.x), __builtin_fmaf(d.y, t, o.y), __builtin_fmaf(d.z, t, o.z));  // Ray::at, fused
+    const GMaterial m = P.prim_mtl[prim];
+    V3 outward;
+    float u = 0.0f, v = 0.0f;  // a quad's stay 0: the kernels never read them
+    if (PR::kHasQuads && cr.w < 0.0f) {
+        outward = v3(qn.x, qn.y, qn.z);
+    } else {
+        const float inv_r = PR::kR2 ? __int_as_float(m.b.w) : qn.w;
+        outward = v3((p.x - cr.x) * inv_r, (p.y - cr.y) * inv_r, (p.z - cr.z) * inv_r);
+        const float theta = rrt_acosf(-outward.y);  // get_sphere_uv (sphere.rs:46-52)
+        const float phi = rrt_atan2f(-outward.z, outward.x) + kPi;
+        u = div_by_const(phi, 2.0f * kPi);
+        v = div_by_const(theta, kPi);
+    }
+    const bool front = dot(d, outward) < 0.0f;
+    const V3 nrm = front ? outward : v3(-outward.x, -outward.y, -outward.z);
+    const int kind = m.b.x;
+    V3 alb = v3(m.a.x, m.a.y, m.a.z);  // Lambertian, Metal; DiffuseLight: the emitted radiance
+    if (kind == 2) {
+        alb = v3(1.0f, 1.0f, 1.0f);
+    } else if (kSurf >= kSurfBook1Tex && kind == 3) {
+        alb = texel(P, m.b.z, u, v);
+    } else if (kSurf == kSurfBook2 && kind == 5) {
+        if (!checker_even(m.a.w, p)) alb = v3(__int_as_float(m.b.y), __int_as_float(m.b.z), __int_as_float(m.b.w));
+    } else if (kSurf == kSurfBook2 && kind == 6) {
+        // noise_at()'s global arm: a query block stages no Perlin tables, so there is no LDS arm to choose
+        const float g = noise_value(P.perlin + m.b.z, m.a.w, p);
+        alb = v3(g, g, g);
+    }
+    out[0] = make_uint4(__float_as_uint(p.x), __float_as_uint(p.y), __float_as_uint(p.z), __float_as_uint(t));
+    out[1] = make_uint4(__float_as_uint(nrm.x), __float_as_uint(nrm.y), __float_as_uint(nrm.z), P.order[prim]);
+    out[2] = make_uint4(__float_as_uint(alb.x), __float_as_uint(alb.y), __float_as_uint(alb.z), (uint32_t)kind);
+    out[3] = make_uint4(__float_as_uint(u), __float_as_uint(v), front ? 1u : 0u, 0u);
+}
+
+template <bool kLds, typename StackT, int kGeom, int kBlk, int kSurf = kSurfNone>
 __global__ __launch_bounds__(kBlk) void rrt_query(QParams P) {
+    static_assert(kSurf != kSurfNone || kGeom != kGeomSurfaces, "only the surface entries accept media");
     extern __shared__ uint4 lds_dyn[];
     using Node = typename std::conditional<kLds, GNode, GNodeH>::type;
     [[maybe_unused]] const uint32_t node_base = kLds ? lds_addr(lds_dyn) : 0u;
@@ -1981,7 +2065,7 @@ __global__ __launch_bounds__(kBlk) void rrt_query(QParams P) {
     constexpr uint32_t kWaves = (uint32_t)kBlk / 64u;
     const uint32_t wave_in_block = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const uint32_t n_waves = gridDim.x * kWaves;
-    const bool any = P.mode == RRT_QUERY_ANY;
+    const bool any = kSurf == kSurfNone && P.mode == RRT_QUERY_ANY;  // surface records: closest hit only
     Counters cnt = {0, 0, 0, 0, 0, 0};
     constexpr bool kOrd16 = !kLds;  // the ordered f16 slab for nodes read from global memory
     for (uint32_t g = blockIdx.x * kWaves + wave_in_block; g < P.n_groups; g += n_waves) {
@@ -2021,7 +2105,9 @@ __global__ __launch_bounds__(kBlk) void rrt_query(QParams P) {
         const uint32_t leaf_min = (live * P.leaf_frac) >> 8;
         RayK rk;
         if (tr.node >= 0) rk = ray_consts<!kOrd16, true>(o, d);
-        const Prims<kGeom> pr{prims, motion, time, P.quads, nullptr, P.n_quads, 0ull, nullptr};
+        using Base = Prims<kGeom == kGeomSurfaces ? 2 : kGeom>;
+        using PR = typename std::conditional<kGeom == kGeomSurfaces, SurfacePrims, Base>::type;
+        const PR pr = Base{prims, motion, time, P.quads, nullptr, P.n_quads, 0ull, nullptr};
         Leaves lv = 0;
         uint64_t step = __ballot(tr.node >= 0);
         for (;;) {  // render_body's BVH2 loop at min_active = 0
@@ -2042,7 +2128,9 @@ __global__ __launch_bounds__(kBlk) void rrt_query(QParams P) {
             }
             if (leave < 0) break;
         }
-        if (valid) {
+        if constexpr (kSurf != kSurfNone) {
+            if (valid) surface_record<kSurf>(P, pr, o, d, tr.closest, tr.hit_prim, P.surf + 4u * slot);
+        } else if (valid) {
             const bool hit = tr.hit_prim >= 0;
             uint2 h;
             h.x = hit ? __float_as_uint(tr.closest) : 0u;
@@ -2349,7 +2437,7 @@ namespace {
 
 // One rrt_query instantiation on a persistent grid: at most occupancy x CUs blocks (each stages the
 // scene once and its waves stride over the ray groups), fewer when the groups are few.
-template <bool kLds, typename StackT, int kGeom>
+template <bool kLds, typename StackT, int kGeom, int kSurf = kSurfNone>
 hipError_t launch_query_variant(const KParams &s, const QParams &q, hipStream_t stream) {
     constexpr int kBlk = kQueryBlock;
     size_t lds = ((size_t)s.stack_depth * kBlk * sizeof(StackT) + 15u) / 16u * 16u;
@@ -2359,7 +2447,7 @@ hipError_t launch_query_variant(const KParams &s, const QParams &q, hipStream_t 
         lds += (size_t)s.n_nodes * sizeof(GNode) + (size_t)s.n_prims * (sizeof(float4) + (kGeom > 0 ? kMotionBytes : 0));
     }
     if (lds > kLdsBlockMax) return hipErrorInvalidValue;
-    auto kernel = rrt_query<kLds, StackT, kGeom, kBlk>;
+    auto kernel = rrt_query<kLds, StackT, kGeom, kBlk, kSurf>;
     hipError_t e;
     if (lds > kLdsDefaultMax) {
         e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -2375,17 +2463,17 @@ hipError_t launch_query_variant(const KParams &s, const QParams &q, hipStream_t 
     e = hipGetLastError();
     static const bool log = std::getenv("RRT_LAUNCH_LOG") != nullptr;  // debug: one line per launch on stderr
     if (log)
-        std::fprintf(stderr, "rrt query: geometry %d, %s, stack %d B x %u, %zu B of LDS, %d block(s)/CU, %u blocks, %u groups: %s\n",
-                     kGeom, kLds ? "LDS" : "global", (int)sizeof(StackT), s.stack_depth, lds, per_cu, blocks, q.n_groups,
+        std::fprintf(stderr, "rrt query: surface class %d, geometry %d, %s, stack %d B x %u, %zu B of LDS, %d block(s)/CU, %u blocks, %u groups: %s\n",
+                     kSurf, kGeom, kLds ? "LDS" : "global", (int)sizeof(StackT), s.stack_depth, lds, per_cu, blocks, q.n_groups,
                      hipGetErrorString(e));
     return e;
 }
 
-template <int kGeom>
+template <int kGeom, int kSurf = kSurfNone>
 hipError_t launch_query_geom(const KParams &s, const LaunchPlan &pl, const QParams &q, hipStream_t stream) {
-    if (pl.stack_bytes == 4u) return launch_query_variant<false, uint32_t, kGeom>(s, q, stream);
-    return pl.scene_in_lds ? launch_query_variant<true, uint16_t, kGeom>(s, q, stream)
-                           : launch_query_variant<false, uint16_t, kGeom>(s, q, stream);
+    if (pl.stack_bytes == 4u) return launch_query_variant<false, uint32_t, kGeom, kSurf>(s, q, stream);
+    return pl.scene_in_lds ? launch_query_variant<true, uint16_t, kGeom, kSurf>(s, q, stream)
+                           : launch_query_variant<false, uint16_t, kGeom, kSurf>(s, q, stream);
 }
 
 }  // namespace
@@ -2393,7 +2481,7 @@ hipError_t launch_query_geom(const KParams &s, const LaunchPlan &pl, const QPara
 hipError_t launch_query(const KParams &s, QParams q, hipStream_t stream) {
     // the tree form is the render plan's: where the tree lives decides the node format the scene holds
     const LaunchPlan pl = plan_launch(s);
-    if (!pl.ok || pl.f64 || s.bvh_width != 2u || pl.kclass == 3) return hipErrorInvalidValue;
+    if (!pl.ok || pl.f64 || s.bvh_width != 2u || (!q.surf && s.n_media)) return hipErrorInvalidValue;
     q.nodes = s.nodes;
     q.prim_cr = s.prim_cr;
     q.prim_motion = s.prim_motion;
@@ -2416,6 +2504,20 @@ hipError_t launch_query(const KParams &s, QParams q, hipStream_t stream) {
         q.n_groups = (uint32_t)(((uint64_t)q.n + 63u) / 64u);
     }
     if (q.n_groups == 0u) return hipSuccess;
+    if (q.surf) {  // surface records: the epilogue's material class, and the form that passes over media
+        q.prim_mtl = s.prim_mtl;
+        q.perlin = s.perlin;
+        q.tex_pool = s.tex_pool;
+        q.texs = s.texs;
+        q.bg_mode = s.bg_mode;
+        for (int i = 0; i < 3; ++i) q.background[i] = s.background[i];
+        if (pl.kclass <= 0)
+            return s.image_tex ? launch_query_geom<kBook1Untextured, kSurfBook1Tex>(s, pl, q, stream)
+                               : launch_query_geom<kBook1Untextured, kSurfBook1>(s, pl, q, stream);
+        if (s.n_media) return launch_query_geom<kGeomSurfaces, kSurfBook2>(s, pl, q, stream);
+        if (pl.kclass == 1) return launch_query_geom<1, kSurfBook2>(s, pl, q, stream);
+        return launch_query_geom<2, kSurfBook2>(s, pl, q, stream);
+    }
     if (pl.kclass <= 0) return launch_query_geom<kBook1Untextured>(s, pl, q, stream);
     if (pl.kclass == 1) return launch_query_geom<1>(s, pl, q, stream);
     return launch_query_geom<2>(s, pl, q, stream);  // quads: the book-2 quad class and book 3

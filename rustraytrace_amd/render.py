@@ -586,6 +586,48 @@ class DeviceScene:
             out = buf.cpu().numpy()[: h * w * 2]
         return out.view(_lib.HIT_DTYPE).reshape(h, w).copy()
 
+    def surface(self, rays) -> np.ndarray:
+        """rrt_scene_surface: the closest-hit query of `rays` (_lib.RAY_DTYPE) answered with the hit's
+        HitRecord, _lib.SURFACE_DTYPE records: p, t, normal (against the ray), prim, albedo, kind, uv,
+        front_face; a miss has prim = _lib.NO_PRIM, kind = _lib.SURFACE_MISS and the background in albedo.
+        Constant media are passed over: the closest surface. Synchronous; f32 scenes."""
+        r = np.ascontiguousarray(rays, dtype=_lib.RAY_DTYPE).ravel()
+        out = np.zeros(len(r), dtype=_lib.SURFACE_DTYPE)
+        _lib.check(self._lib.rrt_scene_surface(self._h, _lib.ptr(r), len(r), _lib.ptr(out)))
+        return out
+
+    def surface_async(self, d_rays_ptr: int, n: int, d_out_ptr: int, stream_ptr: int = 0) -> None:
+        """rrt_scene_surface_async: n RAY_DTYPE records at d_rays_ptr answered into n SURFACE_DTYPE records
+        at d_out_ptr (device memory, 16-byte aligned), enqueued on the stream behind the updates and refits on it."""
+        _lib.check(self._lib.rrt_scene_surface_async(self._h, ctypes.c_void_p(d_rays_ptr), int(n), ctypes.c_void_p(d_out_ptr),
+                                                     ctypes.c_void_p(stream_ptr)))
+
+    def primary_surface_async(self, d_out_ptr: int, time: float = 0.0, stream_ptr: int = 0) -> None:
+        """rrt_scene_primary_surface_async: height x width SURFACE_DTYPE records at d_out_ptr (device
+        memory), record (y, x) the surface record of primary_hits_async's ray through pixel (x, y)."""
+        _lib.check(self._lib.rrt_scene_primary_surface_async(self._h, ctypes.c_float(time), ctypes.c_void_p(d_out_ptr),
+                                                             ctypes.c_void_p(stream_ptr)))
+
+    def primary_surface(self, time: float = 0.0) -> np.ndarray:
+        """primary_surface_async into a torch buffer on the scene's device, synchronised: an (H, W) array
+        of SURFACE_DTYPE (the G-buffer of the current camera: albedo, normal, position, depth, id)."""
+        import torch
+
+        h, w = self.scene.height, self.scene.width
+        with torch.cuda.device(self.device):
+            buf = torch.zeros(max(h * w, 1) * 16, dtype=torch.int32, device=f"cuda:{self.device}")
+            self.primary_surface_async(buf.data_ptr(), time, torch.cuda.current_stream().cuda_stream)
+            torch.cuda.current_stream().synchronize()
+            out = buf.cpu().numpy()[: h * w * 16]
+        return out.view(_lib.SURFACE_DTYPE).reshape(h, w).copy()
+
+    def testing_fail_update(self) -> str:
+        """rrt_testing_scene_fail_update (test support): leaves the scene invalid, as a change that failed
+        midway does; returns the message. A later update that succeeds makes it valid again."""
+        rc = self._lib.rrt_testing_scene_fail_update(self._h)
+        assert rc == -1, rc
+        return self._lib.rrt_hip_last_error().decode()
+
     def update_spheres(self, spheres, motion=None, stream_ptr: int = 0) -> None:
         """rrt_scene_update_spheres: replaces the spheres (and, for a book-2 world, their motion rows;
         None = all zero) of a DeviceScene(device_bvh=True), rebuilds the BVH on the device and re-forms
